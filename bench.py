@@ -24,6 +24,11 @@ leg right behind the timed region and the overlapped times are kept under `roofl
 is the oracle (a port of the reference's CPU path, pinned against golden vectors) timed on a bounded
 sample of the same workload on this box's host cores -- the SAME slices, weights and dropout masks as the
 last timed step, so the sample doubles as the parity check of the timed output (`parity`).
+
+A plain run does only what the headline needs: set up, warm up, time `--steps` steps, write the outputs of the last timed step if
+`--dump-outputs DIR` is given, and print the JSON line (`value`, `ms_per_step`, `config`, ...).  Everything described above that is
+not the timed region itself -- the per-kernel HIP events and the roofline, the resident and all-outputs legs, the standalone aggregation
+and calibration kernel probes, the CPU baseline and the parity checks, the native-shape sub-record -- runs with `--full`.
 """
 import argparse
 import json
@@ -437,9 +442,9 @@ def plan_fingerprint(layers, samples_per_launch):
 
 
 def native_sub_record(T, lanes, steps=4, warmup=1):
-    """`python bench.py --workload brats-native --brief` as a child process (started fresh: no exec from this GPU-touched process), condensed."""
+    """`python bench.py --workload brats-native --full --brief` as a child process (started fresh: no exec from this GPU-touched process), condensed."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--workload', 'brats-native', '--brief', '--steps', str(steps), '--warmup', str(warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), '--workload', 'brats-native', '--full', '--brief', '--steps', str(steps), '--warmup', str(warmup),
            '--mc', str(T), '--lanes', str(lanes), '--cpu-budget', '8']
     try:
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600, env=dict(os.environ, RCU_BENCH_NATIVE='0'))
@@ -473,6 +478,80 @@ def sharding_record(runner, world, args, n_slices, height, width, v_step):
                 statistics='exact float64 sums ({} planes of {} voxels)'.format(planes, vox), volumes_per_step=v_step)
 
 
+def headline_record(args, model, runner, feeder, world, T, isic, native, n_slices, height, width, v_step, samples_per_launch, elapsed,
+                    unit_name):
+    """The head of the JSON line -- metric, value, unit, ms_per_step, config -- from the timed region alone (plain and --full runs alike)."""
+    layers = model.layer_table(height, width, n_slices * args.pass_group)
+    units = T * (n_slices if isic else 1)
+    shape = '{}x{}x{}'.format(ISIC_CHANNELS, height, width) if isic else '4x{}x{}x{}'.format(n_slices, height, width)
+    return {
+        'metric': ('ensemble-member-{}s/sec ({}, K={})'.format(unit_name, shape, T) if args.ensemble
+                   else 'MC-sample-{}s/sec ({}, T={}{}{})'.format(unit_name, shape, T, ', sigma head' if args.aleatoric else '',
+                                                                 ', all outputs' if args.all_outputs else '')),
+        'value': units * args.steps / elapsed,
+        'unit': 'member-{}s/s'.format(unit_name) if args.ensemble else 'MC-sample-{}s/s'.format(unit_name),
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True,
+        'scaling': 'strong',
+        'vs_baseline': None,
+        'dtype': 'f32',
+        'data': 'synthetic',
+        'config': {'workload': ('ISIC {}: 2D U-Net(2,3,depth 4,start_filters 32,dropout 0.05) over a batch of {} images of 3x{}x{}, '
+                                '{} + mean/entropy aggregation per step'
+                                .format('ensemble' if args.ensemble else 'baseline_mc', n_slices, height, width,
+                                        '{} members'.format(T) if args.ensemble else
+                                        'T={} MC-dropout passes{}'.format(T, '' if args.no_ws else ' + weight-scaling pass'))) if isic else
+                               ('BraTS ensemble: {} U-Net(2,4,depth 4,start_filters 32) members over {} slices of 4x{}x{} '
+                                '+ mean/entropy aggregation per step'.format(T, n_slices, height, width)) if args.ensemble else
+                               ('BraTS {}: 2D U-Net(2,4,depth 4,start_filters 32,dropout 0.05{}) over {} slices '
+                                'of 4x{}x{}{}, T={} MC-dropout passes{} + mean/entropy aggregation per step'
+                                .format('aleatoric + MC' if args.aleatoric else 'baseline_mc', ', sigma_out' if args.aleatoric else '',
+                                        n_slices, height, width, ' (the reference\'s uncropped BraTS slices: padded levels)' if native else '',
+                                        T, '' if args.no_ws else ' + weight-scaling pass')),
+                   'T': T, 'ws_pass': not (args.no_ws or args.ensemble), 'slices': n_slices, 'height': height, 'width': width,
+                   'pass_group': args.pass_group, 'lanes': args.lanes, 'volumes_per_step': v_step, 'samples_per_launch': samples_per_launch,
+                   # real extent -> allocated extent of every level (rcu_unet_options.pad_levels: a level that is not whole Winograd tiles is padded)
+                   'level_extents': sorted({'{}x{} -> {}x{}'.format(L['height'], L['width'], L['grid_height'], L['grid_width'])
+                                            for L in layers if not L['upsample']}, key=lambda t: -int(t.split('x')[0])),
+                   'outputs': 'mean + entropy + mutual information + variance (float64 statistics)' if args.all_outputs else
+                              'mean + entropy (MultiPredictionSummary() as every shipped script constructs it)',
+                   'h2d': 'prefetched, inside timed region ({} MB per {} from pinned host memory on a copy stream, one event wait per '
+                          '{}; rechun/dl/customsteps.py:20)'.format(feeder.bytes // 1000000, unit_name if not isic else 'batch',
+                                                                    unit_name if not isic else 'batch'),
+                   'sharding': sharding_record(runner, world, args, n_slices, height, width, v_step) if world > 1 else 'none',
+                   # canonical direct-convolution FLOPs of one forward pass (the layer table's per-slice counts)
+                   'gflop_per_sample_{}'.format(unit_name): sum(L['flops_per_slice'] for L in layers) * n_slices / 1e9 / (n_slices if isic else 1)},
+    }
+
+
+DUMP_BUDGET_BYTES = 64000000
+DUMP_SAMPLE_SEED = 20
+
+
+def dump_outputs(out, directory, budget=DUMP_BUDGET_BYTES):
+    """The arrays of the last timed step (name -> device tensor) as directory/<name>.npy, float32 (float64 stays float64).  If they take
+    more than `budget` bytes in all, every array keeps the same seeded sample of its leading-axis rows (sorted), so that two runs with the
+    same arguments write the same elements.  -> {name: shape written}"""
+    arrays = {}
+    for name, t in sorted(out.items()):
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if total > budget and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (budget * 0.99) // total))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
+
+
 def split_masks(model, flat, n, rows):
     """Concatenated device mask tensor [site][n][C_site] -> list of per-site [len(rows), C_site] CPU tensors."""
     out, off = [], 0
@@ -493,8 +572,8 @@ def main():
                          'brats-native / isic-native: the shapes of the reference\'s real data, 155 slices of 4x240x240 / 32 images of 3x192x256 '
                          '(padded levels)')
     ap.add_argument('--brief', action='store_true',
-                    help='the timed region, roofline and parity only: no all-outputs leg, no standalone aggregation / calibration kernel probes, '
-                         'no native-shape sub-record (what the default run\'s `native_shapes` child runs with)')
+                    help='with --full: the timed region, roofline and parity only -- no all-outputs leg, no standalone aggregation / calibration kernel probes, '
+                         'no native-shape sub-record (what the --full run\'s `native_shapes` child runs with)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-budget', type=float, default=24.0, help='seconds of CPU work the oracle leg may take (bounded sample)')
     ap.add_argument('--ws-transport', choices=('reduce', 'p2p'), default=None,
@@ -518,6 +597,12 @@ def main():
     ap.add_argument('--volumes-per-step', type=int, default=0,
                     help='consecutive volumes a rank takes as ONE batch of 160 v slices, its passes of them in one launch (0 = the rule of '
                          'volumes_per_step(): 1 while a rank\'s share of a volume fills 640-sample launches, 2 at 8 ranks)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the timed region: per-kernel events and roofline, resident and all-outputs legs, aggregation / '
+                         'calibration kernel probes, CPU baseline, parity, native-shape sub-record (a plain run times the steps and nothing else)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64); above {} MB in all, the same '
+                         'seeded sample of leading-axis rows (slices / images) of every array'.format(DUMP_BUDGET_BYTES // 1000000))
     ap.add_argument('--watchdog', type=float, default=1500.0,
                     help='seconds after which a run that has not finished dumps the stacks of all threads to stderr and exits (0 = off)')
     args = ap.parse_args()
@@ -678,6 +763,8 @@ def main():
     # (ensemble members keep to one stream lane: a member of a side lane never runs on its lane-0 handle -- which is the one these
     # calls create and time -- so it is left alone here: 6 GB of workspace per member that nobody would use)
     timed_members = [(i, m) for i, m in enumerate(members) if not (args.ensemble and args.lanes > 1 and i % args.lanes != 0)]
+    if not args.full:
+        timed_members = []          # a plain run: no per-kernel events in the timed region
     for i, m in timed_members:
         count = sum(1 for j in my_jobs if j - 1 == i) if args.ensemble else len(my_jobs)
         m.profile_begin(height, width, samples_per_launch, max(count, 1))
@@ -715,6 +802,24 @@ def main():
     else:
         devices_seen = [device_identity(device, rank)]
     n_ranks_seen = dist.get_world_size() if collective else 1
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(out, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            result = headline_record(args, model, runner, feeder, world, T, isic, native, n_slices, height, width, v_step, samples_per_launch,
+                                     elapsed, unit_name)
+            result.update(n_ranks_seen=n_ranks_seen, devices=devices_seen,
+                          distinct_devices=len({(d_['uuid'], d_['pci'], d_['device_index']) for d_ in devices_seen}),
+                          forwards_per_rank=forwards_per_rank, device_allocs_in_timed_region=device_allocs_in_timed_region)
+            if force_pg:
+                result['rccl_rehearsal'] = dict(backend=dist.get_backend(), world=dist.get_world_size(), ws_transport=runner.ws_transport,
+                                                p2p_messages=runner.p2p_messages,
+                                                note='RCU_BENCH_FORCE_PG=1: one-rank process group, every step through the exchange path')
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(result) + '\n').encode())
+        if collective:
+            dist.destroy_process_group()
+        return
 
     launches, slot_ms = 0, None
     for _, m in timed_members:
@@ -996,44 +1101,9 @@ def main():
             rec['slices_compared'] = [int(v) for v in sel]
 
     units = T * (n_slices if isic else 1)
-    shape = '{}x{}x{}'.format(ISIC_CHANNELS, height, width) if isic else '4x{}x{}x{}'.format(n_slices, height, width)
-    result = {
-        'metric': ('ensemble-member-{}s/sec ({}, K={})'.format(unit_name, shape, T) if args.ensemble
-                   else 'MC-sample-{}s/sec ({}, T={}{}{})'.format(unit_name, shape, T, ', sigma head' if args.aleatoric else '',
-                                                                 ', all outputs' if args.all_outputs else '')),
-        'value': units * args.steps / elapsed,
-        'unit': 'member-{}s/s'.format(unit_name) if args.ensemble else 'MC-sample-{}s/s'.format(unit_name),
-        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': elapsed / args.steps * 1e3,
-        'higher_is_better': True,
-        'scaling': 'strong',
-        'vs_baseline': None,
-        'dtype': 'f32',
-        'data': 'synthetic',
-        'config': {'workload': ('ISIC {}: 2D U-Net(2,3,depth 4,start_filters 32,dropout 0.05) over a batch of {} images of 3x{}x{}, '
-                                '{} + mean/entropy aggregation per step'
-                                .format('ensemble' if args.ensemble else 'baseline_mc', n_slices, height, width,
-                                        '{} members'.format(T) if args.ensemble else
-                                        'T={} MC-dropout passes{}'.format(T, '' if args.no_ws else ' + weight-scaling pass'))) if isic else
-                               ('BraTS ensemble: {} U-Net(2,4,depth 4,start_filters 32) members over {} slices of 4x{}x{} '
-                                '+ mean/entropy aggregation per step'.format(T, n_slices, height, width)) if args.ensemble else
-                               ('BraTS {}: 2D U-Net(2,4,depth 4,start_filters 32,dropout 0.05{}) over {} slices '
-                                'of 4x{}x{}{}, T={} MC-dropout passes{} + mean/entropy aggregation per step'
-                                .format('aleatoric + MC' if args.aleatoric else 'baseline_mc', ', sigma_out' if args.aleatoric else '',
-                                        n_slices, height, width, ' (the reference\'s uncropped BraTS slices: padded levels)' if native else '',
-                                        T, '' if args.no_ws else ' + weight-scaling pass')),
-                   'T': T, 'ws_pass': not (args.no_ws or args.ensemble), 'slices': n_slices, 'height': height, 'width': width,
-                   'pass_group': g, 'lanes': args.lanes, 'volumes_per_step': v_step, 'samples_per_launch': samples_per_launch,
-                   # real extent -> allocated extent of every level (rcu_unet_options.pad_levels: a level that is not whole Winograd tiles is padded)
-                   'level_extents': sorted({'{}x{} -> {}x{}'.format(L['height'], L['width'], L['grid_height'], L['grid_width'])
-                                            for L in layers if not L['upsample']}, key=lambda t: -int(t.split('x')[0])),
-                   'outputs': 'mean + entropy + mutual information + variance (float64 statistics)' if args.all_outputs else
-                              'mean + entropy (MultiPredictionSummary() as every shipped script constructs it)',
-                   'h2d': 'prefetched, inside timed region ({} MB per {} from pinned host memory on a copy stream, one event wait per '
-                          '{}; rechun/dl/customsteps.py:20)'.format(feeder.bytes // 1000000, unit_name if not isic else 'batch',
-                                                                    unit_name if not isic else 'batch'),
-                   'sharding': sharding_record(runner, world, args, n_slices, height, width, v_step) if world > 1 else 'none',
-                   'gflop_per_sample_{}'.format(unit_name): conv_flops / passes_run / 1e9 / (n_slices if isic else 1)},
+    result = headline_record(args, model, runner, feeder, world, T, isic, native, n_slices, height, width, v_step, samples_per_launch,
+                             elapsed, unit_name)
+    result.update({
         'n_ranks_seen': n_ranks_seen,
         'devices': devices_seen,
         'distinct_devices': len({(d_['uuid'], d_['pci'], d_['device_index']) for d_ in devices_seen}),
@@ -1047,7 +1117,7 @@ def main():
         'cpu_baseline': cpu,
         'parity': parity,
         'all_outputs': all_out,
-    }
+    })
     # ---- the reference's real BraTS shape as a sub-record of the default run (a child process: this process keeps its plans; the child has the
     # GPU to itself while rank 0 waits), with its own roofline and parity -- never in the headline's place
     if (args.workload == 'brats' and world == 1 and not (args.brief or args.ensemble or args.aleatoric or args.all_outputs or args.no_cpu_baseline)

@@ -46,7 +46,7 @@ def test_bench_two_ranks_through_torch_distributed_run(extra):
     import json
     env = dict(os.environ, RCU_BENCH_SINGLE_DEVICE='1', RCU_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
-           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
+           '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '2',
            '--warmup', '1'] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -67,7 +67,7 @@ def test_bench_takes_several_volumes_per_step_and_reports_its_devices():
     import json
     env = dict(os.environ, RCU_BENCH_SINGLE_DEVICE='1', RCU_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port',
-           str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--mc', '4', '--volumes-per-step', '2']
+           str(_free_port()), os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1', '--mc', '4', '--volumes-per-step', '2']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
@@ -92,7 +92,7 @@ def test_bench_plain_command_line_starts_its_own_ranks():
     import json
     env = dict(os.environ, RCU_BENCH_SINGLE_DEVICE='1', RCU_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('WORLD_SIZE', None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--mc', '5']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--mc', '5']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -124,7 +124,7 @@ def test_rccl_world1_rehearsal_matches_the_plain_step_bit_for_bit():
         assert d[transport]['inflight_after_drain'] == 0
     env = dict(env, RCU_BENCH_FORCE_PG='1')
     env.pop('WORLD_SIZE', None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--mc', '4', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--mc', '4', '--no-cpu-baseline']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=800, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     b = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
