@@ -340,6 +340,42 @@ int rcu_unc_counts_from_p(const float* p_foreground_dev, const uint8_t* predicti
 int rcu_normalised_entropy(const float* p_foreground_dev, size_t n, double* out_f64_dev, float* out_f32_dev,
                            void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time augmentation (EXTENSION: the reference has no TTA; rcu_amd.steps.TtaMcPredictStep)
+ *   The network runs on transformed copies g(x) of every slice, the statistics of those passes are mapped back with g^-1 and added to
+ *   the canonical statistics.  The transforms are the eight elements of the dihedral group D4 acting on the last two axes (H, W) of an
+ *   NCHW tensor, each defined by its torch equivalent:
+ *     0 identity        x                                      4 transpose        x.transpose(-2, -1)
+ *     1 flip_h          x.flip(-1)                             5 rot90            torch.rot90(x, 1, (-2, -1))
+ *     2 flip_v          x.flip(-2)                             6 rot270           torch.rot90(x, 3, (-2, -1))
+ *     3 rot180          x.flip(-2, -1)                         7 anti_transpose   torch.rot90(x, 2, (-2, -1)).transpose(-2, -1)
+ *   Codes 0-4 and 7 are their own inverses; rot90 and rot270 are each other's.  Codes 4-7 swap H and W: they are accepted for square
+ *   planes only (BraTS 240 x 240 -- not ISIC 192 x 256), elsewhere the call fails with RCU_ERR_INVALID (never a silent skip).
+ *   Dropout masks of a transformed pass: rcu_dropout_masks at first_sample = the slice's global index under a key of (seed, element,
+ *   pass) alone -- the identity's key is the plain MC key of the pass, every other element's differs from all of those and from each
+ *   other's for passes 1..RCU_MC_EXACT_MAX_PASSES (rcu_amd.steps.tta_pass_seed).
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_TTA_IDENTITY 0
+#define RCU_TTA_FLIP_H 1
+#define RCU_TTA_FLIP_V 2
+#define RCU_TTA_ROT180 3
+#define RCU_TTA_TRANSPOSE 4
+#define RCU_TTA_ROT90 5
+#define RCU_TTA_ROT270 6
+#define RCU_TTA_ANTI_TRANSPOSE 7
+
+/* out = g(x), x and out [n][channels][H][W] float32, out != x (the two must not overlap); codes 4-7 need H == W.  n, channels, H, W >= 1. */
+int rcu_tta_transform(const float* x_dev, size_t n, int channels, int height, int width, int element, float* out_dev, void* stream);
+/* dst += g^-1(src), plane by plane, over the rcu_mc_stats_bytes layout (n entries, hw = H*W, flags as for rcu_mc_begin: a combination of
+ * RCU_MC_MI, RCU_MC_VAR, RCU_MC_EXACT, anything else is RCU_ERR_INVALID): src holds statistics accumulated from images transformed by g.
+ * Every plane of the layout is folded -- the C class sums, the C sums of p^2 (VAR), the entropy sum (MI) -- with one addition per element:
+ * dst[v] + src[g(v)].  Under RCU_MC_EXACT the addition is exact, so the merged statistics do not depend on the order of the folds; in the
+ * float32 and the plain float64 (VAR without EXACT) forms the result is that of the folds in call order, each one a single rounded addition
+ * per element (rcu_amd.steps.TtaMcPredictStep folds a lane's transforms in the order the transforms are given, then adds the side lanes'
+ * statistics into lane 0's in lane order).  src and dst must not overlap. */
+int rcu_mc_fold_transformed(const void* src_stats_dev, void* dst_stats_dev, size_t n, int height, int width, int nb_classes, int flags,
+                            int element, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ RCU_MC_EXACT = 8
 RCU_MC_EXACT_MAX_PASSES = 2048
 RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
+# test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
+TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
 class RcuError(RuntimeError):
@@ -111,6 +113,8 @@ SIGNATURES = {
     'rcu_unc_from_p_workspace_bytes': (c_size_t, [c_size_t, c_int]),
     'rcu_unc_counts_from_p': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
                                       c_void_p]),
+    'rcu_tta_transform': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_mc_fold_transformed': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@ static int fail(int code, const std::string& msg)
     g_last_error = msg;
     return code;
 }
+int rcu::report_error(int code, const std::string& msg) { return fail(code, msg); }
 static int hip_fail(hipError_t e, const char* what)
 {
     return fail(RCU_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));

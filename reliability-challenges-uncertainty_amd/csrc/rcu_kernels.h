@@ -4,7 +4,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+
 namespace rcu {
+
+// rcu_last_error() of the calling thread := msg; returns code (the entry points of the other translation units report through it, rcu_api.hip)
+int report_error(int code, const std::string& msg);
 
 // ---------------------------------------------------------------------------------------------
 // conv3x3 implicit GEMM (rcu_conv.hip)

@@ -16,7 +16,7 @@ issues the reduce on RCCL's own stream, finalises on a side stream of the root a
 ``PendingSummary``; the compute stream of every rank goes straight on to its share of the next
 volume (T+1 = 21 jobs on 8 GPUs: 21 forward passes per rank per 8 volumes instead of 3 per volume).
 
-Behind the drop-in scripts: ``ShardedMcPredictStep`` / ``ShardedEnsemblePredictionStep`` are the ``BatchStep`` forms of the runners;
+Behind the drop-in scripts: ``ShardedMcPredictStep`` / ``ShardedEnsemblePredictionStep`` / ``ShardedTtaMcPredictStep`` are the ``BatchStep`` forms of the runners;
 ``rcu_amd.scripts`` picks them when the script runs under ``python -m torch.distributed.run`` (``world_from_env``): every rank iterates
 the same loader, the root alone assembles, evaluates and writes.  Masks are a function of (seed, batch, pass) and the statistics are
 exact sums (rcu_amd.steps.McStatistics), so the files an N-rank run writes are the files the one-process run writes, byte for byte.
@@ -483,6 +483,81 @@ class ShardedEnsembleRunner(ShardedMcRunner):
         self.forwards_run += 1
 
 
+class ShardedTtaMcRunner(ShardedMcRunner):
+    """EXTENSION -- test-time augmentation sharded over the ranks (rcu_amd.steps.TtaMcPredictStep): the jobs of a volume are the weight-scaling
+    pass (job 0) and the V x T (transform, pass) pairs, job 1 + v * T + (t - 1) = pass t of transform ``elements[v]`` (T = max(mc_steps, 1);
+    mc_steps = 0: one eval-mode pass per transform), assigned round robin as ShardedMcRunner's.  A rank runs its consecutive passes of one
+    transform as pass groups over its stream lanes, into a per-lane statistics blob that is folded into the lane's canonical statistics
+    (rcu_mc_fold_transformed) once the rank's passes of that transform are done; the side lanes are added into lane 0 and the ONE sum-reduce of
+    the base class merges the ranks.  Exact sums: an N-rank run gives the bytes of the one-process step."""
+
+    def __init__(self, model, transforms, mc_steps=0, ws_pass=True, rank=0, world=1, do_mi=False, do_var=False, root=0, seed=0, pass_group=1,
+                 lanes=1, ws_transport=None, exact=True, engine=None):
+        self.elements = steps_mod.tta_elements(transforms)
+        self.tta_mc_steps = int(mc_steps)
+        self.per_transform = max(self.tta_mc_steps, 1)
+        super().__init__(model, len(self.elements) * self.per_transform, ws_pass=ws_pass, rank=rank, world=world, engine=engine, do_mi=do_mi,
+                         do_var=do_var, root=root, seed=seed, pass_group=pass_group, lanes=lanes, ws_transport=ws_transport, exact=exact)
+
+    def job_pair(self, job):
+        """MC job id (1 .. V*T) -> (element code, pass 1..T)."""
+        return self.elements[(job - 1) // self.per_transform], (job - 1) % self.per_transform + 1
+
+    def _masks(self, x, element, passes, step_index):
+        if self.tta_mc_steps == 0:
+            return None
+        return self.engine.seeded_masks(x, [steps_mod.tta_pass_seed(self.seed, element, t) for t in passes], self.first_sample(x, step_index))
+
+    def _run_jobs(self, x, step_index, mask_sets):
+        if mask_sets is not None:
+            raise ValueError('the TTA runner draws its masks itself (seeded): no injected mask sets')
+        flat, stats, ws = self.engine.buffers(x, self.ws_pass)
+        jobs = self.jobs_of(step_index, self.rank)
+        lanes = steps_mod.StreamLanes(x.device, self.lanes if x.is_cuda else 1)
+        pass_group = self.pass_group if self.group_samples is None else max(1, int(self.group_samples) // int(x.shape[0]))
+        # the canonical plan of the one-process step: n x min(group, T) samples on every lane
+        self.engine.reserve(x, self.tta_mc_steps, pass_group, lanes.count)
+        # this rank's (transform, passes) launches: consecutive passes of one transform, at most pass_group per launch
+        runs = collections.OrderedDict()
+        for j in jobs:
+            if j != 0:
+                e, t = self.job_pair(j)
+                runs.setdefault(e, []).append(t)
+        xs = {e: (x if e == 0 else steps_mod.tta_transform(x, e)) for e in runs}
+        lanes.begin(stats, lambda: self.engine.side_statistics(x), inputs=tuple(xs.values()), first=step_index if self.world > 1 else 0)
+        if 0 in jobs:      # the weight-scaling pass writes into the volume's buffer: lane 0, outside the rotation
+            self._run_job(0, x, stats, ws, None, step_index)
+        scratch = [None] * lanes.count
+        for e, passes in runs.items():
+            used = []
+            for b in range(0, len(passes), pass_group):
+                group = passes[b:b + pass_group]
+
+                def launch(st, lane, e=e, group=group):
+                    if e != 0:
+                        if scratch[lane] is None:
+                            scratch[lane] = self.engine.side_statistics(x)      # (zeroed on the lane's stream)
+                        st = scratch[lane]
+                    if self.tta_mc_steps == 0:
+                        self.engine.member_pass(self.engine.model, xs[e], st, lane=lane)
+                    else:
+                        self.engine.mc_pass(xs[e], st, self._masks(x, e, group, step_index), passes=len(group), lane=lane)
+                lane = lanes._launch % lanes.count
+                lanes.run(launch)
+                if lane not in used:
+                    used.append(lane)
+                self.forwards_run += len(group)
+            if e != 0:
+                for lane in sorted(used):
+                    def fold(st, lane, e=e):
+                        steps_mod.fold_transformed(scratch[lane], st, e)
+                        steps_mod.restart_statistics(scratch[lane])
+                    lanes.run(fold, lane=lane)
+        if lanes.count > 1:
+            lanes.end(self.engine.merge)
+        return flat, stats, ws
+
+
 class PendingStatistics:
     """What a sharded predict step leaves under ``multi_probabilities`` on the root: the merged statistics of the batch, valid once the
     collective has completed.  ``MultiPredictionSummary`` calls ``finalize_when_merged``: the finalize (and the hand-over of the
@@ -690,4 +765,38 @@ class ShardedEnsemblePredictionStep(_ShardedStepBase):
                                                  lanes=min(self.lanes, len(members)), share_workspace=self.share_workspace, exact=self.exact,
                                                  engine=self._engine(members[0]))
             self._runner_key = key
+        self._hand_over(batch_context, self._runner, images, batch_context.batch_index)
+
+
+class ShardedTtaMcPredictStep(_ShardedStepBase):
+    """``rcu_amd.steps.TtaMcPredictStep`` with the weight-scaling pass and the V x T (transform, pass) jobs of every batch sharded over the
+    ranks (``ShardedTtaMcRunner``); every rank calls the step with the SAME batch, the root's batch context receives what the one-process
+    step leaves there."""
+
+    def __init__(self, transforms, world, mc_steps=0, seed=0, lanes=None, group_pixels=None, exact=True, do_mi=False, do_var=False, ws_pass=True,
+                 ws_transport=None, engine_factory=None) -> None:
+        self.elements = steps_mod.tta_elements(transforms)
+        samples = len(self.elements) * max(int(mc_steps), 1)
+        super().__init__(world, do_mi, do_var, lanes, bool(exact) and samples <= steps_mod._lib.RCU_MC_EXACT_MAX_PASSES, engine_factory)
+        if seed is None and int(mc_steps) > 0:
+            raise ValueError('a sharded MC step needs a seed: the masks of a pass must not depend on the rank that runs it')
+        self.mc_steps, self.seed, self.ws_pass = int(mc_steps), seed, ws_pass
+        self.group_pixels = steps_mod.McPredictStep.GROUP_PIXELS if group_pixels is None else group_pixels
+        self.ws_transport = ws_transport
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        steps_mod._check_context(context)
+        images = steps_mod._images_to_device(batch_context, context)
+        model = context.model
+        n, _, h, w = images.shape
+        steps_mod.check_tta_shape(self.elements, h, w)
+        group = max(1, min(steps_mod.pass_group_size(model, n, h, w, self.group_pixels), max(self.mc_steps, 1)))
+        if self._runner_key != id(model):
+            if self._runner is not None:
+                self._runner.drain()
+            self._runner = ShardedTtaMcRunner(model, self.elements, self.mc_steps, ws_pass=self.ws_pass, rank=self.rank, world=self.world,
+                                              do_mi=self.do_mi, do_var=self.do_var, seed=self.seed, pass_group=group, lanes=self.lanes,
+                                              ws_transport=self.ws_transport, exact=self.exact, engine=self._engine(model))
+            self._runner_key = id(model)
+        self._runner.pass_group = group
         self._hand_over(batch_context, self._runner, images, batch_context.batch_index)

@@ -333,7 +333,7 @@ class PrepareSubjectStep(steps.BatchStep):
 
 def _other(context, key, default=None):
     """A key of the YAML file's free-form ``others`` (rcu_amd extensions, absent from the reference's configs: coalesce_pixels, pipelined,
-    max_inflight, stream_lanes, device_metrics)."""
+    max_inflight, stream_lanes, device_metrics, tta)."""
     return getattr(context.config.others, key, default)
 
 
@@ -353,7 +353,33 @@ def _mask_seed(context, world):
     return seed
 
 
+def _tta_steps(context, world):
+    """``others.tta`` (an rcu_amd extension): test-time augmentation over the listed D4 transforms (include/rcu.h), composed with ``others.mc``
+    when that is set (V transforms x T passes, with the weight-scaling pass as the MC step runs it), else alone in eval mode (V passes, no
+    weight-scaling pass) -- in place of the predict step, followed by MultiPredictionSummary, whose ``probabilities`` the writer saves."""
+    others = context.config.others
+    transforms = others.tta
+    if isinstance(transforms, str):
+        transforms = [transforms]
+    mc = int(getattr(others, 'mc', 0) or 0)
+    lanes, group_pixels, exact = _other(context, 'stream_lanes'), _other(context, 'group_pixels'), bool(_other(context, 'exact', True))
+    seed = _mask_seed(context, world) if mc > 0 else None
+    if world.world > 1:
+        step = rdist.ShardedTtaMcPredictStep(transforms, world, mc_steps=mc, seed=0 if seed is None else seed, lanes=lanes,
+                                             group_pixels=group_pixels, exact=exact, ws_pass=mc > 0)
+    else:
+        step = steps.TtaMcPredictStep(transforms, mc_steps=mc, seed=seed, lanes=lanes, group_pixels=group_pixels, exact=exact, ws_pass=mc > 0)
+    return [step, steps.MultiPredictionSummary()]
+
+
+def _refuse_tta(context, script):
+    if hasattr(context.config.others, 'tta'):
+        raise ValueError('others.tta (test-time augmentation) applies to the default test scripts only; the {} script does not take it'.format(script))
+
+
 def _default_steps(context, world):
+    if hasattr(context.config.others, 'tta'):
+        return _tta_steps(context, world)
     if hasattr(context.config.others, 'mc'):
         lanes = _other(context, 'stream_lanes')
         # ``others.group_pixels`` / ``others.exact`` (rcu_amd extensions): the memory / reproducibility trade of the MC step.  Every stream lane of every
@@ -499,6 +525,7 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_ensemble.yaml'.format(dataset)))
+    _refuse_tta(context, 'ensemble')
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
     if world.world > 1:     # the K members of every batch sharded over the ranks (bin-dl/brats_test_ensemble.py:44-59 on N GPUs)
@@ -510,6 +537,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
 
 def test_aleatoric(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_aleatoric.yaml'.format(dataset)))
+    _refuse_tta(context, 'aleatoric')
     return _run(context, dataset, [steps.AleatoricPredictStep()], WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world)
 
@@ -650,6 +678,7 @@ def _single_rank_only(world):
 
 def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_feat.yaml'.format(dataset)))
+    _refuse_tta(context, 'auxiliary_feat')
     if not _single_rank_only(world):
         return context
     test_model = _load_segmentation_model(context)
@@ -670,6 +699,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
 
 def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_segm.yaml'.format(dataset)))
+    _refuse_tta(context, 'auxiliary_segm')
     if not _single_rank_only(world):
         return context
     if dataset == 'brats':

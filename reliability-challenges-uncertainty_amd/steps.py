@@ -8,6 +8,7 @@ Mirrors (names, arguments, output keys, error behaviour):
   EnsemblePredictionStep        bin-dl/brats_test_ensemble.py:72-94
   AleatoricPredictStep          bin-dl/brats_test_aleatoric.py:51-73
   AleatoricMcPredictStep        extension (BASELINE config 'aleatoric + MC'): composition of the two above
+  TtaMcPredictStep              extension: test-time augmentation (D4 transforms), alone or composed with MC dropout
   BatchContext / TaskContext    common/trainloop/context.py:334-355
 A step is called as ``step(batch_context, task_context, context)``, reads
 ``batch_context.input['images']`` and writes torch tensors with the channel dim at 1 into
@@ -690,6 +691,244 @@ class AleatoricMcPredictStep(BatchStep):
             batch_context.output['sigma'] = sigma_sum.div_(float(max(self.mc_steps, 1)))
         finally:
             set_dropout_mode(model, is_train=False)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# test-time augmentation (EXTENSION; include/rcu.h "Test-time augmentation")
+# ------------------------------------------------------------------------------------------------------------------------------
+TTA_ELEMENTS = _lib.TTA_ELEMENTS                 # code -> name: the eight elements of D4 on (H, W)
+TTA_INVERSE = (0, 1, 2, 3, 4, 6, 5, 7)           # code -> code of the inverse element
+
+
+def tta_element(transform):
+    """Name or code of a D4 element -> its code (include/rcu.h RCU_TTA_*); ValueError for anything else."""
+    if isinstance(transform, str):
+        if transform not in TTA_ELEMENTS:
+            raise ValueError('unknown TTA transform "{}" (one of {})'.format(transform, ', '.join(TTA_ELEMENTS)))
+        return TTA_ELEMENTS.index(transform)
+    if isinstance(transform, bool) or not isinstance(transform, int) or not 0 <= transform < len(TTA_ELEMENTS):
+        raise ValueError('unknown TTA transform {!r} (a name or a code 0..7)'.format(transform))
+    return int(transform)
+
+
+def tta_elements(transforms):
+    """List of names / codes -> tuple of codes, in the given order; empty lists, unknown names and duplicates raise ValueError."""
+    if isinstance(transforms, (str, int)):
+        transforms = [transforms]
+    codes = tuple(tta_element(t) for t in transforms)
+    if not codes:
+        raise ValueError('TTA needs at least one transform')
+    if len(set(codes)) != len(codes):
+        raise ValueError('duplicate TTA transforms in {}'.format(list(transforms)))
+    return codes
+
+
+def tta_swaps_axes(element):
+    """Codes 4-7 (transpose, rot90, rot270, anti_transpose) swap H and W: square planes only."""
+    return tta_element(element) >= 4
+
+
+def tta_torch(x, element):
+    """The torch definition of element ``element`` on the last two axes (the contract the kernels are tested against)."""
+    e = tta_element(element)
+    if e == 0:
+        return x
+    if e == 1:
+        return x.flip(-1)
+    if e == 2:
+        return x.flip(-2)
+    if e == 3:
+        return x.flip(-2, -1)
+    if e == 4:
+        return x.transpose(-2, -1)
+    if e == 5:
+        return torch.rot90(x, 1, (-2, -1))
+    if e == 6:
+        return torch.rot90(x, 3, (-2, -1))
+    return torch.rot90(x, 2, (-2, -1)).transpose(-2, -1)
+
+
+def tta_pass_seed(seed, element, job):
+    """Key of the library's mask draw (rcu_dropout_masks) for MC pass ``job`` (1..T) of the images transformed by ``element``: a function of
+    (seed, element, pass) alone.  The identity's key IS ``pass_seed(seed, job)`` (TTA over [identity] is McPredictStep bit for bit); element e
+    adds e * 2^40, so for passes 1..2048 no key of one element equals a key of another (the differences e * 2^40 + (t - t') are non-zero and
+    far below the modulus 2^63 - 1)."""
+    return (pass_seed(seed, job) + tta_element(element) * (1 << 40)) % (2 ** 63 - 1)
+
+
+def tta_transform(x, element, out=None):
+    """``[N, C, H, W]`` float32 -> g(x) on the device (include/rcu.h rcu_tta_transform), into a new tensor or ``out``."""
+    e = tta_element(element)
+    x = x.to(torch.float32).contiguous()
+    n, c, h, w = x.shape
+    if e >= 4 and h != w:
+        raise ValueError('TTA transform "{}" swaps H and W and needs square slices, got {} x {}'.format(TTA_ELEMENTS[e], h, w))
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(_lib.load().rcu_tta_transform(_lib.ptr(x), n, c, h, w, e, _lib.ptr(out), _lib.current_stream()))
+    return out
+
+
+def fold_transformed(src, dst, element):
+    """``dst += g^-1(src)`` for two McStatistics of the same shape and flags (include/rcu.h rcu_mc_fold_transformed): ``src`` holds the passes
+    over images transformed by ``element``; the pass count moves along."""
+    if (src.n, src.nb_classes, src.height, src.width, src.flags) != (dst.n, dst.nb_classes, dst.height, dst.width, dst.flags):
+        raise ValueError('statistics of different shapes or flags cannot be folded')
+    _lib.check(_lib.load().rcu_mc_fold_transformed(_lib.ptr(src.blob), _lib.ptr(dst.blob), dst.n, dst.height, dst.width, dst.nb_classes, dst.flags,
+                                                   tta_element(element), _lib.current_stream()))
+    dst.count += src.count
+
+
+def restart_statistics(stats):
+    """Zero a statistics blob for reuse (rcu_mc_begin on the current stream)."""
+    _lib.check(_lib.load().rcu_mc_begin(_lib.ptr(stats.blob), stats.n, stats.hw, stats.nb_classes, stats.flags, _lib.current_stream()))
+    stats.count = 0
+
+
+def check_tta_shape(elements, h, w):
+    for e in elements:
+        if e >= 4 and h != w:
+            raise ValueError('TTA transform "{}" swaps H and W and needs square slices; the batch is {} x {}'.format(TTA_ELEMENTS[e], h, w))
+
+
+class TtaMcPredictStep(BatchStep):
+    """EXTENSION -- test-time augmentation, alone or composed with MC dropout (the reference has no TTA).  Every batch runs on its images
+    transformed by each element g of ``transforms`` (names or codes of include/rcu.h's D4 table, in the order given); the statistics of a
+    transform's passes are mapped back with g^-1 and added to the canonical statistics, so ``MultiPredictionSummary`` finalises V x T samples
+    (V transforms, T = ``mc_steps`` passes each) exactly as it finalises McPredictStep's T.
+      ``mc_steps = 0``: TTA alone, eval mode, one pass per transform (V samples) -- works with any checkpoint, MC config or not.
+      ``mc_steps = T``: T seeded dropout passes per transform.  The factors of (transform g, pass t) for the slice with global index s are
+      drawn at first_sample = s under ``tta_pass_seed(seed, g, t)`` -- for the identity the key of McPredictStep's pass t, so
+      ``transforms=['identity']`` gives McPredictStep's outputs bit for bit.  ``seed=None``: a seed drawn from torch's generator per batch.
+    A launch is one transform of the n images with a pass group of passes (the fused forward + softmax + statistics path, on the canonical plan
+    of McPredictStep); a transform's launches alternate over the stream lanes (the first lane rotating with the transform), each lane adds them
+    into a statistics blob of its own and folds that into the lane's canonical statistics (rcu_mc_fold_transformed) when the transform is done;
+    the identity's passes go into the canonical statistics directly.  The side lanes' statistics are added into lane 0's at the end.
+    ``exact`` (default; while V x T <= 2048): exact sums, the outputs do not depend on the transform order, the lanes, the pass groups or the
+    ranks; otherwise the result is that of the fold order above.  The weight-scaling pass (``ws_probabilities``) is the plain identity pass in
+    eval mode.  Transforms 4-7 swap H and W and are refused (ValueError) on batches that are not square."""
+
+    def __init__(self, transforms, mc_steps=0, seed=None, lanes=None, group_pixels=None, exact=True, do_mi=False, do_var=False, ws_pass=True,
+                 materialize=False) -> None:
+        super().__init__()
+        self.elements = tta_elements(transforms)
+        if int(mc_steps) < 0:
+            raise ValueError('mc_steps must be >= 0')
+        self.mc_steps = int(mc_steps)
+        self.seed = seed
+        self.lanes = McPredictStep.LANES if lanes is None else max(1, int(lanes))
+        self.group_pixels = McPredictStep.GROUP_PIXELS if group_pixels is None else group_pixels
+        self.samples = len(self.elements) * max(self.mc_steps, 1)
+        self.exact = bool(exact) and self.samples <= _lib.RCU_MC_EXACT_MAX_PASSES
+        self.do_mi, self.do_var = do_mi, do_var
+        self.ws_pass = ws_pass
+        self.materialize = materialize
+
+    @property
+    def passes_per_transform(self):
+        return max(self.mc_steps, 1)
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        _check_context(context)
+        images = _images_to_device(batch_context, context)
+        model = context.model
+        if not isinstance(model, model_mod.UNet):
+            raise ValueError('TtaMcPredictStep needs a rcu_amd.model.UNet (the transforms and the fold run on librcu_hip)')
+        n, _, h, w = images.shape
+        check_tta_shape(self.elements, h, w)
+        k = first_sample_of(batch_context, n)
+        seed = self.seed
+        if seed is None and self.mc_steps > 0:
+            seed = int(torch.randint(2 ** 31 - 1, (1,)).item())
+        group = pass_group_size(model, n, h, w, self.group_pixels)
+        reserve_canonical_plans(model, n, h, w, self.mc_steps, group, 1 if self.materialize else min(self.lanes, self.samples))
+
+        def ws_pass():
+            set_dropout_mode(model, is_train=False)
+            batch_context.output['ws_probabilities'] = softmax(model(images))
+
+        if self.materialize:
+            if self.ws_pass:
+                ws_pass()
+            batch_context.output['multi_probabilities'] = self._materialized(model, images, k, seed)
+        else:
+            batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, seed,
+                                                                      before=ws_pass if self.ws_pass else None)
+
+    def _masks(self, model, images, e, first, count, first_sample, seed):
+        """Masks of passes first + 1 .. first + count of transform e (None in eval mode)."""
+        if self.mc_steps == 0:
+            return None
+        return model.seeded_masks(images.shape[0], images.device, [tta_pass_seed(seed, e, j + 1) for j in range(first, first + count)], first_sample)
+
+    def _transformed(self, images):
+        return {e: (images if e == 0 else tta_transform(images, e)) for e in self.elements}
+
+    def _fused(self, model, images, do_mi, do_var, first_sample, seed, before=None):
+        n, _, h, w = images.shape
+        dev = images.device
+
+        def fresh():
+            return McStatistics(n, model.nb_classes, h, w, dev, do_mi, do_var, exact=self.exact)
+
+        xs = self._transformed(images)
+        stats = fresh()
+        group = pass_group_size(model, n, h, w, self.group_pixels)
+        lanes = StreamLanes(dev, min(self.lanes, self.samples))
+        sizes = balanced_groups(self.passes_per_transform, group, lanes.count)
+        lanes.begin(stats, fresh, inputs=tuple(xs.values()))
+        if before is not None:
+            before()                   # (the weight-scaling pass, on the caller's stream, in eval mode)
+        set_dropout_mode(model, is_train=self.mc_steps > 0)
+        scratch = [None] * lanes.count       # per lane: the statistics of the current transform's passes, reused from transform to transform
+        try:
+            for v, e in enumerate(self.elements):
+                used, i = [], 0
+                for q, g in enumerate(sizes):
+                    lane = (v + q) % lanes.count
+
+                    def launch(st, lane, e=e, i=i, g=g):
+                        if e != 0:
+                            if scratch[lane] is None:
+                                scratch[lane] = fresh()          # (zeroed on the lane's stream)
+                            st = scratch[lane]
+                        model.forward_accumulate(xs[e], st, self._masks(model, images, e, i, g, first_sample, seed), passes=g, lane=lane)
+                    lanes.run(launch, lane=lane)
+                    if lane not in used:
+                        used.append(lane)
+                    i += g
+                if e != 0:
+                    for lane in sorted(used):
+                        def fold(st, lane, e=e):
+                            fold_transformed(scratch[lane], st, e)
+                            restart_statistics(scratch[lane])
+                        lanes.run(fold, lane=lane)
+        finally:
+            set_dropout_mode(model, is_train=False)
+        lanes.end(merge_statistics)
+
+        def recipe(mi, var, materialize=False):
+            if materialize:
+                return self._materialized(model, images, first_sample, seed)
+            return self._fused(model, images, mi, var, first_sample, seed)
+
+        stats.recipe = recipe
+        return stats
+
+    def _materialized(self, model, images, first_sample, seed):
+        """The V x T probability volumes ``[V*T, N, C, H, W]`` in canonical orientation, transform-major in the given order."""
+        xs = self._transformed(images)
+        probs = []
+        set_dropout_mode(model, is_train=self.mc_steps > 0)
+        try:
+            for e in self.elements:
+                for j in range(self.passes_per_transform):
+                    masks = self._masks(model, images, e, j, 1, first_sample, seed)
+                    p = softmax(model(xs[e]) if masks is None else model(xs[e], masks))
+                    probs.append(p if e == 0 else tta_transform(p, TTA_INVERSE[e]))
+        finally:
+            set_dropout_mode(model, is_train=False)
+        return torch.stack(probs)
 
 
 def wait_for_outputs(batch_context):
