@@ -30,149 +30,7 @@ import torch.distributed as dist
 from . import steps as steps_mod
 
 
-class HipEngine:
-    """The product engine: fused forward + softmax + accumulate on librcu_hip."""
-
-    def __init__(self, model, do_mi=False, do_var=False, exact=True):
-        self.model = model
-        self.do_mi, self.do_var = do_mi, do_var
-        # exact sums (rcu_amd.steps.McStatistics, include/rcu.h RCU_MC_EXACT): float64 planes whose additions are all exact -- the merged
-        # statistics carry the same bits for every world size, job rotation, lane count and reduction tree of the collective
-        self.exact = bool(exact)
-
-    def _statistics(self, x, blob=None):
-        n, _, h, w = x.shape
-        return steps_mod.McStatistics(n, self.model.nb_classes, h, w, x.device, self.do_mi, self.do_var, blob=blob, exact=self.exact)
-
-    def buffers(self, x, with_ws):
-        """-> (flat reduce buffer, statistics object living in its head, ws tensor or None): the weight-scaling
-        probabilities live in the tail of the ONE flat buffer (as float64 when the statistics are float64 -- a float32
-        value is exact in float64, and a sum with the other ranks' zeros is too), so a volume is always one collective."""
-        n, _, h, w = x.shape
-        c = self.model.nb_classes
-        dtype = steps_mod.McStatistics.dtype_of(self.do_var, self.exact)
-        n_stats = steps_mod.McStatistics.blob_elements(n, c, h * w, self.do_mi, self.do_var, self.exact)
-        n_ws = n * c * h * w if with_ws else 0
-        flat = torch.empty(n_stats + n_ws, device=x.device, dtype=dtype)
-        stats = self._statistics(x, flat[:n_stats])
-        ws = None
-        if with_ws:
-            ws = flat[n_stats:].view(n, c, h, w)
-            ws.zero_()
-        return flat, stats, ws
-
-    def reserve(self, x, mc_steps, group, lanes):
-        """The canonical plans of the batch (rcu_amd.steps.reserve_canonical_plans): the bits of a pass must not depend on which launches
-        THIS rank happens to make."""
-        n, _, h, w = x.shape
-        steps_mod.reserve_canonical_plans(self.model, n, h, w, mc_steps, group, lanes)
-
-    def ws_pass(self, x, ws_out):
-        steps_mod.set_dropout_mode(self.model, False)
-        if ws_out.dtype == torch.float32 and ws_out.is_contiguous():
-            steps_mod.softmax(self.model(x), out=ws_out)          # straight into the reduce buffer's tail
-        else:                                                     # float64 statistics: the tail is float64 too
-            ws_out.copy_(steps_mod.softmax(self.model(x)))
-
-    def seeded_masks(self, x, seeds, first_sample=0):
-        """The masks of the passes seeded with ``seeds`` over x, in the layout of their group launch (UNet.seeded_masks: one kernel, the factors
-        of sample i in pass t a function of seeds[t] and the sample's global index ``first_sample + i`` alone)."""
-        steps_mod.set_dropout_mode(self.model, True)
-        try:
-            return self.model.seeded_masks(x.shape[0], x.device, seeds, first_sample)
-        finally:
-            steps_mod.set_dropout_mode(self.model, False)
-
-    def sample_masks(self, x, generator, passes=1):
-        """Dropout factors of ``passes`` stochastic passes over x (rows [site][passes * N][C_site]) from ``generator``."""
-        steps_mod.set_dropout_mode(self.model, True)
-        try:
-            return self.model.sample_masks(x.shape[0] * passes, x.device, generator=generator)
-        finally:
-            steps_mod.set_dropout_mode(self.model, False)
-
-    def mc_pass(self, x, stats, masks=None, passes=1, lane=0):
-        steps_mod.set_dropout_mode(self.model, True)
-        try:
-            self.model.forward_accumulate(x, stats, masks, passes=passes, lane=lane)
-        finally:
-            steps_mod.set_dropout_mode(self.model, False)
-
-    def member_pass(self, member, x, stats, lane=0):
-        steps_mod.set_dropout_mode(member, False)
-        member.forward_accumulate(x, stats, lane=lane)
-
-    def side_statistics(self, x):
-        """Fresh (zeroed) statistics for a stream lane of its own; ``merge`` adds them into the volume's statistics."""
-        return self._statistics(x)
-
-    def merge(self, stats, side):
-        stats.blob.add_(side.blob)          # plain sums (include/rcu.h, rcu_mc_*)
-
-    def finalize(self, stats, count):
-        return stats.finalize(self.do_mi, self.do_var, count=count)
-
-    def ws_outputs(self, ws):
-        return {'ws_probabilities': ws if ws.dtype == torch.float32 else ws.float()}
-
-
-class AleatoricHipEngine(HipEngine):
-    """EXTENSION (BASELINE config "aleatoric + MC", see rcu_amd.steps.AleatoricMcPredictStep): passes of a sigma-head U-Net.  The
-    per-pass sigmas are plain sums like the statistics, so they ride in the same reduce buffer:
-    flat = [statistics | sigma sum [n,C,H,W] | ws probabilities | ws sigma]."""
-
-    def __init__(self, model, is_log_sigma=False, do_mi=False):
-        # float32 statistics: the sigma sums share the buffer (unbounded addends: no exact form), one dtype per collective
-        super().__init__(model, do_mi, False, exact=False)
-        if not getattr(model, 'sigma_out', False):
-            raise ValueError('AleatoricHipEngine needs a model built with sigma_out=True')
-        self.is_log_sigma = is_log_sigma
-
-    def buffers(self, x, with_ws):
-        n, _, h, w = x.shape
-        c = self.model.nb_classes
-        n_stats = steps_mod.McStatistics.blob_elements(n, c, h * w, self.do_mi, False)
-        n_vol = n * c * h * w
-        flat = torch.empty(n_stats + n_vol * (3 if with_ws else 1), device=x.device, dtype=torch.float32)
-        stats = steps_mod.McStatistics(n, c, h, w, x.device, self.do_mi, False, blob=flat[:n_stats])
-        flat[n_stats:].zero_()
-        stats.sigma_sum = flat[n_stats:n_stats + n_vol].view(n, c, h, w)
-        ws = flat[n_stats + n_vol:].view(2, n, c, h, w) if with_ws else None
-        return flat, stats, ws
-
-    def ws_pass(self, x, ws_out):
-        steps_mod.set_dropout_mode(self.model, False)
-        logits, raw = self.model(x)
-        n, c, h, w = logits.shape
-        lib = steps_mod._lib
-        lib.check(lib.load().rcu_aleatoric(lib.ptr(logits), lib.ptr(raw.contiguous()), n, h * w, c, int(self.is_log_sigma),
-                                           lib.ptr(ws_out[0]), lib.ptr(ws_out[1]), None, None, lib.current_stream()))
-
-    def mc_pass(self, x, stats, masks=None, passes=1, lane=0):
-        steps_mod.set_dropout_mode(self.model, True)
-        try:
-            self.model.forward_accumulate_sigma(x, stats, stats.sigma_sum, masks, self.is_log_sigma, lane=lane, passes=passes)
-        finally:
-            steps_mod.set_dropout_mode(self.model, False)
-
-    def side_statistics(self, x):
-        stats = super().side_statistics(x)
-        stats.sigma_sum = torch.zeros((x.shape[0], self.model.nb_classes) + tuple(x.shape[2:]), device=x.device)
-        return stats
-
-    def merge(self, stats, side):
-        super().merge(stats, side)
-        stats.sigma_sum.add_(side.sigma_sum)
-
-    def finalize(self, stats, count):
-        out = stats.finalize(self.do_mi, False, count=count)
-        out['sigma'] = stats.sigma_sum / float(max(count, 1))
-        return out
-
-    def ws_outputs(self, ws):
-        return {'ws_probabilities': ws[0], 'ws_sigma': ws[1]}
-
-
+HipEngine, AleatoricHipEngine = steps_mod.HipEngine, steps_mod.AleatoricHipEngine     # (the engines live in rcu_amd.steps, next to the scheduler)
 job_seed = steps_mod.job_seed      # seed of a torch generator for the masks of MC pass ``job`` of volume ``step_index`` (engines without the library's draw)
 pass_seed = steps_mod.pass_seed    # key of the library's counter-based draw for MC pass ``job``: the counter carries the sample's global index
 
@@ -223,7 +81,8 @@ class ShardedMcRunner:
         self._generator = None
         self.sample_offsets = {}       # step index -> global index of the batch's first sample (the sharded predict steps fill it in; else k x n)
         self.forwards_run = 0          # launches of this rank (a pass group counts its passes)
-        self.reserve_plans = True      # (the ensemble runner: every launch is one member on n samples, nothing to make canonical)
+        # what a job is (rcu_amd.steps.launch_plan): pass j of the images as they are, or of the TTA runner's transformed images, or member j - 1
+        self.elements, self.per_element, self.members, self.stochastic = (0,), max(1, mc_steps), None, True
 
     def masks_of(self, x, step_index, job):
         """The device mask tensor MC pass ``job`` (1..T) of volume ``step_index`` runs under (None without a seed / an engine
@@ -256,66 +115,30 @@ class ShardedMcRunner:
         jobs = self.job_list()
         return [j for i, j in enumerate(jobs) if (i + step * len(jobs)) % self.world == rank]
 
-    def _run_job(self, job, x, stats, ws, mask_sets, step_index=0, lane=0):
-        if job == 0:
-            self.engine.ws_pass(x, ws)
-        else:
-            masks = self.masks_of(x, step_index, job) if mask_sets is None else mask_sets[job - 1]
-            if lane:
-                self.engine.mc_pass(x, stats, masks, lane=lane)
-            else:
-                self.engine.mc_pass(x, stats, masks)
-        self.forwards_run += 1
+    def _draw(self, x, step_index, mask_sets):
+        """``draw(element, jobs)`` of rcu_amd.steps.run_plan: the masks of a launch of this rank."""
+        first_sample = self.first_sample(x, step_index)
 
-    def _lane_of(self, job, count):
-        """Fixed lane of a job, or None: the launches of a volume take the lanes in turn."""
-        return None
+        def draw(e, jobs):
+            if mask_sets is None and self.seed is not None and not hasattr(self.engine, 'seeded_masks'):
+                ms = [self.masks_of(x, step_index, j) for j in jobs]      # (an engine of the CPU tests: a torch generator per pass)
+                return None if any(m is None for m in ms) else ms[0] if len(ms) == 1 else ms
+            return steps_mod.launch_masks(self.engine, x, e, jobs, self.per_element, self.seed, first_sample, mask_sets)
+        return draw
 
     def _run_jobs(self, x, step_index, mask_sets):
+        """This rank's jobs of volume ``step_index`` into a fresh reduce buffer -> (flat buffer, statistics, ws tail or None)."""
+        if mask_sets is not None and self.elements != (0,):
+            raise ValueError('the TTA runner draws its masks itself (seeded): no injected mask sets')
         flat, stats, ws = self.engine.buffers(x, self.ws_pass)
-        jobs = self.jobs_of(step_index, self.rank)
-        # stream lanes (rcu_amd.steps.StreamLanes): lane 0 = the caller's stream and the volume's statistics
-        lanes = steps_mod.StreamLanes(x.device, self.lanes if (x.is_cuda and hasattr(self.engine, 'side_statistics')) else 1)
-        pass_group = self.pass_group if self.group_samples is None else max(1, int(self.group_samples) // int(x.shape[0]))
-        if hasattr(self.engine, 'reserve') and self.reserve_plans:
-            self.engine.reserve(x, self.mc_steps, pass_group, lanes.count)
-        lanes.begin(stats, lambda: self.engine.side_statistics(x), inputs=(x,), first=step_index if self.world > 1 else 0)
-        on_lane = lanes.run
-
-        # group sizes of this rank's MC passes: rounds of one group per lane (steps.balanced_groups), so that the lanes carry the same load
-        sizes = steps_mod.balanced_groups(sum(1 for j in jobs if j != 0), pass_group, lanes.count)
-        i = 0
-        while i < len(jobs):
-            group = [j for j in jobs[i:i + sizes[0]] if j != 0] if jobs[i] != 0 else []
-            if group:
-                sizes.pop(0)
-            if len(group) > 1:     # consecutive MC passes of this rank as one batch of N * g samples
-                def run_group(st, lane, group=group):
-                    if mask_sets is None:
-                        seeded = getattr(self.engine, 'seeded_masks', None)
-                        if self.seed is not None and seeded is not None:
-                            ms = seeded(x, [pass_seed(self.seed, j) for j in group], self.first_sample(x, step_index))
-                        else:
-                            ms = [self.masks_of(x, step_index, j) for j in group]
-                            ms = None if any(m is None for m in ms) else ms
-                    else:
-                        ms = [mask_sets[j - 1] for j in group]
-                    if lane:
-                        self.engine.mc_pass(x, st, ms, passes=len(group), lane=lane)
-                    else:
-                        self.engine.mc_pass(x, st, ms, passes=len(group))
-                on_lane(run_group)
-                self.forwards_run += len(group)
-                i += len(group)
-            elif jobs[i] == 0:     # the weight-scaling pass writes into the volume's buffer: lane 0, outside the rotation
-                self._run_job(0, x, stats, ws, mask_sets, step_index)
-                i += 1
-            else:
-                on_lane(lambda st, lane, job=jobs[i]: self._run_job(job, x, st, ws, mask_sets, step_index, lane),
-                        self._lane_of(jobs[i], lanes.count))
-                i += 1
-        if lanes.count > 1:
-            lanes.end(self.engine.merge)
+        # stream lanes (rcu_amd.steps.StreamLanes): lane 0 = the caller's stream and the volume's statistics; engines without side statistics: one
+        lanes = self.lanes if (x.is_cuda and hasattr(self.engine, 'side_statistics')) else 1
+        group = self.pass_group if self.group_samples is None else max(1, int(self.group_samples) // int(x.shape[0]))
+        plan = steps_mod.launch_plan(self.jobs_of(step_index, self.rank), self.elements, self.per_element, group, lanes,
+                                     first=step_index if self.world > 1 else 0, members=self.members is not None)
+        steps_mod.run_plan(plan, self.engine, x, stats, ws, lanes, draw=self._draw(x, step_index, mask_sets) if self.stochastic else None,
+                           reserve=None if self.members is not None else (self.per_element, group), members=self.members)
+        self.forwards_run += sum(len(jobs) for kind, _, _, jobs in plan if kind != 'fold')
         return flat, stats, ws
 
     def ws_owner(self, step_index):
@@ -465,97 +288,31 @@ class ShardedEnsembleRunner(ShardedMcRunner):
         members = list(members)
         super().__init__(members[0] if members else None, len(members), ws_pass=False, rank=rank, world=world,
                          engine=engine, do_mi=do_mi, do_var=do_var, root=root, lanes=lanes, exact=exact)
+        # (a member keeps to lane (j - 1) % lanes whatever the job rotation does: the members of a lane share its workspace; no canonical plan)
         self.members = members
-        self.reserve_plans = False
         if share_workspace:
             steps_mod.share_member_workspaces(members)
-
-    def _lane_of(self, job, count):
-        # A member keeps to one lane whatever the job rotation of a multi-rank run does: one plan (35 MB of packed weights) per member, and
-        # the members that share a lane's workspace run on that lane's stream, one after the other
-        return (job - 1) % count
-
-    def _run_job(self, job, x, stats, ws, mask_sets, step_index=0, lane=0):
-        if lane:
-            self.engine.member_pass(self.members[job - 1], x, stats, lane=lane)
-        else:
-            self.engine.member_pass(self.members[job - 1], x, stats)
-        self.forwards_run += 1
 
 
 class ShardedTtaMcRunner(ShardedMcRunner):
     """EXTENSION -- test-time augmentation sharded over the ranks (rcu_amd.steps.TtaMcPredictStep): the jobs of a volume are the weight-scaling
     pass (job 0) and the V x T (transform, pass) pairs, job 1 + v * T + (t - 1) = pass t of transform ``elements[v]`` (T = max(mc_steps, 1);
-    mc_steps = 0: one eval-mode pass per transform), assigned round robin as ShardedMcRunner's.  A rank runs its consecutive passes of one
-    transform as pass groups over its stream lanes, into a per-lane statistics blob that is folded into the lane's canonical statistics
-    (rcu_mc_fold_transformed) once the rank's passes of that transform are done; the side lanes are added into lane 0 and the ONE sum-reduce of
-    the base class merges the ranks.  Exact sums: an N-rank run gives the bytes of the one-process step."""
+    mc_steps = 0: one eval-mode pass per transform), assigned round robin as ShardedMcRunner's.  A rank runs its passes of each transform
+    with the one-process step's launch plan (rcu_amd.steps.launch_plan: balanced pass groups, the first lane rotating with the transform and the
+    volume; per-lane scratch statistics folded into the lane's canonical statistics once the transform is done); the side lanes are added into
+    lane 0 and the ONE sum-reduce of the base class merges the ranks.  Exact sums: an N-rank run gives the bytes of the one-process step."""
 
     def __init__(self, model, transforms, mc_steps=0, ws_pass=True, rank=0, world=1, do_mi=False, do_var=False, root=0, seed=0, pass_group=1,
                  lanes=1, ws_transport=None, exact=True, engine=None):
-        self.elements = steps_mod.tta_elements(transforms)
-        self.tta_mc_steps = int(mc_steps)
-        self.per_transform = max(self.tta_mc_steps, 1)
-        super().__init__(model, len(self.elements) * self.per_transform, ws_pass=ws_pass, rank=rank, world=world, engine=engine, do_mi=do_mi,
+        elements = steps_mod.tta_elements(transforms)
+        super().__init__(model, len(elements) * max(int(mc_steps), 1), ws_pass=ws_pass, rank=rank, world=world, engine=engine, do_mi=do_mi,
                          do_var=do_var, root=root, seed=seed, pass_group=pass_group, lanes=lanes, ws_transport=ws_transport, exact=exact)
+        self.elements, self.per_element = elements, max(int(mc_steps), 1)
+        self.stochastic = int(mc_steps) > 0          # mc_steps = 0: one eval-mode pass per transform
 
     def job_pair(self, job):
         """MC job id (1 .. V*T) -> (element code, pass 1..T)."""
-        return self.elements[(job - 1) // self.per_transform], (job - 1) % self.per_transform + 1
-
-    def _masks(self, x, element, passes, step_index):
-        if self.tta_mc_steps == 0:
-            return None
-        return self.engine.seeded_masks(x, [steps_mod.tta_pass_seed(self.seed, element, t) for t in passes], self.first_sample(x, step_index))
-
-    def _run_jobs(self, x, step_index, mask_sets):
-        if mask_sets is not None:
-            raise ValueError('the TTA runner draws its masks itself (seeded): no injected mask sets')
-        flat, stats, ws = self.engine.buffers(x, self.ws_pass)
-        jobs = self.jobs_of(step_index, self.rank)
-        lanes = steps_mod.StreamLanes(x.device, self.lanes if x.is_cuda else 1)
-        pass_group = self.pass_group if self.group_samples is None else max(1, int(self.group_samples) // int(x.shape[0]))
-        # the canonical plan of the one-process step: n x min(group, T) samples on every lane
-        self.engine.reserve(x, self.tta_mc_steps, pass_group, lanes.count)
-        # this rank's (transform, passes) launches: consecutive passes of one transform, at most pass_group per launch
-        runs = collections.OrderedDict()
-        for j in jobs:
-            if j != 0:
-                e, t = self.job_pair(j)
-                runs.setdefault(e, []).append(t)
-        xs = {e: (x if e == 0 else steps_mod.tta_transform(x, e)) for e in runs}
-        lanes.begin(stats, lambda: self.engine.side_statistics(x), inputs=tuple(xs.values()), first=step_index if self.world > 1 else 0)
-        if 0 in jobs:      # the weight-scaling pass writes into the volume's buffer: lane 0, outside the rotation
-            self._run_job(0, x, stats, ws, None, step_index)
-        scratch = [None] * lanes.count
-        for e, passes in runs.items():
-            used = []
-            for b in range(0, len(passes), pass_group):
-                group = passes[b:b + pass_group]
-
-                def launch(st, lane, e=e, group=group):
-                    if e != 0:
-                        if scratch[lane] is None:
-                            scratch[lane] = self.engine.side_statistics(x)      # (zeroed on the lane's stream)
-                        st = scratch[lane]
-                    if self.tta_mc_steps == 0:
-                        self.engine.member_pass(self.engine.model, xs[e], st, lane=lane)
-                    else:
-                        self.engine.mc_pass(xs[e], st, self._masks(x, e, group, step_index), passes=len(group), lane=lane)
-                lane = lanes._launch % lanes.count
-                lanes.run(launch)
-                if lane not in used:
-                    used.append(lane)
-                self.forwards_run += len(group)
-            if e != 0:
-                for lane in sorted(used):
-                    def fold(st, lane, e=e):
-                        steps_mod.fold_transformed(scratch[lane], st, e)
-                        steps_mod.restart_statistics(scratch[lane])
-                    lanes.run(fold, lane=lane)
-        if lanes.count > 1:
-            lanes.end(self.engine.merge)
-        return flat, stats, ws
+        return self.elements[(job - 1) // self.per_element], (job - 1) % self.per_element + 1
 
 
 class PendingStatistics:

@@ -304,6 +304,238 @@ def merge_statistics(stats, side):
         stats.sigma_sum.add_(side.sigma_sum)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# the scheduler of the fused paths: the one-process predict steps and the sharded runners (rcu_amd.distributed) run their passes
+# through ``launch_plan`` + ``run_plan`` on an engine
+# ------------------------------------------------------------------------------------------------------------------------------
+def launch_plan(jobs, elements=(0,), per_element=1, group=1, lanes=1, first=0, members=False):
+    """The launches of one batch -> ``[(kind, lane, element, jobs)]``, in launch order; plain values in, plain values out.
+    ``jobs``: the job ids this process runs -- 0 the weight-scaling pass, j >= 1 pass (j - 1) % per_element + 1 of the images transformed by
+    ``elements[(j - 1) // per_element]`` (plain MC: ``elements=(0,)``), or with ``members`` ensemble member j - 1.  Kinds:
+      'ws'      the weight-scaling pass: lane 0, first, outside the rotation;
+      'passes'  a pass group of one element; the groups of element v are ``balanced_groups`` of its jobs, launch q on lane
+                (first + v + q) % lanes (``first``: a rank of a multi-rank run rotates it with the volume);
+      'fold'    after the last group of an element other than the identity: on every lane that element used, in lane order, fold the
+                lane's scratch statistics into the lane's statistics (rcu_mc_fold_transformed) and restart them;
+      'member'  one ensemble member, always on lane (j - 1) % lanes (the members of a lane share its workspace from batch to batch)."""
+    lanes = max(1, int(lanes))
+    plan = [('ws', 0, 0, (0,))] if 0 in jobs else []
+    if members:
+        return plan + [('member', (j - 1) % lanes, 0, (j,)) for j in jobs if j != 0]
+    runs = {}
+    for j in jobs:
+        if j != 0:
+            runs.setdefault((j - 1) // per_element, []).append(j)
+    for v, run in runs.items():
+        e, used, b = elements[v], set(), 0
+        for q, size in enumerate(balanced_groups(len(run), group, lanes)):
+            lane = (first + v + q) % lanes
+            plan.append(('passes', lane, e, tuple(run[b:b + size])))
+            used.add(lane)
+            b += size
+        if e != 0:
+            plan += [('fold', lane, e, ()) for lane in sorted(used)]
+    return plan
+
+
+def launch_masks(engine, x, element, jobs, per_element, seed=None, first_sample=0, mask_sets=None):
+    """``masks`` argument of the launch of ``jobs`` (see ``launch_plan``): injected sets (indexed by pass), the library's seeded draw under
+    ``tta_pass_seed(seed, element, pass)`` (the identity's key is ``pass_seed``) at the samples' global indices, or None -- drawn inside the
+    launch from the device's default generator."""
+    passes = [(j - 1) % per_element + 1 for j in jobs]
+    if mask_sets is not None:
+        return mask_sets[passes[0] - 1] if len(passes) == 1 else [mask_sets[t - 1] for t in passes]
+    if seed is None:
+        return None
+    return engine.seeded_masks(x, [tta_pass_seed(seed, element, t) for t in passes], first_sample)
+
+
+def run_plan(plan, engine, x, stats, ws=None, lanes=1, draw=None, reserve=None, members=()):
+    """Run ``plan`` (``launch_plan``) on ``engine`` over the images x into ``stats`` (the weight-scaling pass into ``ws``) on ``lanes``
+    StreamLanes.  ``reserve = (passes per element, group)``: the canonical plans of the batch, on every lane, before the first forward
+    (``reserve_canonical_plans``).  ``draw(element, jobs)``: the masks of a pass group, called INSIDE the launch -- on the stream of the lane
+    that reads them; None: eval-mode passes (TTA alone).  ``lanes`` is the count the plan was made for (1 for engines without
+    ``side_statistics``)."""
+    lanes = StreamLanes(x.device, lanes)
+    if reserve is not None and hasattr(engine, 'reserve'):
+        engine.reserve(x, reserve[0], reserve[1], lanes.count)
+    xs = {}
+    for kind, _, e, _ in plan:
+        if kind == 'passes' and e not in xs:
+            xs[e] = x if e == 0 else tta_transform(x, e)
+    lanes.begin(stats, lambda: engine.side_statistics(x), inputs=(x,) + tuple(v for e, v in xs.items() if e != 0))
+    scratch = [None] * lanes.count       # per lane: the statistics of the current element's passes (elements other than the identity)
+
+    def launch(st, lane, kind, e, jobs):
+        # keywords at their defaults are left out: engines that only ever run one lane (one pass per launch) need not take them
+        kw = {'lane': lane} if lane else {}
+        if kind == 'member':
+            engine.member_pass(members[jobs[0] - 1], x, st, **kw)
+        elif kind == 'fold':
+            fold_transformed(scratch[lane], st, e)
+            restart_statistics(scratch[lane])
+        else:
+            if e != 0:
+                if scratch[lane] is None:
+                    scratch[lane] = engine.side_statistics(x)          # (zeroed on the lane's stream)
+                st = scratch[lane]
+            if draw is None:
+                engine.member_pass(engine.model, xs[e], st, **kw)
+            elif len(jobs) == 1:
+                engine.mc_pass(xs[e], st, draw(e, jobs), **kw)
+            else:
+                engine.mc_pass(xs[e], st, draw(e, jobs), passes=len(jobs), **kw)
+
+    for kind, lane, e, jobs in plan:
+        if kind == 'ws':
+            engine.ws_pass(x, ws)          # on the caller's stream, beside the side lanes' first launches
+        else:
+            lanes.run(lambda st, lane, kind=kind, e=e, jobs=jobs: launch(st, lane, kind, e, jobs), lane=lane)
+    if lanes.count > 1:
+        lanes.end(engine.merge)
+    return stats
+
+
+class HipEngine:
+    """The product engine of the fused paths: forward + softmax + accumulate on librcu_hip.  The one-process steps and the sharded runners
+    touch the model through its ``ws_pass``, ``mc_pass``, ``member_pass``, ``side_statistics`` and ``merge`` only."""
+
+    def __init__(self, model, do_mi=False, do_var=False, exact=True):
+        self.model = model
+        self.do_mi, self.do_var = do_mi, do_var
+        # exact sums (McStatistics, include/rcu.h RCU_MC_EXACT): float64 planes whose additions are all exact -- the merged statistics carry
+        # the same bits for every world size, job rotation, lane count and reduction tree of the collective
+        self.exact = bool(exact)
+
+    def _statistics(self, x, blob=None):
+        n, _, h, w = x.shape
+        return McStatistics(n, self.model.nb_classes, h, w, x.device, self.do_mi, self.do_var, blob=blob, exact=self.exact)
+
+    def buffers(self, x, with_ws):
+        """-> (flat reduce buffer, statistics object living in its head, ws tensor or None): the weight-scaling
+        probabilities live in the tail of the ONE flat buffer (as float64 when the statistics are float64 -- a float32
+        value is exact in float64, and a sum with the other ranks' zeros is too), so a volume is always one collective."""
+        n, _, h, w = x.shape
+        c = self.model.nb_classes
+        n_stats = McStatistics.blob_elements(n, c, h * w, self.do_mi, self.do_var, self.exact)
+        flat = torch.empty(n_stats + (n * c * h * w if with_ws else 0), device=x.device, dtype=McStatistics.dtype_of(self.do_var, self.exact))
+        stats = self._statistics(x, flat[:n_stats])
+        ws = None
+        if with_ws:
+            ws = flat[n_stats:].view(n, c, h, w)
+            ws.zero_()
+        return flat, stats, ws
+
+    def reserve(self, x, mc_steps, group, lanes):
+        """The canonical plans of the batch (reserve_canonical_plans): the bits of a pass must not depend on which launches THIS process
+        happens to make."""
+        n, _, h, w = x.shape
+        reserve_canonical_plans(self.model, n, h, w, mc_steps, group, lanes)
+
+    def ws_pass(self, x, ws_out):
+        set_dropout_mode(self.model, False)
+        if ws_out.dtype == torch.float32 and ws_out.is_contiguous():
+            softmax(self.model(x), out=ws_out)
+        else:                                                     # float64 statistics: the reduce buffer's tail is float64 too
+            ws_out.copy_(softmax(self.model(x)))
+
+    def seeded_masks(self, x, seeds, first_sample=0):
+        """The masks of the passes seeded with ``seeds`` over x, in the layout of their group launch (UNet.seeded_masks: one kernel, the factors
+        of sample i in pass t a function of seeds[t] and the sample's global index ``first_sample + i`` alone)."""
+        set_dropout_mode(self.model, True)
+        try:
+            return self.model.seeded_masks(x.shape[0], x.device, seeds, first_sample)
+        finally:
+            set_dropout_mode(self.model, False)
+
+    def sample_masks(self, x, generator, passes=1):
+        """Dropout factors of ``passes`` stochastic passes over x (rows [site][passes * N][C_site]) from ``generator``."""
+        set_dropout_mode(self.model, True)
+        try:
+            return self.model.sample_masks(x.shape[0] * passes, x.device, generator=generator)
+        finally:
+            set_dropout_mode(self.model, False)
+
+    def mc_pass(self, x, stats, masks=None, passes=1, lane=0):
+        set_dropout_mode(self.model, True)
+        try:
+            self.model.forward_accumulate(x, stats, masks, passes=passes, lane=lane)
+        finally:
+            set_dropout_mode(self.model, False)
+
+    def member_pass(self, member, x, stats, lane=0):
+        set_dropout_mode(member, False)
+        member.forward_accumulate(x, stats, lane=lane)
+
+    def side_statistics(self, x):
+        """Fresh (zeroed) statistics: a stream lane's own, or a one-process step's."""
+        return self._statistics(x)
+
+    def merge(self, stats, side):
+        merge_statistics(stats, side)
+
+    def finalize(self, stats, count):
+        return stats.finalize(self.do_mi, self.do_var, count=count)
+
+    def ws_outputs(self, ws):
+        return {'ws_probabilities': ws if ws.dtype == torch.float32 else ws.float()}
+
+
+class AleatoricHipEngine(HipEngine):
+    """EXTENSION (BASELINE config "aleatoric + MC", see AleatoricMcPredictStep): passes of a sigma-head U-Net; statistics carry a float32
+    ``sigma_sum`` [n, C, H, W] next to the blob.  ``exact`` applies to the probability statistics only (the sigmas are unbounded addends:
+    no exact form).  The sharded runner's reduce buffer is float32 throughout, one dtype per collective:
+    flat = [statistics | sigma sum | ws probabilities | ws sigma]."""
+
+    def __init__(self, model, is_log_sigma=False, do_mi=False, do_var=False, exact=False):
+        super().__init__(model, do_mi, do_var, exact)
+        if not getattr(model, 'sigma_out', False):
+            raise ValueError('AleatoricHipEngine needs a model built with sigma_out=True')
+        self.is_log_sigma = is_log_sigma
+
+    def buffers(self, x, with_ws):
+        if self.exact or self.do_var:
+            raise ValueError('the reduce buffer of the sigma-head engine is float32: no exact or do_var statistics')
+        n, _, h, w = x.shape
+        c = self.model.nb_classes
+        n_stats = McStatistics.blob_elements(n, c, h * w, self.do_mi, False)
+        n_vol = n * c * h * w
+        flat = torch.empty(n_stats + n_vol * (3 if with_ws else 1), device=x.device, dtype=torch.float32)
+        stats = McStatistics(n, c, h, w, x.device, self.do_mi, False, blob=flat[:n_stats])
+        flat[n_stats:].zero_()
+        stats.sigma_sum = flat[n_stats:n_stats + n_vol].view(n, c, h, w)
+        ws = flat[n_stats + n_vol:].view(2, n, c, h, w) if with_ws else None
+        return flat, stats, ws
+
+    def ws_pass(self, x, ws_out):
+        """-> ws_out[0] = the probabilities, ws_out[1] = sigma of the deterministic pass."""
+        set_dropout_mode(self.model, False)
+        logits, raw = self.model(x)
+        n, c, h, w = logits.shape
+        _lib.check(_lib.load().rcu_aleatoric(_lib.ptr(logits), _lib.ptr(raw.contiguous()), n, h * w, c, int(self.is_log_sigma),
+                                             _lib.ptr(ws_out[0]), _lib.ptr(ws_out[1]), None, None, _lib.current_stream()))
+
+    def mc_pass(self, x, stats, masks=None, passes=1, lane=0):
+        set_dropout_mode(self.model, True)
+        try:
+            self.model.forward_accumulate_sigma(x, stats, stats.sigma_sum, masks, self.is_log_sigma, lane=lane, passes=passes)
+        finally:
+            set_dropout_mode(self.model, False)
+
+    def side_statistics(self, x):
+        stats = super().side_statistics(x)
+        stats.sigma_sum = torch.zeros((x.shape[0], self.model.nb_classes) + tuple(x.shape[2:]), device=x.device)
+        return stats
+
+    def finalize(self, stats, count):
+        out = stats.finalize(self.do_mi, self.do_var, count=count)
+        out['sigma'] = stats.sigma_sum / float(max(count, 1))
+        return out
+
+    def ws_outputs(self, ws):
+        return {'ws_probabilities': ws[0], 'ws_sigma': ws[1]}
+
+
 def softmax(logits, out=None):
     """F.softmax(logits, 1) on the HIP path (``out``: a contiguous float32 tensor of the same shape to write into)."""
     logits = logits.to(torch.float32).contiguous()
@@ -390,82 +622,61 @@ class McPredictStep(BatchStep):
         (dropout mode is on)."""
         return model.seeded_masks(images.shape[0], images.device, [pass_seed(self.seed, job)], first_sample)
 
-    def _launch_masks(self, model, images, first_sample, first, count):
-        """``masks`` argument of the launch that runs the passes first .. first + count - 1 (0-based): injected sets, seeded draws, or
-        None = drawn inside the launch from the device's default generator."""
+    def _pass_masks(self, model, images, first_sample, job):
+        """Masks of the single pass ``job`` (1..T) of the materialised paths: injected, seeded, or None = drawn by the forward from the
+        device's default generator (dropout mode is on)."""
         if self.masks is not None:
-            return self.masks[first] if count == 1 else self.masks[first:first + count]
-        if self.seed is None:
-            return None
-        # one kernel for the launch's passes, on the stream that reads them, already in the launch's layout (UNet.seeded_masks)
-        return model.seeded_masks(images.shape[0], images.device, [pass_seed(self.seed, j + 1) for j in range(first, first + count)], first_sample)
+            return self.masks[job - 1]
+        return None if self.seed is None else self._seeded_masks(model, images, first_sample, job)
 
     def __call__(self, batch_context, task_context, context) -> None:
         _check_context(context)
         images = _images_to_device(batch_context, context)
         model = context.model
         k = first_sample_of(batch_context, images.shape[0])      # global index of the batch's first sample: what the seeded masks are keyed by
-
-        if isinstance(model, model_mod.UNet):
-            # The CANONICAL plan of the batch, on every lane, before the first forward: which kernel a layer gets depends on the batch its plan
-            # is sized for, and a pass's bits are a property of the plan -- so every way of running the T passes (any grouping, one lane or
-            # two, fused or materialised, one process or the ranks of rcu_amd.distributed) sizes its plans for the same n * min(group, T).
+        if not self.materialize and isinstance(model, model_mod.UNet):
             n, _, h, w = images.shape
-            reserve_canonical_plans(model, n, h, w, self.mc_steps, pass_group_size(model, n, h, w, self.group_pixels),
-                                    1 if self.materialize else min(self.lanes, max(self.mc_steps, 1)))
-        fused = not self.materialize and isinstance(model, model_mod.UNet)
-        if self.ws_pass and not fused:
+            ws = torch.empty((n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
+            if ws is not None:
+                batch_context.output['ws_probabilities'] = ws
+            batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, ws)
+            return
+        unet = isinstance(model, model_mod.UNet)
+        if unet:      # the canonical plan of the fused path (reserve_canonical_plans): a pass's bits are a property of the plan
+            n, _, h, w = images.shape
+            reserve_canonical_plans(model, n, h, w, self.mc_steps, pass_group_size(model, n, h, w, self.group_pixels), 1)
+        if self.ws_pass:
             batch_context.output['ws_probabilities'] = softmax(model(images))
-
-        def ws_pass():      # fused path: issued on lane 0 once the lanes are set up, so that the side lane starts its first group beside it
-            set_dropout_mode(model, is_train=False)
-            batch_context.output['ws_probabilities'] = softmax(model(images))
-            set_dropout_mode(model, is_train=True)
-
         set_dropout_mode(model, is_train=True)
         try:
-            if not fused:
-                probs = []
-                for i in range(self.mc_steps):
-                    masks = self._launch_masks(model, images, k, i, 1) if isinstance(model, model_mod.UNet) else None
-                    logits = model(images) if masks is None else model(images, masks)
-                    probs.append(softmax(logits))
-                batch_context.output['multi_probabilities'] = torch.stack(probs)
-            else:
-                batch_context.output['multi_probabilities'] = self._fused_passes(model, images, self.do_mi, self.do_var, k,
-                                                                                 before=ws_pass if self.ws_pass else None)
+            probs = []
+            for j in range(1, self.mc_steps + 1):
+                masks = self._pass_masks(model, images, k, j) if unet else None
+                probs.append(softmax(model(images) if masks is None else model(images, masks)))
+            batch_context.output['multi_probabilities'] = torch.stack(probs)
         finally:
             set_dropout_mode(model, is_train=False)   # reset to eval for the next batch (customsteps.py:39)
 
-    def _fused_passes(self, model, images, do_mi, do_var, first_sample=0, before=None):
-        """The T passes into per-voxel statistics (dropout mode is on).  The statistics carry a recipe that replays the passes
-        -- same images, same masks (seeded: the same draws again; unseeded: the device generator is put back to where the sampling
-        started) -- so that ``MultiPredictionSummary(do_mi / do_var)`` decides alone which outputs exist, as in the reference
+    def _fused(self, model, images, do_mi, do_var, first_sample=0, ws=None):
+        """The T passes (and, into ``ws``, the weight-scaling pass) into per-voxel statistics, on ``run_plan``.  The statistics carry a recipe
+        that replays the passes -- same images, same masks (seeded: the same draws again; unseeded: the device generator is put back to where
+        the sampling started) -- so that ``MultiPredictionSummary(do_mi / do_var)`` decides alone which outputs exist, as in the reference
         (customsteps.py:44-48)."""
         n, _, h, w = images.shape
         dev = images.device
         unseeded = self.masks is None and self.seed is None
         rng_state = torch.cuda.get_rng_state(dev) if (unseeded and dev.type == 'cuda') else None
-
-        def fresh():
-            return McStatistics(n, model.nb_classes, h, w, dev, do_mi, do_var, exact=self.exact)
-
-        stats = fresh()
+        engine = HipEngine(model, do_mi, do_var, self.exact)
+        stats = engine.side_statistics(images)
         group = pass_group_size(model, n, h, w, self.group_pixels)
         # (every lane gets work whenever there are two passes: T = 20 on batches of 32 slices is 10 | 10 on two lanes, not one launch of 20 on one)
-        lanes = StreamLanes(dev, min(self.lanes, max(self.mc_steps, 1)))
-        sizes = balanced_groups(self.mc_steps, group, lanes.count)
-        lanes.begin(stats, fresh, inputs=(images,))
-        if before is not None:
-            before()                   # (the weight-scaling pass, on the caller's stream)
-        i = 0
-        for g in sizes:
-            # the masks are drawn INSIDE the launch, i.e. on the lane's stream -- the stream that reads them (seeded: from the step's generator;
-            # unseeded: by forward_accumulate from the device's, in launch order whatever the lane)
-            lanes.run(lambda st, lane, i=i, g=g: model.forward_accumulate(images, st, self._launch_masks(model, images, first_sample, i, g),
-                                                                       passes=g, lane=lane))
-            i += g
-        lanes.end(merge_statistics)
+        lanes = min(self.lanes, max(self.mc_steps, 1))
+        plan = launch_plan(([0] if ws is not None else []) + list(range(1, self.mc_steps + 1)), (0,), max(self.mc_steps, 1), group, lanes)
+        try:
+            run_plan(plan, engine, images, stats, ws, lanes, reserve=(self.mc_steps, group),
+                     draw=lambda e, jobs: launch_masks(engine, images, e, jobs, max(self.mc_steps, 1), self.seed, first_sample, self.masks))
+        finally:
+            set_dropout_mode(model, is_train=False)
 
         def recipe(mi, var, materialize=False):
             now = torch.cuda.get_rng_state(dev) if rng_state is not None else None
@@ -474,21 +685,20 @@ class McPredictStep(BatchStep):
             set_dropout_mode(model, is_train=True)
             try:
                 if not materialize:
-                    return self._fused_passes(model, images, mi, var, first_sample)
+                    return self._fused(model, images, mi, var, first_sample)
                 probs = []
-                t = 0
-                for g in sizes:                      # the same draws as the fused path makes: one per pass group
+                for _, _, _, jobs in (launch for launch in plan if launch[0] == 'passes'):      # the draws the fused path makes: one per group
+                    g = len(jobs)
                     if not unseeded:
-                        sets = [self._launch_masks(model, images, first_sample, j, 1) for j in range(t, t + g)]
+                        sets = [self._pass_masks(model, images, first_sample, j) for j in jobs]
                     elif g == 1:
                         sets = [None]
                     else:                            # rows [site][pass * n + i]: split the group's draw into its passes
                         flat = model.sample_masks(n * g, dev)
                         per_site = torch.split(flat, [n * g * c for _, c in model.dropout_sites()])
-                        sets = [[ps.view(g, n, -1)[k] for ps in per_site] for k in range(g)]
+                        sets = [[ps.view(g, n, -1)[i] for ps in per_site] for i in range(g)]
                     for ms in sets:
                         probs.append(softmax(model(images) if ms is None else model(images, ms)))
-                    t += g
                 return torch.stack(probs)
             finally:
                 set_dropout_mode(model, is_train=False)
@@ -537,19 +747,15 @@ class EnsemblePredictionStep(BatchStep):
         if self.share_workspace:
             share_member_workspaces(members)
         if fused:
-            n, _, h, w = images.shape
             def run(mi, var, materialize=False):
                 if materialize:
                     return torch.stack([softmax(m(images)) for m in members])
-                exact = self.exact and len(members) <= _lib.RCU_MC_EXACT_MAX_PASSES
-                st = McStatistics(n, members[0].nb_classes, h, w, images.device, mi, var, exact=exact)
-                lanes = StreamLanes(images.device, min(self.lanes, len(members)))
-                lanes.begin(st, lambda: McStatistics(n, members[0].nb_classes, h, w, images.device, mi, var, exact=exact), inputs=(images,))
-                for m in members:      # (a member keeps to its lane from batch to batch: one workspace per member)
-                    lanes.run(lambda s_, lane, m=m: m.forward_accumulate(images, s_, lane=lane))
-                lanes.end(merge_statistics)
-                st.recipe = run
-                return st
+                engine = HipEngine(members[0], mi, var, self.exact and len(members) <= _lib.RCU_MC_EXACT_MAX_PASSES)
+                stats = engine.side_statistics(images)
+                lanes = min(self.lanes, len(members))
+                run_plan(launch_plan(range(1, len(members) + 1), lanes=lanes, members=True), engine, images, stats, lanes=lanes, members=members)
+                stats.recipe = run
+                return stats
             batch_context.output['multi_probabilities'] = run(self.do_mi, self.do_var)
         else:
             batch_context.output['multi_probabilities'] = torch.stack([softmax(m(images)) for m in members])
@@ -655,42 +861,22 @@ class AleatoricMcPredictStep(BatchStep):
         if not isinstance(model, model_mod.UNet) or not model.sigma_out:
             raise ValueError('AleatoricMcPredictStep needs a rcu_amd.model.UNet built with sigma_out=True')
         n, _, h, w = images.shape
-        c = model.nb_classes
-        if self.ws_pass:
-            logits, sigma_raw = model(images)
-            probs = torch.empty_like(logits)
-            sigma = torch.empty_like(logits)
-            _lib.check(_lib.load().rcu_aleatoric(_lib.ptr(logits), _lib.ptr(sigma_raw.contiguous()), n, h * w, c,
-                                                 int(self.is_log_sigma), _lib.ptr(probs), _lib.ptr(sigma), None, None,
-                                                 _lib.current_stream()))
-            batch_context.output['ws_probabilities'] = probs
-            batch_context.output['ws_sigma'] = sigma
-        set_dropout_mode(model, is_train=True)
+        engine = AleatoricHipEngine(model, self.is_log_sigma, self.do_mi, self.do_var, self.exact)
+        ws = torch.empty((2, n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
+        stats = engine.side_statistics(images)
+        # pass groups and stream lanes as in McPredictStep: g passes per launch, launches alternating over two HIP streams
+        group = pass_group_size(model, n, h, w, McPredictStep.GROUP_PIXELS)
+        lanes = max(1, min(self.lanes, self.mc_steps))
+        plan = launch_plan(([0] if ws is not None else []) + list(range(1, self.mc_steps + 1)), (0,), max(self.mc_steps, 1), group, lanes)
         try:
-            dev = images.device
-
-            def fresh():
-                st = McStatistics(n, c, h, w, dev, self.do_mi, self.do_var, exact=self.exact)
-                st.sigma_sum = torch.zeros((n, c, h, w), device=dev, dtype=torch.float32)
-                return st
-
-            stats = fresh()
-            sigma_sum = stats.sigma_sum
-            # pass groups and stream lanes as in McPredictStep: g passes per launch, launches alternating over two HIP streams
-            group = pass_group_size(model, n, h, w, McPredictStep.GROUP_PIXELS)
-            lanes = StreamLanes(dev, min(self.lanes, self.mc_steps))
-            lanes.begin(stats, fresh, inputs=(images,))
-            i = 0
-            for g in balanced_groups(self.mc_steps, group, lanes.count):
-                masks = None if self.masks is None else (self.masks[i] if g == 1 else self.masks[i:i + g])
-                lanes.run(lambda st, lane, masks=masks, g=g: model.forward_accumulate_sigma(images, st, st.sigma_sum, masks, self.is_log_sigma,
-                                                                                         lane=lane, passes=g))
-                i += g
-            lanes.end(merge_statistics)
-            batch_context.output['multi_probabilities'] = stats
-            batch_context.output['sigma'] = sigma_sum.div_(float(max(self.mc_steps, 1)))
+            run_plan(plan, engine, images, stats, ws, lanes, reserve=(self.mc_steps, group),
+                     draw=lambda e, jobs: launch_masks(engine, images, e, jobs, max(self.mc_steps, 1), mask_sets=self.masks))
         finally:
             set_dropout_mode(model, is_train=False)
+        if ws is not None:
+            batch_context.output['ws_probabilities'], batch_context.output['ws_sigma'] = ws[0], ws[1]
+        batch_context.output['multi_probabilities'] = stats
+        batch_context.output['sigma'] = stats.sigma_sum.div_(float(max(self.mc_steps, 1)))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -840,72 +1026,31 @@ class TtaMcPredictStep(BatchStep):
         seed = self.seed
         if seed is None and self.mc_steps > 0:
             seed = int(torch.randint(2 ** 31 - 1, (1,)).item())
-        group = pass_group_size(model, n, h, w, self.group_pixels)
-        reserve_canonical_plans(model, n, h, w, self.mc_steps, group, 1 if self.materialize else min(self.lanes, self.samples))
-
-        def ws_pass():
-            set_dropout_mode(model, is_train=False)
-            batch_context.output['ws_probabilities'] = softmax(model(images))
-
         if self.materialize:
+            reserve_canonical_plans(model, n, h, w, self.mc_steps, pass_group_size(model, n, h, w, self.group_pixels), 1)
             if self.ws_pass:
-                ws_pass()
+                set_dropout_mode(model, is_train=False)
+                batch_context.output['ws_probabilities'] = softmax(model(images))
             batch_context.output['multi_probabilities'] = self._materialized(model, images, k, seed)
         else:
-            batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, seed,
-                                                                      before=ws_pass if self.ws_pass else None)
+            ws = torch.empty((n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
+            if ws is not None:
+                batch_context.output['ws_probabilities'] = ws
+            batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, seed, ws)
 
-    def _masks(self, model, images, e, first, count, first_sample, seed):
-        """Masks of passes first + 1 .. first + count of transform e (None in eval mode)."""
-        if self.mc_steps == 0:
-            return None
-        return model.seeded_masks(images.shape[0], images.device, [tta_pass_seed(seed, e, j + 1) for j in range(first, first + count)], first_sample)
-
-    def _transformed(self, images):
-        return {e: (images if e == 0 else tta_transform(images, e)) for e in self.elements}
-
-    def _fused(self, model, images, do_mi, do_var, first_sample, seed, before=None):
+    def _fused(self, model, images, do_mi, do_var, first_sample, seed, ws=None):
         n, _, h, w = images.shape
-        dev = images.device
-
-        def fresh():
-            return McStatistics(n, model.nb_classes, h, w, dev, do_mi, do_var, exact=self.exact)
-
-        xs = self._transformed(images)
-        stats = fresh()
+        engine = HipEngine(model, do_mi, do_var, self.exact)
+        stats = engine.side_statistics(images)
         group = pass_group_size(model, n, h, w, self.group_pixels)
-        lanes = StreamLanes(dev, min(self.lanes, self.samples))
-        sizes = balanced_groups(self.passes_per_transform, group, lanes.count)
-        lanes.begin(stats, fresh, inputs=tuple(xs.values()))
-        if before is not None:
-            before()                   # (the weight-scaling pass, on the caller's stream, in eval mode)
-        set_dropout_mode(model, is_train=self.mc_steps > 0)
-        scratch = [None] * lanes.count       # per lane: the statistics of the current transform's passes, reused from transform to transform
+        lanes = min(self.lanes, self.samples)
+        per = self.passes_per_transform
+        plan = launch_plan(([0] if ws is not None else []) + list(range(1, self.samples + 1)), self.elements, per, group, lanes)
+        draw = None if self.mc_steps == 0 else (lambda e, jobs: launch_masks(engine, images, e, jobs, per, seed, first_sample))
         try:
-            for v, e in enumerate(self.elements):
-                used, i = [], 0
-                for q, g in enumerate(sizes):
-                    lane = (v + q) % lanes.count
-
-                    def launch(st, lane, e=e, i=i, g=g):
-                        if e != 0:
-                            if scratch[lane] is None:
-                                scratch[lane] = fresh()          # (zeroed on the lane's stream)
-                            st = scratch[lane]
-                        model.forward_accumulate(xs[e], st, self._masks(model, images, e, i, g, first_sample, seed), passes=g, lane=lane)
-                    lanes.run(launch, lane=lane)
-                    if lane not in used:
-                        used.append(lane)
-                    i += g
-                if e != 0:
-                    for lane in sorted(used):
-                        def fold(st, lane, e=e):
-                            fold_transformed(scratch[lane], st, e)
-                            restart_statistics(scratch[lane])
-                        lanes.run(fold, lane=lane)
+            run_plan(plan, engine, images, stats, ws, lanes, draw=draw, reserve=(self.mc_steps, group))
         finally:
             set_dropout_mode(model, is_train=False)
-        lanes.end(merge_statistics)
 
         def recipe(mi, var, materialize=False):
             if materialize:
@@ -917,13 +1062,13 @@ class TtaMcPredictStep(BatchStep):
 
     def _materialized(self, model, images, first_sample, seed):
         """The V x T probability volumes ``[V*T, N, C, H, W]`` in canonical orientation, transform-major in the given order."""
-        xs = self._transformed(images)
+        xs = {e: (images if e == 0 else tta_transform(images, e)) for e in self.elements}
         probs = []
         set_dropout_mode(model, is_train=self.mc_steps > 0)
         try:
             for e in self.elements:
-                for j in range(self.passes_per_transform):
-                    masks = self._masks(model, images, e, j, 1, first_sample, seed)
+                for j in range(1, self.passes_per_transform + 1):
+                    masks = None if self.mc_steps == 0 else model.seeded_masks(images.shape[0], images.device, [tta_pass_seed(seed, e, j)], first_sample)
                     p = softmax(model(xs[e]) if masks is None else model(xs[e], masks))
                     probs.append(p if e == 0 else tta_transform(p, TTA_INVERSE[e]))
         finally:

@@ -60,7 +60,7 @@ wrap(steps.McStatistics, '__init__', 'McStatistics.__init__')
 wrap(model.UNet, 'sample_masks')
 wrap(model.UNet, 'group_masks')
 wrap(evaluation, 'uncertainty_counts')
-wrap(steps.McPredictStep, '_launch_masks')
+wrap(steps, 'launch_masks')
 wrap(steps.McPredictStep, '__call__', 'McPredictStep.__call__')
 wrap(steps.MultiPredictionSummary, '__call__', 'MultiPredictionSummary.__call__')
 wrap(model.UNet, 'forward_accumulate')
