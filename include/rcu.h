@@ -376,6 +376,39 @@ int rcu_tta_transform(const float* x_dev, size_t n, int channels, int height, in
 int rcu_mc_fold_transformed(const void* src_stats_dev, void* dst_stats_dev, size_t n, int height, int width, int nb_classes, int flags,
                             int element, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Temperature scaling (EXTENSION: the reference has no calibration fitting; rcu_amd.calibration)
+ *   Post-hoc scaling of the classifier by one scalar T: every pass's logits become z / T before the softmax (Guo et al. 2017 for one
+ *   deterministic pass, Laves et al. 2019 for MC dropout), T fitted to minimise the NLL of the pass-averaged prediction on held-out volumes.
+ * ------------------------------------------------------------------------------------------ */
+/* Scale the classifier of the handle by 1 / temperature: at rcu_unet_finalize_weights, conv_cls.1.weight and .bias are packed as
+ * (float)((double)w / temperature) -- conv_cls.1 is a 1x1 conv, so softmax((Wx + b) / T) = softmax((W / T) x + b / T) and every forward path
+ * (fused and standalone head, MC statistics, TTA, pass groups) honours T with no kernel change.  The sigma head is not touched.
+ * Call before rcu_unet_finalize_weights (afterwards: RCU_ERR_STATE; rcu_unet_load_weight re-opens the handle); temperature finite and > 0,
+ * else RCU_ERR_INVALID; a sigma_out handle is RCU_ERR_INVALID (its sigma is in logit units: scaling the mean alone has no defined meaning).
+ * T = 1 packs the bytes of a handle that never called this. */
+int rcu_unet_set_temperature(rcu_unet* h, double temperature);
+
+/* NLL sweep over n_candidates inverse temperatures beta_k (beta_host: finite, > 0).
+ *   logits_dev  [passes][n][C][hw] float32: the pass-major output of ONE rcu_unet_forward over the batch repeated `passes` times (sample t * n + i),
+ *               masks from rcu_dropout_masks with the passes' seeds -- or eval-mode logits with passes = 1
+ *   target_dev  [n][hw] class indices; mask_dev [n][hw] (voxels with mask != 0) or NULL (all voxels)
+ * For every voxel v inside the mask and every k:  l_k(v) = -log( (1/P) sum_t softmax(beta_k z_{t,v})[y_v] ), computed in float32 in the log
+ * domain (correct when every pass's probability underflows float32), clamped to [0, 4096], rounded to the nearest multiple of 2^-20 (ties to
+ * even) and ADDED as an unsigned 64-bit integer: out_dev[k] += sum_v round(l_k(v) * 2^20).  out_dev[n_candidates] += the number of voxels
+ * summed, out_dev[n_candidates + 1] += the number of voxels inside the mask whose target is >= C (they are left out of the sums).  The caller
+ * zeroes out_dev once; every call adds to it, stream-ordered.  Integer sums: the result does not depend on how the voxels are split over
+ * workgroups or calls (the idea of RCU_MC_EXACT).
+ * Limits: 2 <= C <= 8, 1 <= passes <= RCU_MC_EXACT_MAX_PASSES, 1 <= n_candidates <= 128, n >= 1, hw >= 1, n * hw < 2^32.  Every argument is
+ * checked before the device is touched (RCU_ERR_INVALID).  workspace_dev: rcu_temperature_nll_workspace_bytes(n * hw, n_candidates) bytes. */
+size_t rcu_temperature_nll_workspace_bytes(size_t voxels, int n_candidates);
+int rcu_temperature_nll(const float* logits_dev, int passes, size_t n, size_t hw, int nb_classes, const uint8_t* target_dev,
+                        const uint8_t* mask_dev, const float* beta_host, int n_candidates, uint64_t* out_dev, void* workspace_dev, void* stream);
+/* Test aid (as rcu_ece_bin_ids): the float32 l(v) of every voxel for one beta, the arithmetic of rcu_temperature_nll bit for bit (before the
+ * clamp); 0 outside the mask and where the target is >= C.  terms_dev: [n][hw] float32. */
+int rcu_temperature_nll_terms(const float* logits_dev, int passes, size_t n, size_t hw, int nb_classes, const uint8_t* target_dev,
+                              const uint8_t* mask_dev, float beta, float* terms_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ RCU_MC_EXACT_MAX_PASSES = 2048
 RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
 # test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
+# temperature scaling (include/rcu.h): candidates per rcu_temperature_nll call
+RCU_TEMPERATURE_MAX_CANDIDATES = 128
 TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
@@ -115,6 +117,11 @@ SIGNATURES = {
                                       c_void_p]),
     'rcu_tta_transform': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_mc_fold_transformed': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'rcu_unet_set_temperature': (c_int, [c_void_p, c_double]),
+    'rcu_temperature_nll_workspace_bytes': (c_size_t, [c_size_t, c_int]),
+    'rcu_temperature_nll': (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p,
+                                    c_void_p, c_void_p]),
+    'rcu_temperature_nll_terms': (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

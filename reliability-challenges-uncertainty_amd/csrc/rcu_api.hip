@@ -99,6 +99,7 @@ struct rcu_unet {
     int t_features = -1;      // provide_features on a padded level 0: the compact [voxel][channel] copy rcu_unet_features hands out
     std::map<std::string, std::vector<float>> host_weights;
     float *w_cls = nullptr, *b_cls = nullptr, *w_sig = nullptr, *b_sig = nullptr;
+    double temperature = 1.0;  // rcu_unet_set_temperature: conv_cls.1 is packed divided by it
     bool finalized = false;
     bool plan_only = false;   // rcu_unet_plan: no workspace -- the handle can be inspected, never run
     int64_t workspace_bytes = 0;
@@ -657,6 +658,18 @@ extern "C" int rcu_unet_set_fuse_head(rcu_unet* h, int on)
     return RCU_OK;
 }
 
+extern "C" int rcu_unet_set_temperature(rcu_unet* h, double temperature)
+{
+    if (!h) return fail(RCU_ERR_INVALID, "rcu_unet_set_temperature: null handle");
+    if (!std::isfinite(temperature) || !(temperature > 0.0))
+        return fail(RCU_ERR_INVALID, "rcu_unet_set_temperature: the temperature must be finite and > 0");
+    if (h->d.sigma_out)
+        return fail(RCU_ERR_INVALID, "rcu_unet_set_temperature: a sigma_out model's sigma is in logit units; scaling the logits alone is not defined");
+    if (h->finalized) return fail(RCU_ERR_STATE, "rcu_unet_set_temperature after rcu_unet_finalize_weights");
+    h->temperature = temperature;
+    return RCU_OK;
+}
+
 extern "C" int rcu_unet_destroy(rcu_unet* h)
 {
     if (!h) return RCU_OK;
@@ -898,20 +911,24 @@ extern "C" int rcu_unet_finalize_weights(rcu_unet* h)
     }
     // 1x1 heads (unet.py:161, 164): [C][CPh] zero padded
     const int C = h->d.nb_classes, cph = h->head_cph, creal = h->layers.back().cout;
-    auto head = [&](const std::string& key, float** w_dev, float** b_dev) -> int {
+    // `temperature` (rcu_unet_set_temperature): the classifier divided by T, (float)((double)w / T) -- T = 1 leaves every value as it is
+    auto head = [&](const std::string& key, float** w_dev, float** b_dev, double temperature) -> int {
         const std::vector<float>*w, *b;
         int rc = get_weight(h, key + ".weight", (size_t)C * creal, &w);
         if (rc) return rc;
         if ((rc = get_weight(h, key + ".bias", (size_t)C, &b))) return rc;
+        auto scaled = [temperature](float v) { return temperature == 1.0 ? v : (float)((double)v / temperature); };
         std::vector<float> wp((size_t)C * cph, 0.f);
         for (int c = 0; c < C; ++c)
-            for (int k = 0; k < creal; ++k) wp[(size_t)c * cph + k] = (*w)[(size_t)c * creal + k];
+            for (int k = 0; k < creal; ++k) wp[(size_t)c * cph + k] = scaled((*w)[(size_t)c * creal + k]);
         if ((rc = upload(h, wp, w_dev))) return rc;
-        return upload(h, *b, b_dev);
+        std::vector<float> bp(b->size());
+        for (size_t c = 0; c < b->size(); ++c) bp[c] = scaled((*b)[c]);
+        return upload(h, bp, b_dev);
     };
-    int rc = head("conv_cls.1", &h->w_cls, &h->b_cls);
+    int rc = head("conv_cls.1", &h->w_cls, &h->b_cls, h->temperature);
     if (rc) return rc;
-    if (h->d.sigma_out && (rc = head("conv_sigma.1", &h->w_sig, &h->b_sig))) return rc;
+    if (h->d.sigma_out && (rc = head("conv_sigma.1", &h->w_sig, &h->b_sig, 1.0))) return rc;
     h->host_weights.clear();
     h->finalized = true;
     return RCU_OK;

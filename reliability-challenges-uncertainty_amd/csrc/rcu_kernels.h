@@ -268,6 +268,13 @@ hipError_t launch_unc_counts_from_p(const float* p_fg, const uint8_t* prediction
                                     hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
+// temperature scaling: NLL sweep over candidate inverse temperatures (rcu_temperature.hip; entry points rcu_temperature_nll*)
+// ---------------------------------------------------------------------------------------------
+constexpr int TN_MAX_CANDIDATES = 128;
+// bytes of the per-workgroup partials of one rcu_temperature_nll call over `voxels` voxels
+size_t temperature_nll_workspace_bytes(size_t voxels, int n_candidates);
+
+// ---------------------------------------------------------------------------------------------
 // PostNet: fused 1x1-conv stack on the U-Net feature map (rcu_postnet.hip)
 // ---------------------------------------------------------------------------------------------
 // packed layer of CB x CB blocks of 32 channels: weight tiles + accumulator start values + constants behind the dropout factor

@@ -119,6 +119,7 @@ class UNet(nn.Module):
         self.fuse_head = True    # 1x1 classifier + softmax + statistics inside conv_cls.0's epilogue where the shapes allow
         self._donor = None       # share_workspace(): the model whose activation workspaces this one's plans borrow
         self._last_generation = 0   # generation of the plan _handle returned last
+        self.temperature = 1.0   # set_temperature: the classifier conv_cls.1 is packed divided by it
         self.eval()
 
     # ------------------------------------------------------------------ weights
@@ -131,6 +132,24 @@ class UNet(nn.Module):
     def weights_changed(self):
         """Call after editing parameters in place: the packed device copies are rebuilt lazily."""
         self._weights_version += 1
+
+    def set_temperature(self, t):
+        """EXTENSION (temperature scaling, rcu_amd.calibration): every forward path -- logits, the fused and the standalone head, MC
+        statistics, TTA, pass groups -- computes softmax(logits / t).  The library packs conv_cls.1 (a 1x1 conv) divided by t (include/rcu.h,
+        rcu_unet_set_temperature); cached plans are repacked.  ``state_dict()`` stays the checkpoint's.  t = 1 is the unscaled model bit for bit.
+        A ``sigma_out`` model refuses it: its sigma is in logit units."""
+        import math
+        try:
+            value = float(t)
+        except (TypeError, ValueError):
+            raise ValueError('the temperature must be a number, got {!r}'.format(t)) from None
+        if isinstance(t, bool) or not math.isfinite(value) or value <= 0:
+            raise ValueError('the temperature must be finite and > 0, got {!r}'.format(t))
+        if self.sigma_out:
+            raise ValueError('temperature scaling is not defined for a sigma_out model (its sigma is in logit units)')
+        if value != self.temperature:
+            self.temperature = value
+            self.weights_changed()
 
     def share_workspace(self, donor):
         """Borrow the activation workspaces of ``donor`` -- a UNet of the same architecture -- instead of allocating 6 GB per 160
@@ -221,6 +240,8 @@ class UNet(nn.Module):
                 host = value.detach().to('cpu', torch.float32).contiguous()
                 _lib.check(lib.rcu_unet_load_weight(handle, key.encode(), ctypes.c_void_p(host.data_ptr()),
                                                     host.numel()))
+            if self.temperature != 1.0:
+                _lib.check(lib.rcu_unet_set_temperature(handle, float(self.temperature)))
             _lib.check(lib.rcu_unet_finalize_weights(handle))
         except Exception:
             lib.rcu_unet_destroy(handle)

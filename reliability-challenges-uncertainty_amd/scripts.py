@@ -8,15 +8,18 @@ Each function is the ``main`` of the same-named reference script (flags unchange
     bin-dl/{brats,isic}_test_auxiliary_feat.py -config_file       (bin-dl/brats_test_auxiliary_feat.py:23-61)
     bin-dl/{brats,isic}_test_auxiliary_segm.py -config_file       (bin-dl/brats_test_auxiliary_segm.py:23-47)
     bin-eval/eval_uncertainty.py   --ds --ids --act               (bin-eval/eval_uncertainty.py:13-50, 248-288)
+    bin-dl/{brats,isic}_fit_temperature.py -config_file           (EXTENSION: temperature scaling, fit_temperature)
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
 """
+import json
 import logging
 import os
 
 import numpy as np
 import torch
 
+from . import calibration
 from . import data as data_mod
 from . import distributed as rdist
 from . import evalrun
@@ -377,6 +380,33 @@ def _refuse_tta(context, script):
         raise ValueError('others.tta (test-time augmentation) applies to the default test scripts only; the {} script does not take it'.format(script))
 
 
+def _refuse_temperature(context, script):
+    if hasattr(context.config.others, 'temperature'):
+        raise ValueError('others.temperature (temperature scaling) applies to the default test scripts only; the {} script does not take it'
+                         .format(script))
+
+
+class ApplyTemperatureHook(loops.TestLoopHook):
+    """``others.temperature`` (an rcu_amd extension): the model loaded by the test loop is scaled by T (UNet.set_temperature) before the first
+    batch -- on every rank of a sharded run."""
+
+    def __init__(self, temperature):
+        self.temperature = temperature
+
+    def end_startup(self, context):
+        set_temperature = getattr(context.model, 'set_temperature', None)
+        if set_temperature is None:
+            raise ValueError('others.temperature: the model has no temperature scaling')
+        set_temperature(self.temperature)
+
+
+def _temperature_hooks(context):
+    """``others.temperature``: a positive float or the path of a temperature.json (calibration.load_temperature), read before the run starts."""
+    if not hasattr(context.config.others, 'temperature'):
+        return []
+    return [ApplyTemperatureHook(calibration.load_temperature(context.config.others.temperature))]
+
+
 def _default_steps(context, world):
     if hasattr(context.config.others, 'tta'):
         return _tta_steps(context, world)
@@ -439,7 +469,7 @@ def _context(device, config_file):
     return context, world
 
 
-def _run(context, dataset, test_steps, write_hook, entries, world=None):
+def _run(context, dataset, test_steps, write_hook, entries, world=None, startup_hooks=()):
     world = world if world is not None else rdist.World()
     sharded = [s_ for s_ in test_steps if isinstance(s_, rdist._ShardedStepBase)]
     if world.world > 1 and not sharded:
@@ -449,7 +479,7 @@ def _run(context, dataset, test_steps, write_hook, entries, world=None):
             return context
     build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
     options = _loop_options(context)
-    extra_hooks = []
+    extra_hooks = list(startup_hooks)
     spec = _other(context, 'device_metrics')
     if spec and world.is_root:      # opt-in: the evaluation's metrics on the maps while they are in HBM (DeviceMetricsHook)
         store = {}
@@ -466,7 +496,7 @@ def _run(context, dataset, test_steps, write_hook, entries, world=None):
         # (the same coalescing: every rank must see the root's batches -- their shapes size the collective, their indices rotate the jobs)
         test = loops.Test(test_steps, [], None, entries=(), coalesce=options['coalesce'], pipelined=options['pipelined'],
                           max_inflight=options['max_inflight'])
-        hook = loops.TestLoopHook()
+        hook = loops.ReducedComposeTestLoopHook(list(startup_hooks)) if startup_hooks else loops.TestLoopHook()
     elif dataset == 'brats':
         test = loops.Test(test_steps, [loops.ExtractSubjectInfoStep(), EvalSubjectStep()], loops.SubjectAssembler(),
                           entries=entries, **options)
@@ -520,12 +550,14 @@ def _abandon_process_group(timeout_s=10.0):
 def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     entries = ('probabilities',) if dataset == 'brats' else None
-    return _run(context, dataset, _default_steps(context, world), WriteHook(link_inputs=dataset == 'isic'), entries, world)
+    return _run(context, dataset, _default_steps(context, world), WriteHook(link_inputs=dataset == 'isic'), entries, world,
+                startup_hooks=_temperature_hooks(context))
 
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_ensemble.yaml'.format(dataset)))
     _refuse_tta(context, 'ensemble')
+    _refuse_temperature(context, 'ensemble')
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
     if world.world > 1:     # the K members of every batch sharded over the ranks (bin-dl/brats_test_ensemble.py:44-59 on N GPUs)
@@ -538,6 +570,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
 def test_aleatoric(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_aleatoric.yaml'.format(dataset)))
     _refuse_tta(context, 'aleatoric')
+    _refuse_temperature(context, 'aleatoric')
     return _run(context, dataset, [steps.AleatoricPredictStep()], WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world)
 
@@ -679,6 +712,7 @@ def _single_rank_only(world):
 def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_feat.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_feat')
+    _refuse_temperature(context, 'auxiliary_feat')
     if not _single_rank_only(world):
         return context
     test_model = _load_segmentation_model(context)
@@ -700,6 +734,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
 def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_segm.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_segm')
+    _refuse_temperature(context, 'auxiliary_segm')
     if not _single_rank_only(world):
         return context
     if dataset == 'brats':
@@ -719,7 +754,78 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     return context
 
 
-for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm):
+# ------------------------------------------------------------------------------- temperature scaling (EXTENSION)
+def _validation_batches(context, dataset, device):
+    """(images, target) per loader batch of ``test_data`` -- the validation volumes, read as the test scripts read theirs -- with the target the
+    evaluation binarises to (labels > 0, rechun/eval/analysis.py: target > 0), on the device."""
+    loader = context.test_data.loader
+    volumes = {}
+    for batch in loader:
+        images = batch['images'].float().to(device)
+        images = images.contiguous()
+        n, _, h, w = images.shape
+        if dataset == 'brats':
+            source = context.test_data.dataset
+            pieces = []
+            for si, k in zip(batch['subject_index'], batch['slice_index']):
+                si, k = int(si), int(k)
+                if si not in volumes:
+                    volumes.clear()
+                    labels = np.asarray(source.direct_extract(si, ('labels',))['labels'])
+                    volumes[si] = torch.from_numpy(np.ascontiguousarray(labels.reshape(labels.shape[:3]) > 0).astype(np.uint8)).to(device)
+                pieces.append(volumes[si][k])
+            target = torch.stack(pieces)
+        else:
+            labels = batch['labels']
+            labels = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+            target = (labels.to(device).reshape(n, h, w) > 0).to(torch.uint8)
+        yield images, target
+
+
+def fit_temperature(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_temperature.py (EXTENSION): fit the temperature of a test configuration's model on the volumes its ``test_data``
+    names -- the VALIDATION volumes -- by the NLL of the pass-averaged prediction (``others.mc`` passes with the YAML ``seed``, 0 without one,
+    else one eval-mode pass), on all voxels, target labels > 0.  Writes ``temperature.json`` into the run directory and returns the fit;
+    ``others.temperature: <that file>`` applies it in the default test scripts."""
+    if dataset not in ('brats', 'isic'):
+        raise ValueError('chose "brats" or "isic" as dataset')
+    context, world = _context(device, config_file)
+    if world.world > 1:
+        raise ValueError('the temperature fit runs in one process; launch it without torch.distributed.run')
+    others = context.config.others
+    if hasattr(others, 'tta'):
+        raise ValueError('others.tta: the temperature fit does not run under test-time augmentation')
+    _refuse_temperature(context, 'fit_temperature')
+    mc = int(getattr(others, 'mc', 0) or 0)
+    seed = 0 if context.config.seed is None else int(context.config.seed)
+    context.load_from_checkpoint(context.get_test_at())
+    model = context.model
+    if not hasattr(model, 'set_temperature'):
+        raise ValueError('the temperature fit needs a U-Net segmentation model')
+    if model.sigma_out:
+        raise ValueError('the temperature fit is not defined for a sigma_out model (its sigma is in logit units)')
+    if model.nb_classes != 2:
+        raise ValueError('the temperature fit scripts take binary models (nb_classes = 2), got {}'.format(model.nb_classes))
+    context.setup_directory()
+    context.setup_logging()
+    context.do_seed(seed)
+    build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
+    context.load_test_data(build)
+    fit = calibration.fit_temperature(model, _validation_batches(context, dataset, context.device), mc_steps=mc, seed=seed,
+                                      group_pixels=_other(context, 'group_pixels'))
+    record = dict(fit.as_dict(), model_dir=context.config.model_dir, test_at=context.config.test_at,
+                  dataset=context.config.test_data.dataset, mc=mc)
+    path = os.path.join(context.test_dir, 'temperature.json')
+    with open(path, 'w') as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write('\n')
+    logging.info('temperature %.6f (mean NLL %.6f at T = 1, %.6f at the best candidate, %d voxels, %d passes) -> %s', fit.temperature,
+                 fit.mean_nll_at_1, fit.mean_nll_at_best_candidate, fit.voxels, fit.passes, path)
+    print('temperature: {!r}'.format(fit.temperature))
+    return fit
+
+
+for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature):
     _fn.__test__ = False   # not pytest tests
 
 
