@@ -409,6 +409,43 @@ int rcu_temperature_nll(const float* logits_dev, int passes, size_t n, size_t hw
 int rcu_temperature_nll_terms(const float* logits_dev, int passes, size_t n, size_t hw, int nb_classes, const uint8_t* target_dev,
                               const uint8_t* mask_dev, float beta, float* terms_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time logit sampling (EXTENSION: the reference writes softmax(mu) of its sigma-head models; rcu_amd.steps.AleatoricPredictStep /
+ * AleatoricMcPredictStep with logit_samples = S)
+ *   A sigma-head U-Net (sigma_out) is trained on the NLL of E_eps[softmax(mu + sigma * eps)] (Kendall & Gal 2017).  At test time the sampled
+ *   predictive of a voxel with logits mu[c] and raw sigma raw[c] (c < C <= 8) is
+ *       sig[c]   = is_log_sigma ? expf(raw[c]) : fabsf(raw[c])
+ *       p_bar[c] = (1/S) sum_{s < S} softmax(mu + sig * z_s)[c]     (for s in order: x[c] = fmaf(sig[c], z, mu[c]), softmax, float32 sum; / S)
+ *   with the normal z(K, g, p, s, c) of the pass key K, the slice's GLOBAL index g, the pixel p = y * W + x, the sample s and the class c:
+ *       j = s * C + c;  w[0..3] = Philox4x32-10(key (K lo, K hi), counter (p, g lo, g hi, 2^31 | j >> 2))
+ *       u[i] = ((w[i] >> 8) + 0.5f) * 2^-24 in float32;  (a, b) = (u0, u1) if (j & 3) < 2 else (u2, u3)
+ *       r = sqrtf(-2 logf(a)),  sincospif(2 b, &sn, &cs),  z = (j & 1) ? r sn : r cs
+ *   Bit 31 of counter word 3 keeps the noise apart from rcu_dropout_masks (words 2 and 3 are 0 there): a pass may use its mask key.  The first
+ *   S samples do not depend on the total S.  With MC dropout pass t adds p_bar_t where it would add softmax(mu_t): entropy of the mean is the
+ *   total uncertainty, the mutual information the epistemic part and entropy - mutual information = mean_t H(p_bar_t) the aleatoric part.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_LOGIT_MAX_SAMPLES 1024
+
+/* Test aid: out_dev[v][s][c] = z(key, first_sample + v / hw, v % hw, s, c) for the n * hw voxels v, s < samples, c < nb_classes (float32,
+ * n * hw * samples * nb_classes elements).  RCU_ERR_INVALID for a null out_dev, nb_classes outside 1..8, samples outside
+ * 1..RCU_LOGIT_MAX_SAMPLES, n or hw of 0, hw >= 2^32. */
+int rcu_logit_normals(uint64_t key, uint64_t first_sample, size_t n, size_t hw, int nb_classes, int samples, float* out_dev, void* stream);
+/* The sampled predictive of materialised logits_dev and sigma_raw_dev ([n][nb_classes][hw] float32, the outputs of rcu_unet_forward) under
+ * `key`, image i being slice first_sample + i: written to probs_dev ([n][nb_classes][hw], or NULL) and / or added to the statistics blob
+ * stats_dev (rcu_mc_stats_bytes layout, flags a combination of RCU_MC_MI, RCU_MC_VAR, RCU_MC_EXACT -- the addition of rcu_mc_accumulate with
+ * p_bar in place of the softmax; or NULL).  RCU_ERR_INVALID for null inputs, both outputs NULL, other flags, and the limits of
+ * rcu_logit_normals. */
+int rcu_logit_sampling(const float* logits_dev, const float* sigma_raw_dev, size_t n, size_t hw, int nb_classes, int is_log_sigma, int samples,
+                       uint64_t key, uint64_t first_sample, float* probs_dev, void* stats_dev, int flags, void* stream);
+/* rcu_unet_forward_accumulate_sigma_passes with the sampled predictive: pass t of the group (masks as there) adds p_bar_t under keys_host[t]
+ * ([passes] on the host, read before the call returns) into stats_dev, and its sig to sigma_sum_dev exactly as
+ * rcu_unet_forward_accumulate_sigma_passes adds it.  Image i is slice first_sample + i.  Neither mu nor sigma reaches HBM: the sampling runs
+ * in the head kernel (a group of more than 32 passes as one head launch per 32 passes, in pass order -- the same bits).  RCU_ERR_INVALID for
+ * a null handle or pointer, a handle without sigma_out, n * passes outside 1..max_batch, samples outside 1..RCU_LOGIT_MAX_SAMPLES. */
+int rcu_unet_forward_sample_sigma_passes(rcu_unet* h, const float* x_dev, int n, int passes, const float* masks_dev, const uint64_t* keys_host,
+                                         uint64_t first_sample, int samples, void* stats_dev, int flags, float* sigma_sum_dev, int is_log_sigma,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

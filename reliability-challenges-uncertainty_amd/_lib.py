@@ -22,6 +22,8 @@ RCU_MAX_THRESHOLDS = 16
 # test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
 # temperature scaling (include/rcu.h): candidates per rcu_temperature_nll call
 RCU_TEMPERATURE_MAX_CANDIDATES = 128
+# test-time logit sampling (include/rcu.h): samples per voxel
+RCU_LOGIT_MAX_SAMPLES = 1024
 TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
@@ -122,6 +124,11 @@ SIGNATURES = {
     'rcu_temperature_nll': (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, POINTER(c_float), c_int, c_void_p,
                                     c_void_p, c_void_p]),
     'rcu_temperature_nll_terms': (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    'rcu_logit_normals': (c_int, [c_uint64, c_uint64, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_logit_sampling': (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_int, c_int, c_uint64, c_uint64, c_void_p, c_void_p, c_int,
+                                   c_void_p]),
+    'rcu_unet_forward_sample_sigma_passes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, POINTER(c_uint64), c_uint64, c_int, c_void_p,
+                                                     c_int, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -1033,8 +1033,16 @@ static int run_layer(rcu_unet* h, const ConvLayer& L, int n, const float* masks,
 
 // `passes` > 1 (statistics only): the n images run as ONE batch of n * passes samples -- sample t * n + i is image i
 // under the mask rows [site][t * n + i] -- and the head adds all passes into the n statistics entries.
+// test-time logit sampling in the head (rcu_unet_forward_sample_sigma_passes): keys[t] of pass t, S samples per voxel
+struct HeadSampling {
+    const uint64_t* keys;
+    uint64_t first_sample;
+    int samples;
+};
+
 static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, float* logits, float* sigma, void* stats,
-                        int flags, hipStream_t stream, int passes = 1, float* sigma_sum = nullptr, int sigma_log = 0)
+                        int flags, hipStream_t stream, int passes = 1, float* sigma_sum = nullptr, int sigma_log = 0,
+                        const HeadSampling* sampling = nullptr)
 {
     if (!h || !x) return fail(RCU_ERR_INVALID, "rcu_unet_forward: null argument");
     if (!h->finalized) return fail(RCU_ERR_STATE, "rcu_unet_forward before rcu_unet_finalize_weights");
@@ -1058,7 +1066,7 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     // rcu_unet_set_fuse_head keep them apart): two classes, no sigma twin, 32-cout Winograd tile; the passes of a pass group run back to back on the
     // workgroup that owns the tile, so their read-modify-writes of the statistics are ordered (pass 0 first, as head_kernel adds them)
     const ConvLayer& last = h->layers.back();
-    const bool fuse = head_fusable(h) && sigma == nullptr && (logits != nullptr || stats != nullptr) && h->opt.fuse_head != 0;
+    const bool fuse = head_fusable(h) && sigma == nullptr && (logits != nullptr || stats != nullptr) && h->opt.fuse_head != 0 && sampling == nullptr;
     for (const ConvLayer& L : h->layers) {
         const FusedHead fh{logits, stats, flags, passes};
         int rc = run_layer(h, L, n, masks, stream, (fuse && &L == &last) ? &fh : nullptr, direct_input ? x : nullptr, n_one);
@@ -1082,7 +1090,12 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     a.HW = (size_t)h->d.height * h->d.width;
     a.V = a.HW * n_one;
     a.passes = passes;
-    RCU_HIP(launch_head(a, stream));
+    if (sampling) {
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "pass keys");
+        RCU_HIP(launch_head_sampled(a, reinterpret_cast<const unsigned long long*>(sampling->keys), sampling->first_sample, sampling->samples, stream));
+    } else {
+        RCU_HIP(launch_head(a, stream));
+    }
     if (ev) RCU_HIP(hipEventRecord(*ev++, stream));
     return RCU_OK;
 }
@@ -1153,6 +1166,23 @@ extern "C" int rcu_unet_forward_accumulate_sigma_passes(rcu_unet* h, const float
     if (!stats_dev || !sigma_sum_dev) return fail(RCU_ERR_INVALID, "rcu_unet_forward_accumulate_sigma_passes: null stats / sigma sum");
     return forward_impl(h, x_dev, n, masks_dev, nullptr, nullptr, stats_dev, flags & (RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT),
                         static_cast<hipStream_t>(stream), passes, sigma_sum_dev, is_log_sigma ? 1 : 0);
+}
+
+extern "C" int rcu_unet_forward_sample_sigma_passes(rcu_unet* h, const float* x_dev, int n, int passes, const float* masks_dev,
+                                                    const uint64_t* keys_host, uint64_t first_sample, int samples, void* stats_dev, int flags,
+                                                    float* sigma_sum_dev, int is_log_sigma, void* stream)
+{
+    const char* fn = "rcu_unet_forward_sample_sigma_passes";
+    if (!h) return fail(RCU_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!x_dev || !keys_host || !stats_dev || !sigma_sum_dev)
+        return fail(RCU_ERR_INVALID, std::string(fn) + ": null x_dev / keys_host / stats_dev / sigma_sum_dev");
+    if (!h->d.sigma_out) return fail(RCU_ERR_INVALID, std::string(fn) + ": the handle has no sigma head (sigma_out = 0)");
+    if (n < 1 || passes < 1 || (long)n * passes > h->d.max_batch)
+        return fail(RCU_ERR_INVALID, std::string(fn) + ": batch size (times passes) outside 1..max_batch");
+    if (int st = check_logit_sampling_shape(fn, (size_t)n, (size_t)h->d.height * h->d.width, h->d.nb_classes, samples)) return st;
+    const HeadSampling sampling{keys_host, first_sample, samples};
+    return forward_impl(h, x_dev, n, masks_dev, nullptr, nullptr, stats_dev, flags & (RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT),
+                        static_cast<hipStream_t>(stream), passes, sigma_sum_dev, is_log_sigma ? 1 : 0, &sampling);
 }
 
 extern "C" int rcu_unet_features(const rcu_unet* h, const float** features_dev, int* channels, int* channel_pitch)

@@ -133,5 +133,79 @@ struct VoxelStats {
     }
 };
 
+// ------------------------------------------------------------------------------- counter-based random numbers
+// Philox4x32-10 (Salmon et al., SC'11) under key (k0, k1) at the 128-bit counter (c0, c1, c2, c3).  The dropout masks draw with c2 = c3 = 0
+// (rcu_pointwise.hip, dropout_masks_kernel); the logit noise below sets bit 31 of c3, so the two never share a counter under one key.
+__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4])
+{
+    uint32_t c[4] = {c0, c1, c2, c3};
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
+}
+
+// ------------------------------------------------------------------------------- test-time logit sampling (sigma-head models)
+// include/rcu.h "Test-time logit sampling".  The normal z of (key K, slice g, pixel p, sample s, class c), j = s * C + c, is element j & 3 of
+// the block j >> 2: Philox4x32-10 under (K lo, K hi) at counter (p, g lo, g hi, 2^31 | j >> 2) gives four words w, u = ((w >> 8) + 0.5f) * 2^-24
+// in float32, and Box-Muller turns (u0, u1) into the block's elements 0 and 1 (r cos, r sin) and (u2, u3) into 2 and 3.
+__device__ __forceinline__ void logit_normals4(unsigned long long key, unsigned long long g, uint32_t p, uint32_t q, float (&z)[4])
+{
+    uint32_t w[4];
+    philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), p, (uint32_t)g, (uint32_t)(g >> 32), 0x80000000u | q, w);
+    float u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u[i] = ((float)(w[i] >> 8) + 0.5f) * 5.9604644775390625e-8f;     // 2^-24
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float r = sqrtf(-2.f * logf(u[2 * k]));
+        float sn, cs;
+        sincospif(2.f * u[2 * k + 1], &sn, &cs);
+        z[2 * k] = r * cs;
+        z[2 * k + 1] = r * sn;
+    }
+}
+
+// l: the logits mu in, the sampled predictive p_bar = (1/S) sum_s softmax(mu + sig * z_s) out (float32 sums in sample order).
+// sig: the voxel's sigma (|raw| or exp(raw)).  S, g and key are the same on every lane of a wave: the branches below are uniform.
+template <int C>
+__device__ __forceinline__ void logit_sample_predictive(float (&l)[C], const float (&sig)[C], unsigned long long key, unsigned long long g,
+                                                        uint32_t p, int S)
+{
+    float acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 0.f;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t block = 0xFFFFFFFFu;
+    for (int s = 0; s < S; ++s) {
+        float x[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const uint32_t j = (uint32_t)(s * C + c);
+            if ((j >> 2) != block) {
+                block = j >> 2;
+                logit_normals4(key, g, p, block, z);
+            }
+            const uint32_t e = j & 3u;
+            const float zj = e == 0 ? z[0] : e == 1 ? z[1] : e == 2 ? z[2] : z[3];
+            x[c] = fmaf(sig[c], zj, l[c]);
+        }
+        softmax_inplace<C>(x);
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] += x[c];
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) l[c] = acc[c] / (float)S;
+}
+
+// sigma of a raw sigma-head output: what rcu_aleatoric writes and the sigma sums add
+__device__ __forceinline__ float sigma_of_raw(float raw, int is_log_sigma) { return is_log_sigma ? expf(raw) : fabsf(raw); }
+
 
 }  // namespace rcu

@@ -206,6 +206,25 @@ struct HeadArgs {
                           // into the same V statistics entries, in pass order
 };
 hipError_t launch_head(const HeadArgs& a, hipStream_t stream);
+// test-time logit sampling of a sigma head (rcu_head_common.h, logit_sample_predictive): the head kernels with softmax(mu) replaced by the sampled
+// predictive of (mu, sigma) under keys[t] for pass t.  launch_head_sampled runs a pass group of more than SAMPLE_MAX_PASSES passes as one launch per
+// SAMPLE_MAX_PASSES passes, in pass order (keys_host: a.passes keys, or one for a single pass); a.stats is required.
+constexpr int LOGIT_MAX_SAMPLES = 1024;
+constexpr int SAMPLE_MAX_PASSES = 32;
+struct SampleArgs {
+    unsigned long long keys[SAMPLE_MAX_PASSES];   // key of pass t of the launch
+    unsigned long long first_sample;              // global index of the batch's image 0
+    int samples;                                  // S, 1..LOGIT_MAX_SAMPLES
+};
+hipError_t launch_head_sampled(const HeadArgs& a, const unsigned long long* keys_host, unsigned long long first_sample, int samples,
+                               hipStream_t stream);
+// standalone forms over materialised [n][C][hw] logits and raw sigma (rcu_logit_sampling.hip)
+hipError_t launch_logit_normals(unsigned long long key, unsigned long long first_sample, size_t n, size_t hw, int C, int samples, float* out,
+                                hipStream_t stream);
+hipError_t launch_logit_sampling(const float* logits, const float* sigma_raw, size_t n, size_t hw, int C, int is_log_sigma, int samples,
+                                 unsigned long long key, unsigned long long first_sample, float* probs, void* stats, int flags, hipStream_t stream);
+// RCU_ERR_INVALID (with its message) unless 1 <= nb_classes <= 8, 1 <= samples <= LOGIT_MAX_SAMPLES, n, hw >= 1 and hw < 2^32
+int check_logit_sampling_shape(const char* fn, size_t n, size_t hw, int nb_classes, int samples);
 
 hipError_t launch_mc_accumulate(const float* in_nchw, void* stats, int C, size_t N, size_t HW, int flags,
                                 hipStream_t stream);

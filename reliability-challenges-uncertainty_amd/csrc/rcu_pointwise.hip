@@ -210,9 +210,21 @@ __device__ __forceinline__ void head_logits(const HeadArgs& a, const float* __re
     head_reduce<C, SIG, CPH>(a, act, v0, lane, w, t, l, s);
 }
 
-// One 64-voxel group of the single-pass form: logits / sigma outputs, softmax, statistics update (the group's statistics entries in `st`).
-template <int C, bool SIG>
-__device__ __forceinline__ void head_finish(const HeadArgs& a, size_t v, float (&l)[C], const float (&s)[C], VoxelStats<C>& st)
+// softmax(mu) of one pass, or with SAMPLE (a sigma head: SIG) the sampled predictive of (mu, sig) under the pass's key (rcu_head_common.h)
+template <int C, bool SAMPLE>
+__device__ __forceinline__ void head_predictive(float (&l)[C], const float (&sg)[C], const SampleArgs* sa, int t, size_t n, size_t hw)
+{
+    if constexpr (SAMPLE)
+        logit_sample_predictive<C>(l, sg, sa->keys[t], sa->first_sample + n, (uint32_t)hw, sa->samples);
+    else
+        softmax_inplace<C>(l);
+}
+
+// One 64-voxel group of the single-pass form: logits / sigma outputs, softmax (SAMPLE: the sampled predictive under sa->keys[0]), statistics
+// update (the group's statistics entries in `st`).
+template <int C, bool SIG, bool SAMPLE = false>
+__device__ __forceinline__ void head_finish(const HeadArgs& a, size_t v, float (&l)[C], const float (&s)[C], VoxelStats<C>& st,
+                                            const SampleArgs* sa = nullptr)
 {
     if (v >= a.V) return;
     const size_t n = v / a.HW, hw = v % a.HW;
@@ -226,15 +238,15 @@ __device__ __forceinline__ void head_finish(const HeadArgs& a, size_t v, float (
 #pragma unroll
         for (int c = 0; c < C; ++c) a.sigma[(n * C + c) * a.HW + hw] = s[c] + a.b_sig[c];
     }
+    float sg[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) sg[c] = SIG ? sigma_of_raw(s[c] + a.b_sig[c], a.sigma_log) : 0.f;
     if (SIG && a.sigma_sum != nullptr) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float raw = s[c] + a.b_sig[c];
-            a.sigma_sum[(n * C + c) * a.HW + hw] += a.sigma_log ? expf(raw) : fabsf(raw);
-        }
+        for (int c = 0; c < C; ++c) a.sigma_sum[(n * C + c) * a.HW + hw] += sg[c];
     }
     if (a.stats != nullptr) {
-        softmax_inplace<C>(l);
+        head_predictive<C, SAMPLE>(l, sg, sa, 0, n, hw);
         st.add(a.stats_flags, l);
         st.store(a.stats, v, a.V, a.stats_flags);
     }
@@ -243,8 +255,8 @@ __device__ __forceinline__ void head_finish(const HeadArgs& a, size_t v, float (
 // The single-pass form as a STREAM (32 head channels): a wave walks over its groups of 64 voxels (group g, g + waves, ...) and requests
 // the next group's activations -- behind the current group's statistics entries, so that waiting for those does not wait for them:
 // vector memory returns in order -- before it reduces the current group: 8-16 KB in flight per wave the whole time, not in bursts.
-template <int C, bool SIG>
-__global__ __launch_bounds__(PW_THREADS) void head_stream_kernel(const HeadArgs a)
+template <int C, bool SIG, bool SAMPLE>
+__device__ __forceinline__ void head_stream_body(const HeadArgs& a, const SampleArgs* sa)
 {
     const int lane = threadIdx.x & 63;
     const size_t n_waves = (size_t)gridDim.x * (PW_THREADS / 64);
@@ -263,7 +275,7 @@ __global__ __launch_bounds__(PW_THREADS) void head_stream_kernel(const HeadArgs 
             if (a.stats != nullptr && v < a.V) st.load(a.stats, v, a.V, a.stats_flags);
             if (gn < groups) head_load32<SIG>(a, a.act, gn * 64, lane, tb);
             head_reduce<C, SIG, 32>(a, a.act, g * 64, lane, w, ta, l, s);
-            head_finish<C, SIG>(a, v, l, s, st);
+            head_finish<C, SIG, SAMPLE>(a, v, l, s, st, sa);
             if (gn >= groups) return;
             g = gn;
         }
@@ -273,15 +285,28 @@ __global__ __launch_bounds__(PW_THREADS) void head_stream_kernel(const HeadArgs 
             if (a.stats != nullptr && v < a.V) st.load(a.stats, v, a.V, a.stats_flags);
             if (gn < groups) head_load32<SIG>(a, a.act, gn * 64, lane, ta);
             head_reduce<C, SIG, 32>(a, a.act, g * 64, lane, w, tb, l, s);
-            head_finish<C, SIG>(a, v, l, s, st);
+            head_finish<C, SIG, SAMPLE>(a, v, l, s, st, sa);
             if (gn >= groups) return;
             g = gn;
         }
     }
 }
 
-template <int C, bool SIG, int CPH>
-__global__ __launch_bounds__(PW_THREADS) void head_kernel(const HeadArgs a)
+template <int C, bool SIG>
+__global__ __launch_bounds__(PW_THREADS) void head_stream_kernel(const HeadArgs a)
+{
+    head_stream_body<C, SIG, false>(a, nullptr);
+}
+
+// the sampling instantiation (a sigma head, one pass: key sa.keys[0])
+template <int C>
+__global__ __launch_bounds__(PW_THREADS) void head_stream_sample_kernel(const HeadArgs a, const SampleArgs sa)
+{
+    head_stream_body<C, true, true>(a, &sa);
+}
+
+template <int C, bool SIG, int CPH, bool SAMPLE>
+__device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* sa)
 {
     const int lane = threadIdx.x & 63;
     const size_t wave_id = ((size_t)blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
@@ -304,14 +329,14 @@ __global__ __launch_bounds__(PW_THREADS) void head_kernel(const HeadArgs a)
             head_logits<C, SIG, CPH>(a, a.act + (size_t)t * a.V * a.CP, v0, lane, l, s);
 #pragma unroll
             for (int c = 0; c < C; ++c) l[c] += a.b_cls[c];
-            softmax_inplace<C>(l);
+            float sg[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) sg[c] = SIG ? sigma_of_raw(s[c] + a.b_sig[c], a.sigma_log) : 0.f;
+            head_predictive<C, SAMPLE>(l, sg, sa, t, n, hw);
             st.add(a.stats_flags, l);
             if (SIG && a.sigma_sum != nullptr) {
 #pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float raw = s[c] + a.b_sig[c];
-                    ssum[c] += a.sigma_log ? expf(raw) : fabsf(raw);
-                }
+                for (int c = 0; c < C; ++c) ssum[c] += sg[c];
             }
         }
         if (v < a.V) {
@@ -328,7 +353,20 @@ __global__ __launch_bounds__(PW_THREADS) void head_kernel(const HeadArgs a)
     VoxelStats<C> st;
     if (a.stats != nullptr && v < a.V) st.load(a.stats, v, a.V, a.stats_flags);
     head_logits<C, SIG, CPH>(a, a.act, v0, lane, l, s);
-    head_finish<C, SIG>(a, v, l, s, st);
+    head_finish<C, SIG, SAMPLE>(a, v, l, s, st, sa);
+}
+
+template <int C, bool SIG, int CPH>
+__global__ __launch_bounds__(PW_THREADS) void head_kernel(const HeadArgs a)
+{
+    head_body<C, SIG, CPH, false>(a, nullptr);
+}
+
+// the sampling instantiation (a sigma head; pass t of the launch under sa.keys[t])
+template <int C, int CPH>
+__global__ __launch_bounds__(PW_THREADS) void head_sample_kernel(const HeadArgs a, const SampleArgs sa)
+{
+    head_body<C, true, CPH, true>(a, &sa);
 }
 
 #define RCU_DISPATCH_C(Cval, ...)                                    \
@@ -371,6 +409,36 @@ hipError_t launch_head(const HeadArgs& a, hipStream_t stream)
         RCU_DISPATCH_C(a.C, hipLaunchKernelGGL((head_kernel<C_, false, 0>), dim3(grid_for(a.V)), dim3(PW_THREADS), 0, stream, a));
     }
     return hipGetLastError();
+}
+
+hipError_t launch_head_sampled(const HeadArgs& a, const unsigned long long* keys_host, unsigned long long first_sample, int samples,
+                               hipStream_t stream)
+{
+    if (a.stats == nullptr || a.w_sig == nullptr || samples < 1 || samples > LOGIT_MAX_SAMPLES) return hipErrorInvalidValue;
+    const bool c32 = a.CPh == 32 && a.V > 0;
+    const int passes = a.passes < 1 ? 1 : a.passes;
+    // one launch per SAMPLE_MAX_PASSES passes, in pass order: each adds its passes into the statistics and the sigma sum the previous one stored
+    for (int first = 0; first < passes; first += SAMPLE_MAX_PASSES) {
+        HeadArgs b = a;
+        b.act = a.act + (size_t)first * a.V * a.CP;
+        b.passes = passes - first < SAMPLE_MAX_PASSES ? passes - first : SAMPLE_MAX_PASSES;
+        SampleArgs sa{};
+        for (int t = 0; t < b.passes; ++t) sa.keys[t] = keys_host[first + t];
+        sa.first_sample = first_sample;
+        sa.samples = samples;
+        if (c32 && b.passes <= 1) {
+            const unsigned need = grid_for(b.V), cap = 256u * RCU_HEAD_WGS;
+            const unsigned grid = need < cap ? need : cap;
+            RCU_DISPATCH_C(b.C, hipLaunchKernelGGL((head_stream_sample_kernel<C_>), dim3(grid), dim3(PW_THREADS), 0, stream, b, sa));
+        } else if (c32) {
+            RCU_DISPATCH_C(b.C, hipLaunchKernelGGL((head_sample_kernel<C_, 32>), dim3(grid_for(b.V)), dim3(PW_THREADS), 0, stream, b, sa));
+        } else {
+            RCU_DISPATCH_C(b.C, hipLaunchKernelGGL((head_sample_kernel<C_, 0>), dim3(grid_for(b.V)), dim3(PW_THREADS), 0, stream, b, sa));
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------- standalone accumulate
@@ -672,21 +740,6 @@ hipError_t launch_argmax_fg(const float* probs, int C, size_t N, size_t HW, uint
 // e = (first_sample + i) * per_sample + site_off[s] + c: a function of (seed, GLOBAL sample index, site, channel) alone -- the same value whatever
 // the batch the sample arrives in, the group the pass is launched in, the lane and the rank.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t (&out)[4])
-{
-    uint32_t c[4] = {c0, c1, 0u, 0u};
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
-
 __global__ __launch_bounds__(PW_THREADS) void dropout_masks_kernel(const MaskArgs a, float* __restrict__ out)
 {
     const int r = blockIdx.x * PW_THREADS + threadIdx.x;      // element of the pass's own mask [site][n][C_site]
@@ -698,7 +751,7 @@ __global__ __launch_bounds__(PW_THREADS) void dropout_masks_kernel(const MaskArg
     const int ch = a.site_ch[s], i = (r - begin) / ch, c = (r - begin) - i * ch;
     const unsigned long long e = (a.first_sample + (unsigned long long)i) * (unsigned long long)a.per_sample + (unsigned long long)(a.site_off[s] + c);
     uint32_t w[4];
-    philox4x32_10((uint32_t)a.seed[t], (uint32_t)(a.seed[t] >> 32), (uint32_t)(e >> 2), (uint32_t)(e >> 34), w);
+    philox4x32_10((uint32_t)a.seed[t], (uint32_t)(a.seed[t] >> 32), (uint32_t)(e >> 2), (uint32_t)(e >> 34), 0u, 0u, w);   // (rcu_head_common.h)
     const uint32_t word = (e & 3) == 0 ? w[0] : (e & 3) == 1 ? w[1] : (e & 3) == 2 ? w[2] : w[3];
     const float keep = a.site_keep[s];
     const float u = (float)(word >> 8) * (1.0f / 16777216.0f);        // uniform in [0, 1), 24 bits

@@ -442,6 +442,35 @@ class UNet(nn.Module):
                                                                  _lib.current_stream()))
         stats.count += 1
 
+    def forward_sample_sigma(self, x, stats, sigma_sum, keys, first_sample, samples, masks=None, is_log_sigma=False, lane=0):
+        """EXTENSION (test-time logit sampling, include/rcu.h): ``forward_accumulate_sigma`` with the sampled predictive
+        (1/S) sum_s softmax(mu + sigma * z_s) in place of softmax(mu).  One pass per key of ``keys`` (pass t's noise under keys[t]; more than
+        one key: a pass group, ``masks`` as there); image i of the batch is slice ``first_sample + i``; ``samples`` = S in 1..1024."""
+        if not self.sigma_out:
+            raise ValueError('forward_sample_sigma needs a model built with sigma_out=True')
+        x = self._check_input(x)
+        n, _, h, w = x.shape
+        passes = len(keys)
+        if passes < 1:
+            raise ValueError('forward_sample_sigma needs one key per pass')
+        if (n, self.nb_classes, h * w) != (stats.n, stats.nb_classes, stats.hw):
+            raise ValueError('statistics blob shape does not match the batch')
+        if (tuple(sigma_sum.shape) != (n, self.nb_classes, h, w) or sigma_sum.dtype != torch.float32 or
+                not sigma_sum.is_contiguous() or sigma_sum.device != x.device):
+            raise ValueError('sigma_sum must be a contiguous float32 [N, C, H, W] tensor on the input device')
+        handle = self._handle(h, w, n * passes, lane)
+        if masks is None:
+            if passes > 1 and not self.mc_active():
+                raise ValueError('a pass group needs stochastic passes: set_dropout_mode(model, True) or inject masks')
+            masks = self.sample_masks(n * passes, x.device) if self.mc_active() else None
+        elif isinstance(masks, (list, tuple)):
+            masks = self.group_masks(masks, n, x.device) if passes > 1 else self.pack_masks(masks, n, x.device)
+        key_arr = (ctypes.c_uint64 * passes)(*[int(k) for k in keys])
+        _lib.check(_lib.load().rcu_unet_forward_sample_sigma_passes(handle, _lib.ptr(x), n, passes, _lib.ptr(masks), key_arr, int(first_sample),
+                                                                    int(samples), _lib.ptr(stats.blob), stats.flags, _lib.ptr(sigma_sum),
+                                                                    int(bool(is_log_sigma)), _lib.current_stream()))
+        stats.count += passes
+
     def group_masks(self, mask_sets, n, device):
         """``passes`` mask sets (each [site][n][C_site]) -> the [site][passes * n][C_site] layout of a pass group."""
         sites = self.dropout_sites()

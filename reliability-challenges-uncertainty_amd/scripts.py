@@ -19,6 +19,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from . import calibration
 from . import data as data_mod
 from . import distributed as rdist
@@ -380,6 +381,41 @@ def _refuse_tta(context, script):
         raise ValueError('others.tta (test-time augmentation) applies to the default test scripts only; the {} script does not take it'.format(script))
 
 
+def _refuse_logit_samples(context, script):
+    if hasattr(context.config.others, 'logit_samples'):
+        raise ValueError('others.logit_samples (test-time logit sampling) applies to the aleatoric test scripts only; the {} script does not take it'
+                         .format(script))
+
+
+def _logit_samples(context):
+    """``others.logit_samples`` (an rcu_amd extension): S in 1..RCU_LOGIT_MAX_SAMPLES, or None when the key is absent."""
+    if not hasattr(context.config.others, 'logit_samples'):
+        return None
+    value = context.config.others.logit_samples
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= _lib.RCU_LOGIT_MAX_SAMPLES:
+        raise ValueError('others.logit_samples must be an integer in 1..{}, got {!r}'.format(_lib.RCU_LOGIT_MAX_SAMPLES, value))
+    return value
+
+
+def _aleatoric_steps(context, world):
+    """The batch steps of the aleatoric script.  ``others.is_log_sigma`` (default false, as the shipped configs: sigma = |raw|; true: exp(raw),
+    bin-dl/brats_test_aleatoric.py:34-37).  ``others.logit_samples: S`` (an rcu_amd extension, include/rcu.h "Test-time logit sampling"): the
+    written probabilities are the sampled predictive (1/S) sum_s softmax(mu + sigma * z_s) of one eval-mode pass (AleatoricPredictStep) or,
+    with ``others.mc: T``, of each of T seeded MC-dropout passes, averaged (AleatoricMcPredictStep + MultiPredictionSummary); the noise and the
+    masks are keyed by the YAML file's ``seed``.  Without ``logit_samples`` ``others.mc`` is not read here, as before.  A multi-rank run is rank
+    0's alone (one process runs the whole batch: nothing is sharded)."""
+    others = context.config.others
+    is_log_sigma = bool(getattr(others, 'is_log_sigma', False))
+    samples = _logit_samples(context)
+    if samples is None:
+        return [steps.AleatoricPredictStep(is_log_sigma)]
+    seed = context.config.seed
+    mc = int(getattr(others, 'mc', 0) or 0)
+    if mc > 0:
+        return [steps.AleatoricMcPredictStep(mc, is_log_sigma, logit_samples=samples, seed=seed), steps.MultiPredictionSummary()]
+    return [steps.AleatoricPredictStep(is_log_sigma, samples, seed)]
+
+
 def _refuse_temperature(context, script):
     if hasattr(context.config.others, 'temperature'):
         raise ValueError('others.temperature (temperature scaling) applies to the default test scripts only; the {} script does not take it'
@@ -549,6 +585,7 @@ def _abandon_process_group(timeout_s=10.0):
 
 def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
+    _refuse_logit_samples(context, 'default')
     entries = ('probabilities',) if dataset == 'brats' else None
     return _run(context, dataset, _default_steps(context, world), WriteHook(link_inputs=dataset == 'isic'), entries, world,
                 startup_hooks=_temperature_hooks(context))
@@ -558,6 +595,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_ensemble.yaml'.format(dataset)))
     _refuse_tta(context, 'ensemble')
     _refuse_temperature(context, 'ensemble')
+    _refuse_logit_samples(context, 'ensemble')
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
     if world.world > 1:     # the K members of every batch sharded over the ranks (bin-dl/brats_test_ensemble.py:44-59 on N GPUs)
@@ -571,7 +609,7 @@ def test_aleatoric(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_aleatoric.yaml'.format(dataset)))
     _refuse_tta(context, 'aleatoric')
     _refuse_temperature(context, 'aleatoric')
-    return _run(context, dataset, [steps.AleatoricPredictStep()], WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
+    return _run(context, dataset, _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world)
 
 
@@ -713,6 +751,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_feat.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_feat')
     _refuse_temperature(context, 'auxiliary_feat')
+    _refuse_logit_samples(context, 'auxiliary_feat')
     if not _single_rank_only(world):
         return context
     test_model = _load_segmentation_model(context)
@@ -735,6 +774,7 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_segm.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_segm')
     _refuse_temperature(context, 'auxiliary_segm')
+    _refuse_logit_samples(context, 'auxiliary_segm')
     if not _single_rank_only(world):
         return context
     if dataset == 'brats':
@@ -796,6 +836,7 @@ def fit_temperature(dataset, config_file, device='cuda'):
     if hasattr(others, 'tta'):
         raise ValueError('others.tta: the temperature fit does not run under test-time augmentation')
     _refuse_temperature(context, 'fit_temperature')
+    _refuse_logit_samples(context, 'fit_temperature')
     mc = int(getattr(others, 'mc', 0) or 0)
     seed = 0 if context.config.seed is None else int(context.config.seed)
     context.load_from_checkpoint(context.get_test_at())

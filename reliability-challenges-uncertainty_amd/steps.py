@@ -8,6 +8,7 @@ Mirrors (names, arguments, output keys, error behaviour):
   EnsemblePredictionStep        bin-dl/brats_test_ensemble.py:72-94
   AleatoricPredictStep          bin-dl/brats_test_aleatoric.py:51-73
   AleatoricMcPredictStep        extension (BASELINE config 'aleatoric + MC'): composition of the two above
+  (both with logit_samples = S)  extension: test-time logit sampling, the predictive E_eps[softmax(mu + sigma eps)] (include/rcu.h)
   TtaMcPredictStep              extension: test-time augmentation (D4 transforms), alone or composed with MC dropout
   BatchContext / TaskContext    common/trainloop/context.py:334-355
 A step is called as ``step(batch_context, task_context, context)``, reads
@@ -22,6 +23,7 @@ sums, updated by the fused forward+softmax+accumulate kernel) under ``multi_prob
 """
 import abc
 import logging
+import operator
 
 import torch
 
@@ -381,7 +383,10 @@ def run_plan(plan, engine, x, stats, ws=None, lanes=1, draw=None, reserve=None, 
                 st = scratch[lane]
             if draw is None:
                 engine.member_pass(engine.model, xs[e], st, **kw)
-            elif len(jobs) == 1:
+                return
+            if getattr(engine, 'takes_jobs', False):      # an engine that keys its passes by the pass number (AleatoricHipEngine sampling)
+                kw['jobs'] = jobs
+            if len(jobs) == 1:
                 engine.mc_pass(xs[e], st, draw(e, jobs), **kw)
             else:
                 engine.mc_pass(xs[e], st, draw(e, jobs), passes=len(jobs), **kw)
@@ -485,13 +490,23 @@ class AleatoricHipEngine(HipEngine):
     """EXTENSION (BASELINE config "aleatoric + MC", see AleatoricMcPredictStep): passes of a sigma-head U-Net; statistics carry a float32
     ``sigma_sum`` [n, C, H, W] next to the blob.  ``exact`` applies to the probability statistics only (the sigmas are unbounded addends:
     no exact form).  The sharded runner's reduce buffer is float32 throughout, one dtype per collective:
-    flat = [statistics | sigma sum | ws probabilities | ws sigma]."""
+    flat = [statistics | sigma sum | ws probabilities | ws sigma].
+    ``logit_samples`` = S > 0 (test-time logit sampling): every pass adds the sampled predictive of its (mu, sigma) in place of softmax(mu),
+    pass j under the key ``pass_seed(seed, j)`` (the weight-scaling pass: j = 0), image i of the batch being slice ``first_sample + i``; the
+    engine then ``takes_jobs``: run_plan tells ``mc_pass`` the pass numbers of each launch."""
 
-    def __init__(self, model, is_log_sigma=False, do_mi=False, do_var=False, exact=False):
+    def __init__(self, model, is_log_sigma=False, do_mi=False, do_var=False, exact=False, logit_samples=0, seed=0, first_sample=0):
         super().__init__(model, do_mi, do_var, exact)
         if not getattr(model, 'sigma_out', False):
             raise ValueError('AleatoricHipEngine needs a model built with sigma_out=True')
         self.is_log_sigma = is_log_sigma
+        self.logit_samples = check_logit_samples(logit_samples)
+        self.seed = 0 if seed is None else int(seed)
+        self.first_sample = int(first_sample)
+
+    @property
+    def takes_jobs(self):
+        return self.logit_samples > 0
 
     def buffers(self, x, with_ws):
         if self.exact or self.do_var:
@@ -512,13 +527,22 @@ class AleatoricHipEngine(HipEngine):
         set_dropout_mode(self.model, False)
         logits, raw = self.model(x)
         n, c, h, w = logits.shape
+        sampled = self.logit_samples > 0
         _lib.check(_lib.load().rcu_aleatoric(_lib.ptr(logits), _lib.ptr(raw.contiguous()), n, h * w, c, int(self.is_log_sigma),
-                                             _lib.ptr(ws_out[0]), _lib.ptr(ws_out[1]), None, None, _lib.current_stream()))
+                                             None if sampled else _lib.ptr(ws_out[0]), _lib.ptr(ws_out[1]), None, None, _lib.current_stream()))
+        if sampled:
+            sample_logits(logits, raw, self.logit_samples, pass_seed(self.seed, 0), self.first_sample, self.is_log_sigma, out=ws_out[0])
 
-    def mc_pass(self, x, stats, masks=None, passes=1, lane=0):
+    def mc_pass(self, x, stats, masks=None, passes=1, lane=0, jobs=None):
         set_dropout_mode(self.model, True)
         try:
-            self.model.forward_accumulate_sigma(x, stats, stats.sigma_sum, masks, self.is_log_sigma, lane=lane, passes=passes)
+            if self.logit_samples > 0:
+                if jobs is None or len(jobs) != passes:
+                    raise ValueError('a sampling pass needs the pass numbers of its launch (jobs)')
+                self.model.forward_sample_sigma(x, stats, stats.sigma_sum, [pass_seed(self.seed, j) for j in jobs], self.first_sample,
+                                                self.logit_samples, masks, self.is_log_sigma, lane=lane)
+            else:
+                self.model.forward_accumulate_sigma(x, stats, stats.sigma_sum, masks, self.is_log_sigma, lane=lane, passes=passes)
         finally:
             set_dropout_mode(self.model, False)
 
@@ -534,6 +558,35 @@ class AleatoricHipEngine(HipEngine):
 
     def ws_outputs(self, ws):
         return {'ws_probabilities': ws[0], 'ws_sigma': ws[1]}
+
+
+def check_logit_samples(samples):
+    """``logit_samples`` of the aleatoric steps: an int in 0..RCU_LOGIT_MAX_SAMPLES (0: softmax(mu), no sampling); ValueError otherwise."""
+    try:
+        value = None if isinstance(samples, bool) else operator.index(samples)
+    except TypeError:
+        value = None
+    if value is None or not 0 <= value <= _lib.RCU_LOGIT_MAX_SAMPLES:
+        raise ValueError('logit_samples must be an integer in 0..{} (0: no sampling), got {!r}'.format(_lib.RCU_LOGIT_MAX_SAMPLES, samples))
+    return value
+
+
+def sample_logits(logits, sigma_raw, samples, key, first_sample, is_log_sigma=False, out=None):
+    """Test-time logit sampling on the HIP path (include/rcu.h rcu_logit_sampling): p_bar = (1/S) sum_s softmax(mu + sigma * z_s) of the
+    ``[N, C, H, W]`` logits and raw sigma of a sigma head (sigma = |raw|, or exp(raw) with ``is_log_sigma``), the noise of image i keyed by
+    ``key`` and the slice index ``first_sample + i``.  ``out``: a contiguous float32 tensor of the logits' shape to write into."""
+    logits = logits.to(torch.float32).contiguous()
+    sigma_raw = sigma_raw.to(torch.float32).contiguous()
+    if logits.dim() != 4 or sigma_raw.shape != logits.shape or sigma_raw.device != logits.device:
+        raise ValueError('logits and sigma_raw must be [N, C, H, W] tensors of one shape on one device')
+    n, c, h, w = logits.shape
+    if out is None:
+        out = torch.empty_like(logits)
+    elif out.shape != logits.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != logits.device:
+        raise ValueError('out must be a contiguous float32 tensor of the shape and device of the logits')
+    _lib.check(_lib.load().rcu_logit_sampling(_lib.ptr(logits), _lib.ptr(sigma_raw), n, h * w, c, int(bool(is_log_sigma)), int(samples), int(key),
+                                              int(first_sample), _lib.ptr(out), None, 0, _lib.current_stream()))
+    return out
 
 
 def softmax(logits, out=None):
@@ -816,10 +869,17 @@ class MultiPredictionSummary(BatchStep):
 
 
 class AleatoricPredictStep(BatchStep):
+    """bin-dl/brats_test_aleatoric.py:51-73: ``logits``, ``sigma`` (|raw| or exp(raw)) and ``probabilities`` = softmax(logits) of one
+    eval-mode pass of a sigma-head model.  EXTENSION ``logit_samples`` = S > 0 (test-time logit sampling, include/rcu.h): ``probabilities`` is the
+    predictive the model was trained for (AleatoricLoss, Kendall & Gal 2017), p_bar = (1/S) sum_s softmax(mu + sigma * z_s), the noise of slice g
+    keyed by ``pass_seed(seed, 0)`` and g (the batch's ``first_sample_of`` + position) -- the same bits for any batching.  ``logits`` and
+    ``sigma`` do not change."""
 
-    def __init__(self, is_log_sigma=False) -> None:
+    def __init__(self, is_log_sigma=False, logit_samples=0, seed=0) -> None:
         super().__init__()
         self.is_log_sigma = is_log_sigma
+        self.logit_samples = check_logit_samples(logit_samples)
+        self.seed = 0 if seed is None else int(seed)
 
     def __call__(self, batch_context, task_context, context) -> None:
         _check_context(context)
@@ -829,9 +889,13 @@ class AleatoricPredictStep(BatchStep):
         n, c, h, w = mean_logits.shape
         probs = torch.empty_like(mean_logits)
         sigma = torch.empty_like(mean_logits)
+        sampled = self.logit_samples > 0
         _lib.check(_lib.load().rcu_aleatoric(_lib.ptr(mean_logits), _lib.ptr(sigma_raw.contiguous()), n, h * w, c,
-                                             int(self.is_log_sigma), _lib.ptr(probs), _lib.ptr(sigma), None, None,
+                                             int(self.is_log_sigma), None if sampled else _lib.ptr(probs), _lib.ptr(sigma), None, None,
                                              _lib.current_stream()))
+        if sampled:
+            sample_logits(mean_logits, sigma_raw, self.logit_samples, pass_seed(self.seed, 0), first_sample_of(batch_context, n),
+                          self.is_log_sigma, out=probs)
         batch_context.output['sigma'] = sigma
         batch_context.output['probabilities'] = probs
 
@@ -842,11 +906,21 @@ class AleatoricMcPredictStep(BatchStep):
     pieces: per pass t, with dropout on, ``logits_t, raw_t = model(x)``; ``p_t = softmax(logits_t)`` goes into the MC statistics
     (-> ``multi_probabilities`` for MultiPredictionSummary, as McPredictStep); ``sigma_t = |raw_t|`` or ``exp(raw_t)``
     (AleatoricPredictStep, brats_test_aleatoric.py:66-69) is averaged over the passes -> ``sigma`` [N, C, H, W].  The
-    deterministic pass that McPredictStep runs first gives ``ws_probabilities`` and ``ws_sigma``."""
+    deterministic pass that McPredictStep runs first gives ``ws_probabilities`` and ``ws_sigma``.
+    ``seed``: the Dropout2d masks are drawn as McPredictStep draws them under its ``seed`` (pass j: ``pass_seed(seed, j)`` at the slices' global
+    indices); None: from the device generator (or ``masks``, injected).
+    EXTENSION ``logit_samples`` = S > 0 (test-time logit sampling, include/rcu.h): pass j adds its sampled predictive
+    p_bar_j = (1/S) sum_s softmax(mu_j + sigma_j * z_s) where it would add softmax(mu_j), the noise keyed by ``pass_seed(seed or 0, j)`` and the
+    slice (the weight-scaling pass: j = 0, as AleatoricPredictStep) -- in the head kernel of the fused forward, mu and sigma never reach HBM.
+    MultiPredictionSummary then splits the total uncertainty: ``probabilities`` = mean_j p_bar_j, ``entropy`` = H(mean) the total,
+    ``mutual_info`` the epistemic part (the dropout's), ``entropy - mutual_info`` = mean_j H(p_bar_j) the aleatoric part."""
 
-    def __init__(self, mc_steps, is_log_sigma=False, do_mi=False, do_var=False, masks=None, ws_pass=True, lanes=None, exact=True) -> None:
+    def __init__(self, mc_steps, is_log_sigma=False, do_mi=False, do_var=False, masks=None, ws_pass=True, lanes=None, exact=True,
+                 logit_samples=0, seed=None) -> None:
         super().__init__()
         self.mc_steps = mc_steps
+        self.logit_samples = check_logit_samples(logit_samples)
+        self.seed = seed
         self.is_log_sigma = is_log_sigma
         self.do_mi, self.do_var = do_mi, do_var
         self.masks = masks
@@ -861,7 +935,8 @@ class AleatoricMcPredictStep(BatchStep):
         if not isinstance(model, model_mod.UNet) or not model.sigma_out:
             raise ValueError('AleatoricMcPredictStep needs a rcu_amd.model.UNet built with sigma_out=True')
         n, _, h, w = images.shape
-        engine = AleatoricHipEngine(model, self.is_log_sigma, self.do_mi, self.do_var, self.exact)
+        first_sample = first_sample_of(batch_context, n)
+        engine = AleatoricHipEngine(model, self.is_log_sigma, self.do_mi, self.do_var, self.exact, self.logit_samples, self.seed, first_sample)
         ws = torch.empty((2, n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
         stats = engine.side_statistics(images)
         # pass groups and stream lanes as in McPredictStep: g passes per launch, launches alternating over two HIP streams
@@ -870,7 +945,7 @@ class AleatoricMcPredictStep(BatchStep):
         plan = launch_plan(([0] if ws is not None else []) + list(range(1, self.mc_steps + 1)), (0,), max(self.mc_steps, 1), group, lanes)
         try:
             run_plan(plan, engine, images, stats, ws, lanes, reserve=(self.mc_steps, group),
-                     draw=lambda e, jobs: launch_masks(engine, images, e, jobs, max(self.mc_steps, 1), mask_sets=self.masks))
+                     draw=lambda e, jobs: launch_masks(engine, images, e, jobs, max(self.mc_steps, 1), self.seed, first_sample, self.masks))
         finally:
             set_dropout_mode(model, is_train=False)
         if ws is not None:
