@@ -340,6 +340,38 @@ int rcu_unc_counts_from_p(const float* p_foreground_dev, const uint8_t* predicti
 int rcu_normalised_entropy(const float* p_foreground_dev, size_t n, double* out_f64_dev, float* out_f32_dev,
                            void* stream);
 
+/* EXTENSION (the reference thresholds the uncertainty at 11 hand-picked values; rcu_amd.evaluation.uncertainty_histogram, ue_curve_metrics):
+ * the joint histogram of (uncertainty level, confusion cell) of n_volumes volumes of n_per_volume voxels each (volume v at offset
+ * v * n_per_volume in every array, which need not be a multiple of 4), from which the threshold-free uncertainty-error metrics (AUROC / AUPRC
+ * of error detection, risk-coverage area, the uncertainty-error Dice at its best threshold) are host arithmetic on integers.
+ *   levels B        2 <= B <= RCU_UNC_HIST_MAX_LEVELS
+ *   boundaries      t_k = (double)k / (double)B, k = 1 .. B-1: one correctly rounded float64 division each (for B = 1000 the doubles of the
+ *                   script's literals 0.05, 0.1, ... 0.95: k / 1000 equals the decimal exactly, and both are rounded once)
+ *   level(u)        #{k : u > t_k}, compared in float64 exactly as rcu_unc_counts compares: u <= t_1, negative u and NaN -> 0; u exactly t_k -> k-1;
+ *                   u > t_{B-1} (also u > 1) -> B-1
+ *   cells           tp = 0, tn = 1, fp = 2, fn = 3 (prediction != 0, target != 0); voxels with mask == 0 are skipped (mask_dev NULL = all voxels)
+ *   hist_dev        [n_volumes][4][B] uint64, written (not added to)
+ * Hence, for every k in 1..B-1, sum_{l >= k} hist[v][c][l] is the "uncertain" count and sum_l hist[v][c][l] the base count that rcu_unc_counts
+ * returns for thr = t_k.  Integer sums: the histogram does not depend on the launch geometry, and histograms of disjoint voxel sets add.
+ * rcu_unc_hist takes the prepared uncertainty map (float64 with unc_is_f64 = 1, what ToEntropy yields, or float32), like rcu_unc_counts.
+ * rcu_unc_hist_from_p takes the float32 foreground-probability map and computes the normalised entropy in registers with the arithmetic of
+ * rcu_normalised_entropy (one device function, csrc/rcu_entropy.h): rcu_unc_hist_from_p(p) == rcu_unc_hist(rcu_normalised_entropy(p)) integer
+ * for integer, and the 8-byte-per-voxel map is never made (6 bytes read per voxel instead of 4 read + 8 written + 10 read).  It is NOT
+ * table-based like rcu_unc_counts_from_p: right at a level boundary the device's logf may place one of the one to three float32 values there
+ * differently from a host's numpy -- the caveat stated above for the map-based path.
+ * Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it): levels outside
+ * 2..RCU_UNC_HIST_MAX_LEVELS, a null pointer (mask_dev may be NULL), n_per_volume == 0, n_volumes outside 1..65535.
+ * workspace_dev: rcu_unc_hist_workspace_bytes(...) bytes (the boundary table; 0 for levels out of range). */
+#define RCU_UNC_HIST_MAX_LEVELS 4096
+size_t rcu_unc_hist_workspace_bytes(size_t n_per_volume, int n_volumes, int levels);
+int rcu_unc_hist(const void* unc_dev, int unc_is_f64, const uint8_t* prediction_dev, const uint8_t* target_dev, const uint8_t* mask_dev,
+                 size_t n_per_volume, int n_volumes, int levels, uint64_t* hist_dev, void* workspace_dev, void* stream);
+int rcu_unc_hist_from_p(const float* p_foreground_dev, const uint8_t* prediction_dev, const uint8_t* target_dev, const uint8_t* mask_dev,
+                        size_t n_per_volume, int n_volumes, int levels, uint64_t* hist_dev, void* workspace_dev, void* stream);
+/* Test / tuning aid (as rcu_calib_set_blocks_per_workgroup): consecutive blocks (16,384 voxels; 65,536 for levels > 1365) a workgroup of the level
+ * histogram takes, at most 64; 0 = the launcher's choice (default).  Integer sums: every value gives the same histogram.  Process-wide. */
+int rcu_unc_hist_set_blocks_per_workgroup(int blocks);
+
 /* ------------------------------------------------------------------------------------------
  * Test-time augmentation (EXTENSION: the reference has no TTA; rcu_amd.steps.TtaMcPredictStep)
  *   The network runs on transformed copies g(x) of every slice, the statistics of those passes are mapped back with g^-1 and added to

@@ -19,6 +19,7 @@ RCU_MC_EXACT = 8
 RCU_MC_EXACT_MAX_PASSES = 2048
 RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
+RCU_UNC_HIST_MAX_LEVELS = 4096
 # test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
 # temperature scaling (include/rcu.h): candidates per rcu_temperature_nll call
 RCU_TEMPERATURE_MAX_CANDIDATES = 128
@@ -117,6 +118,10 @@ SIGNATURES = {
     'rcu_unc_from_p_workspace_bytes': (c_size_t, [c_size_t, c_int]),
     'rcu_unc_counts_from_p': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
                                       c_void_p]),
+    'rcu_unc_hist_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int]),
+    'rcu_unc_hist': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_unc_hist_from_p': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_unc_hist_set_blocks_per_workgroup': (c_int, [c_int]),
     'rcu_tta_transform': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_mc_fold_transformed': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rcu_unet_set_temperature': (c_int, [c_void_p, c_double]),

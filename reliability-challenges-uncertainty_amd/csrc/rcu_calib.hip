@@ -18,6 +18,7 @@
 // Bin indices are bit-exact with np.digitize: p is compared against the float32 thresholds
 // t_k = min{float32 t : t >= edge_k}.
 #include "rcu_kernels.h"
+#include "rcu_entropy.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -854,11 +855,7 @@ __global__ __launch_bounds__(CB_THREADS) void norm_entropy_kernel(const float* _
 {
     const size_t i = (size_t)blockIdx.x * CB_THREADS + threadIdx.x;
     if (i >= n) return;
-    const float f = p[i];
-    const float b = 1.0f - f;
-    const double tf = (f > 0.f) ? (double)(f * logf(f)) : 0.0;
-    const double tb = (b > 0.f) ? (double)(b * logf(b)) : 0.0;
-    const double h = -(tb + tf) / 0.6931471805599453;
+    const double h = normalised_entropy_of_p(p[i]);      // rcu_entropy.h: the arithmetic rcu_unc_hist_from_p shares
     if (out64) out64[i] = h;
     if (out32) out32[i] = (float)h;
 }

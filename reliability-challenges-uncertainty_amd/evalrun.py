@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue)
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves is an extension
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -31,6 +31,10 @@ CALIBRATION_PLACEHOLDER = 'eval_calibration_{}.csv'
 UNCERTAINTY_PLACEHOLDER = 'eval_uncertainty_{}_th{}.csv'
 ECE_PLACEHOLDER = 'eval_ece_{}.csv'
 MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
+# rcu_amd extension (the 'ue_curves' action), next to the per-threshold files in UNCERTAINTY_NAME
+UE_CURVES_PLACEHOLDER = 'eval_ue_curves_{}.csv'
+UE_CURVES_POOLED_PLACEHOLDER = 'eval_ue_curves_pooled_{}.csv'
+UE_LEVELS_PLACEHOLDER = 'eval_ue_levels_{}.csv'
 
 CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities', 'center': 'probabilities',
                     'center_mc': 'probabilities', 'ensemble': 'probabilities', 'auxiliary_feat': 'confidence',
@@ -417,11 +421,67 @@ class CorrectionAction(EvalAction):
             case.record(results[thr], sf.subject, self.id_)
 
 
+class UeCurvesAction(EvalAction):
+    """EXTENSION (the reference has no such action): threshold-free uncertainty-error metrics from one level histogram per subject
+    (evaluation.uncertainty_histogram / ue_curve_metrics), prepared exactly like ``CorrectionAction`` and, like it, without a brain mask.
+    Files in ``<base_dir>/uncertainty``:
+      eval_ue_curves_<id>.csv          one row per subject: n, n_errors, auroc, auprc, aurc, eaurc, ue_dice_max, ue_dice_max_threshold
+      eval_ue_curves_pooled_<id>.csv   the same metrics of the SUM of the subjects' histograms (integers: whatever the batching or order)
+      eval_ue_levels_<id>.csv          that pooled histogram, one row per level: level, threshold, tp, tn, fp, fn -- ``threshold`` = level /
+                                       levels, the boundary below the level; the rows from level k on add up to the voxels with
+                                       uncertainty > k / levels, so risk-coverage and uncertainty-error Dice curves need no second run"""
+
+    def __init__(self, levels, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        super().__init__()
+        self.levels = int(levels)
+        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
+            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
+        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.pooled = None
+
+    def setup_eval(self, eval_data):
+        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
+        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
+        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
+                                                                self.rescale_confidence, self.rescale_sigma, mm)
+        self.load_params = Loader.Params(eval_data.confidence_entry)
+        hook = WriteCsvHook(os.path.join(self.out_dir, UE_CURVES_PLACEHOLDER.format(self.id_)), entries=ev.UE_CURVE_KEYS)
+        self.eval_cases = [EvalCase(None, hook)]
+        self.pooled = np.zeros((4, self.levels), dtype=np.uint64)
+
+    def record_histogram(self, hist, subject_name):
+        """One subject's level histogram ``[4, levels]``: its metrics row, and its share of the pooled histogram."""
+        self.eval_cases[0].record(ev.ue_curve_metrics(hist), subject_name, self.id_)
+        self.pooled += np.asarray(hist, dtype=np.uint64)
+
+    def eval_subject(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        if self.prepare:
+            to_eval = self.prepare(to_eval)
+        self.record_histogram(ev.uncertainty_histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], self.levels)[0],
+                              sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        pooled = ev.ue_curve_metrics(self.pooled)
+        with open(os.path.join(self.out_dir, UE_CURVES_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id'] + list(ev.UE_CURVE_KEYS))
+            writer.writerow([self.id_] + [pooled[k] for k in ev.UE_CURVE_KEYS])
+        with open(os.path.join(self.out_dir, UE_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['level', 'threshold', 'tp', 'tn', 'fp', 'fn'])
+            for level in range(self.levels):
+                writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]])
+
+
 ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
-def get_actions(action_names, min_max_dir, base_dir, ece_details):
-    """bin-eval/eval_uncertainty.py:226-244."""
+def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS):
+    """bin-eval/eval_uncertainty.py:226-244, plus the extension 'ue_curves' (``levels``: its number of uncertainty levels)."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -432,6 +492,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details):
             actions.append(EceCalibrationAction(base_dir, ece_details, 'subject', 'global', min_max_dir))
         elif name == 'bnf_ue':
             actions.append(CorrectionAction(ev.UE_THRESHOLDS, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'ue_curves':
+            actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
     return actions
 
 
@@ -517,19 +579,20 @@ class _LoaderAhead:
 
 def _fusable(entry, actions):
     """The fused loop covers the runs whose confidence entry IS the probability map (baseline, baseline_mc, center, center_mc, ensemble:
-    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion -- and the four actions of the script."""
+    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script and 'ue_curves'."""
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
-            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction) for a in actions) and
+            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction) for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
 
 def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
-    list of actions on a probability-map run."""
+    list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
-           (['ue'] if (CorrectionAction in by_type or (ECE_TYPES & set(by_type))) else [])
+           (['ue'] if (CorrectionAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
+           (['ue_hist'] if UeCurvesAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -565,6 +628,8 @@ def record_subject(actions, subject, res, slot, n_dim):
         elif isinstance(action, CorrectionAction):
             for t, case in enumerate(action.eval_cases):
                 case.record(ev.correction_results(counts[t]), subject, action.id_)
+        elif isinstance(action, UeCurvesAction):
+            action.record_histogram(res['ue_hist'][slot], subject)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -574,6 +639,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     fn are ece_dice's confusion matrix), min / max -- and the results fanned out to the actions' CSV hooks in subject order.  The rows are
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
     want, thresholds, want_mask = metrics_wanted(actions)
+    levels = next((a.levels for a in actions if isinstance(a, UeCurvesAction)), ev.UE_LEVELS)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
     files = entry.subject_files
     reader = _ReadAhead(files, params, depth=2 * batch_subjects)
@@ -600,7 +666,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want)
+            res = batch.metrics(thresholds=thresholds, want=want, levels=levels)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)
@@ -629,13 +695,13 @@ class _Done:
         return self.value
 
 
-def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None):
+def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
-    ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py)."""
-    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details)
+    ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' action."""
+    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

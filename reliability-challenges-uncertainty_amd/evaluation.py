@@ -186,11 +186,12 @@ class SubjectBatch:
                     dev[s_].copy_(host[s_], non_blocking=True)
         self._staged = set()
 
-    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue')):
+    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000):
         """-> dict of host arrays over the ``used`` subjects: ``min`` / ``max`` (float32), ``hist`` = (count, sum_conf, sum_pos) of the
         reliability histogram inside the mask, ``counts`` [used, len(thresholds), 8] of the uncertainty-error action on the WHOLE volume
-        (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice).  One launch per
-        scan for all subjects, one synchronisation for all results."""
+        (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice) and, with
+        ``'ue_hist'`` in ``want``, ``ue_hist`` uint64 [used, 4, levels]: the level histogram of ``uncertainty_histogram_from_p``, on the whole
+        volume like the counts.  One launch per scan for all subjects, one synchronisation for all results."""
         v = self.used
         lib = _lib.load()
         out, keep = {}, []
@@ -210,6 +211,12 @@ class SubjectBatch:
             _lib.check(lib.rcu_unc_counts_from_p(_lib.ptr(self.p), _lib.ptr(self.prediction), _lib.ptr(self.target), None, self.n, v, thr,
                                                  len(thresholds), _lib.ptr(counts), _lib.ptr(ws2), _lib.current_stream()))
             keep.append(('ue', counts))
+        if 'ue_hist' in want:
+            ue_hist = torch.empty((v, 4, int(levels)), device=self.device, dtype=torch.int64)
+            ws3 = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(self.n, v, int(levels)), 8), device=self.device, dtype=torch.uint8)
+            _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(self.p), _lib.ptr(self.prediction), _lib.ptr(self.target), None, self.n, v, int(levels),
+                                               _lib.ptr(ue_hist), _lib.ptr(ws3), _lib.current_stream()))
+            keep.append(('ue_hist', ue_hist))
         host = {k: t.cpu() for k, t in keep}          # (the first .cpu() waits for the stream: the others are ready by then)
         if 'minmax' in host:
             mm = host['minmax'].numpy()
@@ -219,6 +226,8 @@ class SubjectBatch:
             out['hist'] = (raw[:, 0, :n_bins].astype(np.int64), raw[:, 1, :n_bins].copy().view(np.float64), raw[:, 2, :n_bins].astype(np.int64))
         if 'ue' in host:
             out['counts'] = host['ue'].numpy()
+        if 'ue_hist' in host:
+            out['ue_hist'] = host['ue_hist'].numpy().view(np.uint64)
         return out
 
 
@@ -306,6 +315,107 @@ class EntropyOfProbability:
 
     def max(self):
         return self.materialise().max()
+
+
+# ------------------------------------------------ threshold-free uncertainty-error metrics from a level histogram (EXTENSION)
+UE_LEVELS = 1000        # default number of levels: every threshold of UE_THRESHOLDS is then a level boundary k / 1000
+UE_CURVE_KEYS = ('n', 'n_errors', 'auroc', 'auprc', 'aurc', 'eaurc', 'ue_dice_max', 'ue_dice_max_threshold')
+
+
+def _histogram_on_device(fn_name, source, source_dtype, extra, prediction, target, levels, mask, n_volumes):
+    u = _to_dev(source, source_dtype).reshape(n_volumes, -1)
+    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
+    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
+    m = None if mask is None else _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    n, levels = u.shape[1], int(levels)
+    lib = _lib.load()
+    out = torch.empty((n_volumes, 4, max(levels, 1)), device=u.device, dtype=torch.int64)
+    ws = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(n, n_volumes, levels), 8), device=u.device, dtype=torch.uint8)
+    _lib.check(getattr(lib, fn_name)(_lib.ptr(u), *extra, _lib.ptr(pr), _lib.ptr(tg), _lib.ptr(m), n, n_volumes, levels, _lib.ptr(out),
+                                     _lib.ptr(ws), _lib.current_stream()))
+    return out.cpu().numpy().view(np.uint64)
+
+
+def uncertainty_histogram(prediction, target, uncertainty, levels=UE_LEVELS, mask=None, n_volumes=1):
+    """uint64 ``[n_volumes, 4, levels]``: per volume the joint histogram of (confusion cell tp, tn, fp, fn; uncertainty level), with
+    level(u) = #{k in 1..levels-1 : u > k / levels} compared in float64 (include/rcu.h, rcu_unc_hist), in one GPU pass.  For every k the
+    sums over the levels >= k are the "uncertain" counts ``uncertainty_counts`` returns for the threshold k / levels, the sums over all
+    levels its base counts.  Accepts what ``uncertainty_counts`` accepts; an ``EntropyOfProbability`` goes through
+    ``uncertainty_histogram_from_p`` (no entropy volume)."""
+    if isinstance(uncertainty, EntropyOfProbability):
+        return uncertainty_histogram_from_p(prediction, target, uncertainty.foreground_probability, levels, mask, n_volumes)
+    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
+    return _histogram_on_device('rcu_unc_hist', uncertainty, torch.float64 if is64 else torch.float32, (int(is64),), prediction, target,
+                                levels, mask, n_volumes)
+
+
+def uncertainty_histogram_from_p(prediction, target, foreground_probability, levels=UE_LEVELS, mask=None, n_volumes=1):
+    """``uncertainty_histogram`` for uncertainty = ToEntropy([1 - p, p]), from the float32 foreground-probability map itself: the entropy
+    is computed in registers with ``normalised_entropy``'s arithmetic, so the result equals
+    ``uncertainty_histogram(..., normalised_entropy(p))`` integer for integer and the float64 map is never made."""
+    return _histogram_on_device('rcu_unc_hist_from_p', foreground_probability, torch.float32, (), prediction, target, levels, mask, n_volumes)
+
+
+def ue_curve_metrics(hist):
+    """Threshold-free uncertainty-error metrics of ONE level histogram ``[4, B]`` (cells tp, tn, fp, fn; a subject's, or the sum of
+    several subjects': histograms add) -> dict with the keys ``UE_CURVE_KEYS``.  Host arithmetic on Python integers, every ratio rounded once.
+    With e_l = fp_l + fn_l (errors of level l), c_l = tp_l + tn_l, n_l = e_l + c_l and totals E, C, N:
+      auroc   sum_l e_l (C_{<l} + c_l / 2) / (E C): the probability that an erroneous voxel is ranked more uncertain than a correct one,
+              ties counted half (sklearn.metrics.roc_auc_score(error, level))
+      auprc   sum_{l: e_l > 0} (e_l / E) (E_{>=l} / N_{>=l}): average precision of detecting errors, levels descending
+              (sklearn.metrics.average_precision_score(error, level))
+      aurc    sum_{l: n_l > 0} (n_l / N) (E_{<=l} / N_{<=l}): mean selective risk, voxels accepted from the most certain level upwards, a
+              whole level at a time;  eaurc = aurc minus the same sum for the ideal ranking of the same E and N at the same coverages
+      ue_dice_max, ue_dice_max_threshold   the maximum over k = 1..B-1 of ``error_dice`` on the counts at the threshold k / B, and the
+              smallest such threshold that attains it
+    Undefined cases (E = 0 or C = 0 for auroc, E = 0 for auprc, N = 0 for all four) are ``float('nan')``."""
+    import math
+    h = np.asarray(hist)
+    if h.ndim != 2 or h.shape[0] != 4 or h.shape[1] < 2:
+        raise ValueError('expected one level histogram of shape [4, levels >= 2], got {}'.format(h.shape))
+    tp, tn, fp, fn = ([int(v) for v in row] for row in h)
+    levels = len(tp)
+    e = [fp[l] + fn[l] for l in range(levels)]
+    c = [tp[l] + tn[l] for l in range(levels)]
+    n_errors, n_correct = sum(e), sum(c)
+    n = n_errors + n_correct
+    nan = float('nan')
+    out = {'n': n, 'n_errors': n_errors}
+    # auroc: twice the numerator is an integer
+    below, twice = 0, 0
+    for l in range(levels):
+        twice += e[l] * (2 * below + c[l])
+        below += c[l]
+    out['auroc'] = twice / (2 * n_errors * n_correct) if n_errors and n_correct else nan
+    # auprc: levels descending
+    terms, e_ge, n_ge = [], 0, 0
+    for l in range(levels - 1, -1, -1):
+        e_ge += e[l]
+        n_ge += e[l] + c[l]
+        if e[l]:
+            terms.append((e[l] * e_ge) / (n_errors * n_ge))
+    out['auprc'] = math.fsum(terms) if n_errors else nan
+    # aurc / eaurc: levels ascending
+    risk, ideal, e_le, n_le = [], [], 0, 0
+    for l in range(levels):
+        n_l = e[l] + c[l]
+        e_le += e[l]
+        n_le += n_l
+        if n_l:
+            risk.append((n_l * e_le) / (n * n_le))
+            ideal.append((n_l * max(0, n_le - n_correct)) / (n * n_le))
+    out['aurc'] = math.fsum(risk) if n else nan
+    out['eaurc'] = out['aurc'] - math.fsum(ideal) if n else nan
+    # uncertainty-error Dice at its best threshold: suffix sums from the top
+    fp_all, fn_all = sum(fp), sum(fn)
+    dice_at, tpu, tnu, fpu, fnu = [None] * levels, 0, 0, 0, 0
+    for k in range(levels - 1, 0, -1):
+        tpu, tnu, fpu, fnu = tpu + tp[k], tnu + tn[k], fpu + fp[k], fnu + fn[k]
+        dice_at[k] = error_dice(fp_all, fn_all, tpu, tnu, fpu, fnu)
+    best = max(range(1, levels), key=lambda k: (dice_at[k], -k))
+    out['ue_dice_max'] = dice_at[best]
+    out['ue_dice_max_threshold'] = best / levels
+    return out
 
 
 def _counts(prediction, target, uncertainty, thresholds, mask=None):
