@@ -478,6 +478,58 @@ int rcu_unet_forward_sample_sigma_passes(rcu_unet* h, const float* x_dev, int n,
                                          uint64_t first_sample, int samples, void* stats_dev, int flags, float* sigma_sum_dev, int is_log_sigma,
                                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Connected components (EXTENSION: every measure of the reference is per voxel; rcu_amd.evaluation.connected_components, component_table,
+ * component_metrics and the 'components' evaluation action work on connected regions)
+ *   Labelling.  n_volumes independent volumes of depth x height x width uint8 voxels each (volume v at offset v * depth * height * width; a voxel
+ *   is foreground iff its value is not 0), connectivity 6 (face neighbours) or 26 (the 3 x 3 x 3 neighbourhood); with depth 1 these are the 2-D
+ *   4- and 8-neighbourhoods.  Volumes never connect to each other.
+ *     labels_dev   [n_volumes][depth * height * width] int32: 0 for background, for foreground 1 + the smallest linear index (C order within
+ *                  the volume) of any voxel of the component -- a function of the mask alone, whatever the tiles, the launch order or the batch
+ *   Block-based union-find (csrc/rcu_cc.hip): a tile-local pass in LDS, a seam pass and a flatten pass in global memory with agent-scope atomics,
+ *   lock-free (no workgroup ever waits for another).
+ *   Limits: depth, height, width >= 1, fewer than 2^31 - 1 voxels per volume, n_volumes in 1..65535, connectivity 6 or 26.
+ *
+ *   Table.  The components of the whole batch in increasing order of (volume, label) -- within a volume the raster order of the components' first
+ *   voxels, the numbering of scipy.ndimage.label --, one rcu_cc_entry each:
+ *     root           label - 1: the linear index of the component's first voxel
+ *     voxels         its size
+ *     other_voxels   its voxels where other_dev is not 0 (0 without other_dev)
+ *     unc_sum        the sum of q(u) over its voxels,   q(u) = rint(clamp(u, 0, 1) * 2^24) in float64, ties to even, NaN -> 0
+ *     unc_max        the maximum of q(u)
+ *   Integer sums (the idea of RCU_MC_EXACT): the table carries the same bits whatever the launch geometry or batching.  u is a float32 map
+ *   (RCU_CC_UNC_F32), a float64 map (RCU_CC_UNC_F64) or the normalised entropy of a float32 foreground-probability map computed in registers
+ *   with the arithmetic of rcu_normalised_entropy (RCU_CC_UNC_P: the table equals the one of RCU_CC_UNC_F64 on rcu_normalised_entropy's output,
+ *   integer for integer); RCU_CC_UNC_NONE with a null unc_dev leaves unc_sum and unc_max 0.
+ *   Three calls, all stream-ordered, over labels in the format above:
+ *     rcu_cc_compact   ranks the roots: counts_dev[v] (uint32, [n_volumes]) = the components of volume v; the ranks stay in workspace_dev
+ *     rcu_cc_relabel   dense_dev [n_volumes][n_per_volume] int32 = 1 .. counts[v] in table order, 0 for background (may be labels_dev itself)
+ *     rcu_cc_table     fills table_dev[0 .. table_entries), table_entries = the sum of counts (the caller reads the counts in between); volume
+ *                      v's rows start at the sum of the counts in front of it.  Rows beyond table_entries are never written.
+ *   workspace_dev: rcu_cc_workspace_bytes(n_per_volume, n_volumes) bytes, the same memory for the three calls (0 for arguments out of range).
+ *   Limits: those of the labelling and n_per_volume * n_volumes < 2^32.
+ *   Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it).
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_CC_UNC_NONE 0
+#define RCU_CC_UNC_F32 1
+#define RCU_CC_UNC_F64 2
+#define RCU_CC_UNC_P 3
+typedef struct rcu_cc_entry {
+    int32_t root;
+    uint32_t voxels, other_voxels, unc_max;
+    uint64_t unc_sum;
+} rcu_cc_entry;      /* 24 bytes */
+
+int rcu_cc_label(const uint8_t* mask_dev, int depth, int height, int width, int n_volumes, int connectivity, int32_t* labels_dev, void* stream);
+size_t rcu_cc_workspace_bytes(size_t n_per_volume, int n_volumes);
+int rcu_cc_compact(const int32_t* labels_dev, size_t n_per_volume, int n_volumes, uint32_t* counts_dev, void* workspace_dev, void* stream);
+int rcu_cc_relabel(const int32_t* labels_dev, size_t n_per_volume, int n_volumes, const void* workspace_dev, int32_t* dense_dev, void* stream);
+int rcu_cc_table(const int32_t* labels_dev, const uint8_t* other_dev, const void* unc_dev, int unc_kind, size_t n_per_volume, int n_volumes,
+                 const void* workspace_dev, rcu_cc_entry* table_dev, size_t table_entries, void* stream);
+/* Test / tuning aid (as rcu_unc_hist_set_blocks_per_workgroup): the tile of the labelling's LDS pass, every extent >= 1 and at most 1024 voxels
+ * in all; 0, 0, 0 = the launcher's choice (4 x 8 x 32, or 1 x 16 x 64 for depth 1).  Every tile gives the same labels.  Process-wide. */
+int rcu_cc_set_tile(int tile_depth, int tile_height, int tile_width);
+
 #ifdef __cplusplus
 }
 #endif

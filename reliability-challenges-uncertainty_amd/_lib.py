@@ -20,6 +20,8 @@ RCU_MC_EXACT_MAX_PASSES = 2048
 RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
 RCU_UNC_HIST_MAX_LEVELS = 4096
+# connected components (include/rcu.h): the uncertainty source of rcu_cc_table
+RCU_CC_UNC_NONE, RCU_CC_UNC_F32, RCU_CC_UNC_F64, RCU_CC_UNC_P = 0, 1, 2, 3
 # test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
 # temperature scaling (include/rcu.h): candidates per rcu_temperature_nll call
 RCU_TEMPERATURE_MAX_CANDIDATES = 128
@@ -122,6 +124,12 @@ SIGNATURES = {
     'rcu_unc_hist': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_unc_hist_from_p': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_unc_hist_set_blocks_per_workgroup': (c_int, [c_int]),
+    'rcu_cc_label': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_cc_workspace_bytes': (c_size_t, [c_size_t, c_int]),
+    'rcu_cc_compact': (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_cc_relabel': (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_cc_table': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'rcu_cc_set_tile': (c_int, [c_int, c_int, c_int]),
     'rcu_tta_transform': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_mc_fold_transformed': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rcu_unet_set_temperature': (c_int, [c_void_p, c_double]),

@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves is an extension
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves and components are extensions
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -35,6 +35,10 @@ MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
 UE_CURVES_PLACEHOLDER = 'eval_ue_curves_{}.csv'
 UE_CURVES_POOLED_PLACEHOLDER = 'eval_ue_curves_pooled_{}.csv'
 UE_LEVELS_PLACEHOLDER = 'eval_ue_levels_{}.csv'
+# rcu_amd extension (the 'components' action), in UNCERTAINTY_NAME as well
+COMPONENTS_PLACEHOLDER = 'eval_components_{}.csv'
+COMPONENTS_POOLED_PLACEHOLDER = 'eval_components_pooled_{}.csv'
+COMPONENT_LIST_PLACEHOLDER = 'eval_component_list_{}.csv'
 
 CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities', 'center': 'probabilities',
                     'center_mc': 'probabilities', 'ensemble': 'probabilities', 'auxiliary_feat': 'confidence',
@@ -477,11 +481,78 @@ class UeCurvesAction(EvalAction):
                 writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]])
 
 
+class ComponentsAction(EvalAction):
+    """EXTENSION (the reference has no such action): component-level uncertainty metrics from connected components labelled on the GPU
+    (evaluation.component_table / component_metrics).  The uncertainty is prepared exactly like ``UeCurvesAction``'s -- the entropy of a
+    probability map in registers, the rescaled map of a 'confidence' / 'sigma' run -- and there is no brain mask.  Files in
+    ``<base_dir>/uncertainty``:
+      eval_components_<id>.csv          one row per subject: the keys of evaluation.COMPONENT_METRIC_KEYS
+      eval_components_pooled_<id>.csv   the same metrics of all subjects' tables together (whatever the batching or the subject order)
+      eval_component_list_<id>.csv      one row per predicted component: subject, component (1..K in raster order of first voxels), root_index,
+                                        voxels, target_voxels, mean_uncertainty, max_uncertainty, is_fp"""
+
+    LIST_HEADER = ('subject', 'component', 'root_index', 'voxels', 'target_voxels', 'mean_uncertainty', 'max_uncertainty', 'is_fp')
+
+    def __init__(self, levels, connectivity, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        super().__init__()
+        self.levels, self.connectivity = int(levels), int(connectivity)
+        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
+            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        if self.connectivity not in (6, 26):
+            raise ValueError('connectivity must be 6 or 26, got {}'.format(connectivity))
+        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
+        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.tables, self.list_rows = [], []
+
+    def setup_eval(self, eval_data):
+        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
+        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
+        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
+                                                                self.rescale_confidence, self.rescale_sigma, mm)
+        self.load_params = Loader.Params(eval_data.confidence_entry)
+        hook = WriteCsvHook(os.path.join(self.out_dir, COMPONENTS_PLACEHOLDER.format(self.id_)), entries=ev.COMPONENT_METRIC_KEYS)
+        self.eval_cases = [EvalCase(None, hook)]
+        self.tables, self.list_rows = [], []
+
+    def record_tables(self, pred_table, target_table, subject_name):
+        """One subject's two tables: its metrics row, its components' rows, and its share of the pooled tables."""
+        self.eval_cases[0].record(ev.component_metrics(pred_table, target_table, self.levels), subject_name, self.id_)
+        for k, row in enumerate(pred_table):
+            voxels, overlap = int(row['voxels']), int(row['other_voxels'])
+            self.list_rows.append([subject_name, k + 1, int(row['root']), voxels, overlap, int(row['unc_sum']) / (voxels * ev.COMPONENT_UNC_ONE),
+                                   int(row['unc_max']) / ev.COMPONENT_UNC_ONE, int(overlap == 0)])
+        self.tables.append((pred_table, target_table))
+
+    def eval_subject(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        if self.prepare:
+            to_eval = self.prepare(to_eval)
+        pr, tg = to_eval['prediction'], to_eval['target']
+        self.record_tables(ev.component_table(pr, tg, to_eval['uncertainty'], self.connectivity)[0],
+                           ev.component_table(tg, pr, None, self.connectivity)[0], sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        empty = np.zeros(0, dtype=ev.COMPONENT_DTYPE)
+        pooled = ev.component_metrics(np.concatenate([empty] + [t[0] for t in self.tables]), np.concatenate([empty] + [t[1] for t in self.tables]),
+                                      self.levels)
+        with open(os.path.join(self.out_dir, COMPONENTS_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id'] + list(ev.COMPONENT_METRIC_KEYS))
+            writer.writerow([self.id_] + [pooled[k] for k in ev.COMPONENT_METRIC_KEYS])
+        with open(os.path.join(self.out_dir, COMPONENT_LIST_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(self.LIST_HEADER)
+            writer.writerows(self.list_rows)
+
+
 ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
-def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS):
-    """bin-eval/eval_uncertainty.py:226-244, plus the extension 'ue_curves' (``levels``: its number of uncertainty levels)."""
+def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26):
+    """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels) and 'components'
+    (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice)."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -494,6 +565,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(CorrectionAction(ev.UE_THRESHOLDS, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'ue_curves':
             actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'components':
+            actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
     return actions
 
 
@@ -579,20 +652,22 @@ class _LoaderAhead:
 
 def _fusable(entry, actions):
     """The fused loop covers the runs whose confidence entry IS the probability map (baseline, baseline_mc, center, center_mc, ensemble:
-    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script and 'ue_curves'."""
+    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script, 'ue_curves' and 'components'."""
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
-            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction) for a in actions) and
+            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction) for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
 
 def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
-    list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for)."""
+    list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
+    by a ComponentsAction, which holds the `connectivity`)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
            (['ue'] if (CorrectionAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
-           (['ue_hist'] if UeCurvesAction in by_type else [])
+           (['ue_hist'] if UeCurvesAction in by_type else []) + \
+           (['components'] if ComponentsAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -630,6 +705,8 @@ def record_subject(actions, subject, res, slot, n_dim):
                 case.record(ev.correction_results(counts[t]), subject, action.id_)
         elif isinstance(action, UeCurvesAction):
             action.record_histogram(res['ue_hist'][slot], subject)
+        elif isinstance(action, ComponentsAction):
+            action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -640,6 +717,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
     want, thresholds, want_mask = metrics_wanted(actions)
     levels = next((a.levels for a in actions if isinstance(a, UeCurvesAction)), ev.UE_LEVELS)
+    connectivity = next((a.connectivity for a in actions if isinstance(a, ComponentsAction)), 26)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
     files = entry.subject_files
     reader = _ReadAhead(files, params, depth=2 * batch_subjects)
@@ -666,7 +744,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want, levels=levels)
+            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)
@@ -695,13 +773,15 @@ class _Done:
         return self.value
 
 
-def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS):
+def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
+                  connectivity=26):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
-    ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' action."""
-    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels)
+    ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
+    'components' actions; ``connectivity``: of the 'components' action."""
+    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

@@ -141,6 +141,7 @@ class SubjectBatch:
         self._pinned = None
         self._staged = set()        # (entry, slot) pairs filled on the host since the last upload
         self.used = 0
+        self.shapes = {}            # slot -> the shape its prediction was put with (what the 'components' scan labels)
 
     def _staging(self):
         if self._pinned is None:       # one pinned image of the batch: the slots are filled on the host, the batch goes up in four copies
@@ -171,6 +172,7 @@ class SubjectBatch:
                 np.copyto(dst, a.reshape(-1), casting='unsafe')      # (bool / int64 label maps -> uint8, as torch's cast on the device would)
                 self._staged.add((key, slot))
         self.used = max(self.used, slot + 1)
+        self.shapes[slot] = tuple(int(v) for v in (prediction.shape if hasattr(prediction, 'shape') else np.shape(prediction)))
 
     def upload(self):
         """Host-staged entries -> device (entries that were put as device tensors are there already and stay untouched)."""
@@ -186,12 +188,15 @@ class SubjectBatch:
                     dev[s_].copy_(host[s_], non_blocking=True)
         self._staged = set()
 
-    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000):
+    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26):
         """-> dict of host arrays over the ``used`` subjects: ``min`` / ``max`` (float32), ``hist`` = (count, sum_conf, sum_pos) of the
         reliability histogram inside the mask, ``counts`` [used, len(thresholds), 8] of the uncertainty-error action on the WHOLE volume
         (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice) and, with
         ``'ue_hist'`` in ``want``, ``ue_hist`` uint64 [used, 4, levels]: the level histogram of ``uncertainty_histogram_from_p``, on the whole
-        volume like the counts.  One launch per scan for all subjects, one synchronisation for all results."""
+        volume like the counts.  One launch per scan for all subjects, one synchronisation for all results.  With ``'components'`` in
+        ``want``, ``components`` = per subject the pair (table of the prediction's components with the target as the other map and the
+        entropy of p as the uncertainty, table of the target's components with the prediction as the other map) of ``component_table``,
+        labelled under ``connectivity`` in the shapes the subjects were put with -- from the resident maps, all subjects in one call."""
         v = self.used
         lib = _lib.load()
         out, keep = {}, []
@@ -217,6 +222,8 @@ class SubjectBatch:
             _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(self.p), _lib.ptr(self.prediction), _lib.ptr(self.target), None, self.n, v, int(levels),
                                                _lib.ptr(ue_hist), _lib.ptr(ws3), _lib.current_stream()))
             keep.append(('ue_hist', ue_hist))
+        if 'components' in want:
+            out['components'] = self._component_tables(v, connectivity)
         host = {k: t.cpu() for k, t in keep}          # (the first .cpu() waits for the stream: the others are ready by then)
         if 'minmax' in host:
             mm = host['minmax'].numpy()
@@ -229,6 +236,23 @@ class SubjectBatch:
         if 'ue_hist' in host:
             out['ue_hist'] = host['ue_hist'].numpy().view(np.uint64)
         return out
+
+
+    def _component_tables(self, v, connectivity):
+        shapes = [self.shapes[slot] for slot in range(v)]
+        pairs = [None] * v
+        for shape in sorted(set(shapes)):       # (subjects of one size are of one shape but for transposed images: one call per shape)
+            slots = [slot for slot in range(v) if shapes[slot] == shape]
+            if len(slots) == v:
+                p, pr, tg = self.p[:v], self.prediction[:v], self.target[:v]
+            else:
+                index = torch.as_tensor(slots, device=self.device)
+                p, pr, tg = self.p[index], self.prediction[index], self.target[index]
+            of_prediction = _component_tables_on_device(pr, _volume_dims(shape), tg, _lib.RCU_CC_UNC_P, p, connectivity)
+            of_target = _component_tables_on_device(tg, _volume_dims(shape), pr, _lib.RCU_CC_UNC_NONE, None, connectivity)
+            for k, slot in enumerate(slots):
+                pairs[slot] = (of_prediction[k], of_target[k])
+        return pairs
 
 
 # ---------------------------------------------------------------------- uncertainty-error counts
@@ -415,6 +439,181 @@ def ue_curve_metrics(hist):
     best = max(range(1, levels), key=lambda k: (dice_at[k], -k))
     out['ue_dice_max'] = dice_at[best]
     out['ue_dice_max_threshold'] = best / levels
+    return out
+
+
+# ------------------------------------------------ component-level metrics from connected components on the GPU (EXTENSION)
+# one row per component (include/rcu.h, rcu_cc_entry: unc_max sits in front of unc_sum in memory)
+COMPONENT_DTYPE = np.dtype({'names': ['root', 'voxels', 'other_voxels', 'unc_sum', 'unc_max'], 'formats': ['<i4', '<u4', '<u4', '<u8', '<u4'],
+                            'offsets': [0, 4, 8, 16, 12], 'itemsize': 24})
+COMPONENT_UNC_ONE = 1 << 24       # the integer of an uncertainty of 1: q(u) = rint(clamp(u, 0, 1) * 2^24)
+COMPONENT_METRIC_KEYS = ('n_components', 'n_fp_components', 'fp_voxels', 'n_target_components', 'n_missed_target_components', 'auroc_fp',
+                         'auprc_fp', 'dice', 'dice_filtered_max', 'dice_filtered_max_threshold')
+
+
+def _volume_dims(shape):
+    """(depth, height, width) of a volume of this shape: up to three axes, the missing leading ones of extent 1 (2-D images: depth 1)."""
+    shape = tuple(int(v) for v in shape)
+    if not 1 <= len(shape) <= 3:
+        raise ValueError('a volume has one to three axes, got shape {}'.format(shape))
+    return (1,) * (3 - len(shape)) + shape
+
+
+def _split_volumes(shape, n_volumes):
+    """The shape of ONE volume: the whole array for n_volumes = 1, else the axes behind a leading axis of n_volumes."""
+    shape = tuple(int(v) for v in shape)
+    if n_volumes == 1:
+        return shape
+    if not shape or shape[0] != n_volumes:
+        raise ValueError('n_volumes = {} needs a leading axis of that extent, got shape {}'.format(n_volumes, shape))
+    return shape[1:]
+
+
+def _labels_on_device(mask, dims, connectivity):
+    """mask: device uint8 [V, n] -> device int32 [V, n] canonical labels (0 background, else 1 + the component's smallest linear index)."""
+    v, n = mask.shape
+    labels = torch.empty((v, n), device=mask.device, dtype=torch.int32)
+    _lib.check(_lib.load().rcu_cc_label(_lib.ptr(mask), dims[0], dims[1], dims[2], v, int(connectivity), _lib.ptr(labels), _lib.current_stream()))
+    return labels
+
+
+def _compact_on_device(labels):
+    """-> (components per volume as a host int64 array, the workspace that holds the roots' ranks).  Waits for the stream."""
+    v, n = labels.shape
+    lib = _lib.load()
+    ws = torch.empty(max(lib.rcu_cc_workspace_bytes(n, v), 8), device=labels.device, dtype=torch.uint8)
+    counts = torch.empty(v, device=labels.device, dtype=torch.int32)
+    _lib.check(lib.rcu_cc_compact(_lib.ptr(labels), n, v, _lib.ptr(counts), _lib.ptr(ws), _lib.current_stream()))
+    return counts.cpu().numpy().view(np.uint32).astype(np.int64), ws
+
+
+def _component_tables_on_device(mask, dims, other, unc_kind, unc, connectivity):
+    """Device arrays [V, n] (mask, other: uint8 or None; unc as ``unc_kind`` says) -> list of V host tables of COMPONENT_DTYPE."""
+    v, n = mask.shape
+    labels = _labels_on_device(mask, dims, connectivity)
+    counts, ws = _compact_on_device(labels)
+    total = int(counts.sum())
+    table = torch.empty(max(total, 1) * COMPONENT_DTYPE.itemsize, device=mask.device, dtype=torch.uint8)
+    _lib.check(_lib.load().rcu_cc_table(_lib.ptr(labels), _lib.ptr(other), _lib.ptr(unc), int(unc_kind), n, v, _lib.ptr(ws), _lib.ptr(table), total,
+                                        _lib.current_stream()))
+    rows = table.cpu().numpy()[:total * COMPONENT_DTYPE.itemsize].view(COMPONENT_DTYPE)
+    ends = np.cumsum(counts)
+    return [rows[int(e - c):int(e)].copy() for c, e in zip(counts, ends)]
+
+
+def connected_components(mask, connectivity=26, n_volumes=1):
+    """Connected components of a binary mask (foreground: not 0) on the GPU -> ``(labels, counts)``: ``labels`` int32 of the mask's shape, 0
+    for background and 1..K per volume in raster order of the components' first voxels (scipy.ndimage.label's numbering), ``counts``
+    int64 ``[n_volumes]`` = K per volume.  The mask's own shape gives depth / height / width (2-D arrays: depth 1, where connectivity 6 / 26
+    are the 4- / 8-neighbourhoods); ``n_volumes`` > 1 treats the leading axis as independent volumes.  A device tensor gets a device tensor."""
+    dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
+    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    labels = _labels_on_device(m, dims, connectivity)
+    counts, ws = _compact_on_device(labels)
+    dense = torch.empty_like(labels)
+    _lib.check(_lib.load().rcu_cc_relabel(_lib.ptr(labels), m.shape[1], n_volumes, _lib.ptr(ws), _lib.ptr(dense), _lib.current_stream()))
+    dense = dense.reshape(tuple(mask.shape))
+    return (dense if isinstance(mask, torch.Tensor) and mask.is_cuda else dense.cpu().numpy()), counts
+
+
+def canonical_labels(mask, connectivity=26, n_volumes=1):
+    """The labelling before it is made dense (include/rcu.h, rcu_cc_label): int32 of the mask's shape, 0 for background, else 1 + the
+    smallest linear index (C order within the volume) of the voxel's component.  Host array."""
+    dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
+    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    return _labels_on_device(m, dims, connectivity).cpu().numpy().reshape(tuple(mask.shape))
+
+
+def component_table(mask, other=None, uncertainty=None, connectivity=26, n_volumes=1):
+    """One structured array (COMPONENT_DTYPE) per volume -> list of ``n_volumes`` tables, the components of ``mask`` in the order of
+    ``connected_components``' labels with the fields
+      root           linear index of the component's first voxel          voxels         its size
+      other_voxels   its voxels where ``other`` is not 0 (0 without it)
+      unc_sum        sum of q(u) over its voxels, q(u) = rint(clamp(u, 0, 1) * 2^24) in float64 (NaN -> 0);     unc_max   max of q(u)
+    Integer sums: the same bits whatever the launch geometry or batching.  ``uncertainty``: a float64 or float32 map, or an
+    ``EntropyOfProbability`` whose entropy is computed in registers (the table of its materialised map, integer for integer); numpy
+    arrays or device tensors."""
+    dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
+    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    o = None if other is None else _to_dev(other, torch.uint8).reshape(n_volumes, -1)
+    if o is not None and o.shape != m.shape:
+        raise ValueError('mask and other differ in size')
+    kind, u = _lib.RCU_CC_UNC_NONE, None
+    if isinstance(uncertainty, EntropyOfProbability):
+        kind, u = _lib.RCU_CC_UNC_P, _to_dev(uncertainty.foreground_probability, torch.float32).reshape(n_volumes, -1)
+    elif uncertainty is not None:
+        is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
+        kind = _lib.RCU_CC_UNC_F64 if is64 else _lib.RCU_CC_UNC_F32
+        u = _to_dev(uncertainty, torch.float64 if is64 else torch.float32).reshape(n_volumes, -1)
+    if u is not None and u.shape != m.shape:
+        raise ValueError('mask and uncertainty differ in size')
+    return _component_tables_on_device(m, dims, o, kind, u, connectivity)
+
+
+def component_metrics(pred_table, target_table, levels=UE_LEVELS):
+    """Component-level metrics of the prediction's table (other map: the target) and the target's table (other map: the prediction) --
+    one subject's, or several subjects' tables concatenated: tables add by concatenation, and nothing here depends on the order of the
+    rows -> dict with the keys ``COMPONENT_METRIC_KEYS``.  Host arithmetic on Python integers, every ratio rounded once.
+      m_k = unc_sum_k / (voxels_k * 2^24), one float64 division: the mean uncertainty of predicted component k
+      a predicted component is a false positive iff its other_voxels == 0; a target component is missed iff its other_voxels == 0
+      auroc_fp, auprc_fp   detection of the false-positive components by m_k, ties counted half: the formulas of ``ue_curve_metrics`` with
+                           components in place of voxels and the distinct values of m_k in place of the levels (NaN where undefined)
+      dice                 2 TP / (P + T): P, TP = the sums of the prediction table's voxels, other_voxels, T = the target table's voxels
+      dice_filtered_max, dice_filtered_max_threshold   over the thresholds k / levels, k = 0..levels, the predicted components with
+                           m_k > k / levels (float64) removed: 2 (TP - removed other_voxels) / (P - removed voxels + T); the maximum and the
+                           smallest threshold that attains it"""
+    import bisect
+    import math
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError('levels must be >= 1, got {}'.format(levels))
+    voxels = [int(x) for x in pred_table['voxels']]
+    overlap = [int(x) for x in pred_table['other_voxels']]
+    mean = [int(s_) / (v_ * COMPONENT_UNC_ONE) for s_, v_ in zip(pred_table['unc_sum'], voxels)]
+    is_fp = [o == 0 for o in overlap]
+    p_all, tp, t_all = sum(voxels), sum(overlap), sum(int(x) for x in target_table['voxels'])
+    nan = float('nan')
+    out = {'n_components': len(voxels), 'n_fp_components': sum(is_fp), 'fp_voxels': sum(v_ for v_, f in zip(voxels, is_fp) if f),
+           'n_target_components': len(target_table), 'n_missed_target_components': int(sum(1 for x in target_table['other_voxels'] if int(x) == 0))}
+    # the distinct scores ascending, with their false-positive and true-positive component counts
+    groups = {}
+    for m_, f in zip(mean, is_fp):
+        g = groups.setdefault(m_, [0, 0])
+        g[0 if f else 1] += 1
+    scores = sorted(groups)
+    n_pos, n_neg = out['n_fp_components'], len(voxels) - out['n_fp_components']
+    below, twice = 0, 0
+    for sc in scores:
+        pos, neg = groups[sc]
+        twice += pos * (2 * below + neg)
+        below += neg
+    out['auroc_fp'] = twice / (2 * n_pos * n_neg) if n_pos and n_neg else nan
+    terms, pos_ge, n_ge = [], 0, 0
+    for sc in reversed(scores):
+        pos, neg = groups[sc]
+        pos_ge += pos
+        n_ge += pos + neg
+        if pos:
+            terms.append((pos * pos_ge) / (n_pos * n_ge))
+    out['auprc_fp'] = math.fsum(terms) if n_pos else nan
+    out['dice'] = _dice(tp, p_all - tp, t_all - tp)
+    # component k is removed at the thresholds below m_k: at k' / levels for k' < c_k = #{k' : k' / levels < m_k}
+    grid = [k / levels for k in range(levels + 1)]
+    gone_voxels, gone_overlap = [0] * (levels + 2), [0] * (levels + 2)
+    for m_, v_, o in zip(mean, voxels, overlap):
+        c = bisect.bisect_left(grid, m_)
+        gone_voxels[c] += v_
+        gone_overlap[c] += o
+    removed_v, removed_o = sum(gone_voxels), sum(gone_overlap)
+    best, best_k = None, None
+    for k in range(levels + 1):
+        removed_v -= gone_voxels[k]          # now the sums over c > k
+        removed_o -= gone_overlap[k]
+        d = _dice(tp - removed_o, (p_all - removed_v) - (tp - removed_o), t_all - (tp - removed_o))
+        if best is None or d > best:
+            best, best_k = d, k
+    out['dice_filtered_max'] = best
+    out['dice_filtered_max_threshold'] = best_k / levels
     return out
 
 
