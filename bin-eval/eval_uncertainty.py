@@ -14,8 +14,9 @@ if __name__ == '__main__':
     parser.add_argument('--ds', type=str, nargs='?', help='the dataset to evaluate the runs on')
     parser.add_argument('--ids', type=str, nargs='*', help='the ids of the runs to be evaluated')
     parser.add_argument('--act', type=str, nargs='*', help='the names of the evaluation configuration: minmax, ece_dice, calib, bnf_ue (the default: '
-                        'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) and components '
-                        '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice)')
+                        'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) components '
+                        '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice) and '
+                        'boundary (errors and uncertainty by distance to the target\'s boundary, surface distances, metrics off the border shell)')
     parser.add_argument('--pred_dir', type=str, default=None, help='root with one sub-directory per dataset and run id '
                         '(default: directories.PREDICT_DIR and the per-run *_PREDICT names)')
     parser.add_argument('--gt_dir', type=str, default=None, help='BraTS training tree / ISIC dataset prefix '
@@ -25,6 +26,7 @@ if __name__ == '__main__':
     parser.add_argument('--levels', type=int, default=1000, help='rcu_amd: uncertainty levels of the ue_curves action and threshold grid of the '
                         'components action (2..4096)')
     parser.add_argument('--connectivity', type=int, default=26, choices=(6, 26), help='rcu_amd: neighbourhood of the components action (2-D images: 4 / 8)')
+    parser.add_argument('--bands', type=int, default=10, help='rcu_amd: distance bands of the boundary action (1..64)')
     parser.add_argument('--plain', action='store_true', help='rcu_amd: the reference\'s subject-by-subject, action-by-action loop for every run')
     args = parser.parse_args()
     from rcu_amd import directories as dirs
@@ -46,4 +48,4 @@ if __name__ == '__main__':
     runs = {i: (os.path.join(args.pred_dir, ds, i) if args.pred_dir else dirs.prediction_dir(ds, i)) for i in ids}
     out_dir = os.path.join(args.out_dir, ds) if args.out_dir else dirs.eval_dir(ds)
     scripts.eval_uncertainty(ds, runs, gt_dir, out_dir, acts, fused=not args.plain, batch_subjects=args.batch_subjects,
-                             levels=args.levels, connectivity=args.connectivity)
+                             levels=args.levels, connectivity=args.connectivity, bands=args.bands)

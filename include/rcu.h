@@ -530,6 +530,65 @@ int rcu_cc_table(const int32_t* labels_dev, const uint8_t* other_dev, const void
  * in all; 0, 0, 0 = the launcher's choice (4 x 8 x 32, or 1 x 16 x 64 for depth 1).  Every tile gives the same labels.  Process-wide. */
 int rcu_cc_set_tile(int tile_depth, int tile_height, int tile_width);
 
+/* ------------------------------------------------------------------------------------------
+ * Distance transform (EXTENSION: where in the image the errors and the uncertainty sit; rcu_amd.evaluation.distance_transform_sq, boarder_mask,
+ * boundary_table, surface_distance_histograms and the 'boundary' evaluation action.  The reference builds its border shell with two host
+ * distance transforms: common/utils/labelhelper.py:12-20)
+ *   Transform.  n_volumes independent volumes of depth x height x width uint8 voxels, laid out as for rcu_cc_label; volumes never see each other.
+ *   The feature set of a volume is its voxels with value 0 (zero_is_feature = 1: scipy.ndimage.distance_transform_edt(mask)) or with a value
+ *   other than 0 (zero_is_feature = 0: the transform of ~mask, with no inverted copy made).
+ *     out_dev   [n_volumes][depth * height * width] uint32: the minimum over the feature voxels w of the same volume of |v - w|^2, unit spacing:
+ *               an exact integer, 0 on the feature voxels -- a function of the mask alone, whatever the launch geometry or the batch
+ *   A volume without a feature voxel gets RCU_EDT_NONE everywhere.  (scipy's output there is an artefact -- distances to a virtual voxel in front
+ *   of the array -- and is NOT copied.)  Depth 1 gives the 2-D transform.
+ *   Three separable passes in place in out_dev (csrc/rcu_edt.hip): a two-sweep ballot scan per row, then min_j f(j) + (i - j)^2 along the height
+ *   and the depth from a slab in LDS, every thread walking outward from its own voxel until (i - j)^2 reaches its best.  Integers only; sums with
+ *   NONE saturate.
+ *   Limits: every extent in 1..16384 (the three squares then add below 2^32 - 1), fewer than 2^31 - 1 voxels per volume, n_volumes in 1..65535,
+ *   n_per_volume * n_volumes < 2^32, zero_is_feature 0 or 1.
+ *
+ *   Border shell.  From d_in = the transform of a label map with zero_is_feature = 1 (squared distance to the nearest background voxel) and d_out
+ *   = the one with zero_is_feature = 0 (to the nearest foreground voxel), n entries each:
+ *     mask_dev       uint8 (d_in <= distance_in^2) && (d_out <= distance_out^2), compared in integers: labelhelper.boarder_mask's mask
+ *     distance_dev   float64 sqrt(d_in + d_out), correctly rounded (one of the two terms is 0): labelhelper.boarder_mask's distance, bit for bit
+ *   RCU_EDT_NONE counts as +inf: no border on that side, and the distance is inf.  Either output may be null, not both.  distance_in and
+ *   distance_out in 0..65535.
+ *
+ *   Boundary table.  Per volume 2 x (bands + 1) cells, cell (side, band) at index side * (bands + 1) + band:
+ *     side   target != 0;     band   from d = d_in + d_out of the TARGET: band k < bands holds k^2 < d <= (k + 1)^2, band `bands` holds
+ *            d > bands^2, RCU_EDT_NONE included.  Integer comparisons.  Band 0 of both sides together is the reference's border shell (1, 1).
+ *     voxels, errors ((prediction != 0) != (target != 0)), unc_sum = the sum of q(u) over the cell's voxels, unc_err_sum = over its error voxels
+ *   q and the uncertainty sources are rcu_cc_table's (RCU_CC_UNC_NONE / _F32 / _F64 / _P, the same arithmetic).  Integer sums, reduced per wave and
+ *   per workgroup in LDS before they reach global memory: the same bits whatever the batching.  bands in 1..64; the limits of rcu_cc_table.
+ *
+ *   Surface distances.  The surface of a label map A is S(A) = {v in A : d_in_A(v) == 1}: the voxels of A that are face-adjacent to a voxel
+ *   outside A INSIDE the volume (A & ~scipy.ndimage.binary_erosion(A, border_value=1); medpy's border_value=0 differs from it only where A touches
+ *   the volume face, whose voxels medpy counts as surface).  For the maps P and T of every volume:
+ *     hist_dev   [n_volumes][2][bins] uint32, bins = rcu_surface_distance_bins(depth, height, width) = (D-1)^2 + (H-1)^2 + (W-1)^2 + 2:
+ *                direction 0 counts the voxels of S(P) by their squared distance to S(T) (rcu_edt_sq with the feature set S(T)), direction 1 the
+ *                voxels of S(T) by their squared distance to S(P); the LAST bin counts the voxels whose other surface is empty (RCU_EDT_NONE)
+ *   workspace_dev: rcu_surface_distance_workspace_bytes(n_per_volume, n_volumes) bytes (0 for arguments out of range).  The limits of rcu_edt_sq.
+ *   Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it).
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_EDT_NONE 0xFFFFFFFFu
+typedef struct rcu_boundary_cell {
+    uint64_t voxels, errors, unc_sum, unc_err_sum;
+} rcu_boundary_cell;      /* 32 bytes */
+
+int rcu_edt_sq(const uint8_t* mask_dev, int depth, int height, int width, int n_volumes, int zero_is_feature, uint32_t* out_dev, void* stream);
+int rcu_border_mask(const uint32_t* d_in_dev, const uint32_t* d_out_dev, size_t n, int distance_in, int distance_out, uint8_t* mask_dev,
+                    double* distance_dev, void* stream);
+int rcu_boundary_table(const uint8_t* prediction_dev, const uint8_t* target_dev, const uint32_t* d_in_dev, const uint32_t* d_out_dev,
+                       const void* unc_dev, int unc_kind, size_t n_per_volume, int n_volumes, int bands, rcu_boundary_cell* table_dev, void* stream);
+size_t rcu_surface_distance_bins(int depth, int height, int width);
+size_t rcu_surface_distance_workspace_bytes(size_t n_per_volume, int n_volumes);
+int rcu_surface_distance_hist(const uint8_t* prediction_dev, const uint8_t* target_dev, int depth, int height, int width, int n_volumes,
+                              uint32_t* hist_dev, void* workspace_dev, void* stream);
+/* Test / tuning aid (as rcu_cc_set_tile): the run of adjacent x a workgroup of the height / depth passes stages per line, a power of two in
+ * 1..64; 0 = the launcher's choice (32).  It is halved until a whole line fits the slab (16384 entries).  Every width gives the same distances.
+ * Process-wide. */
+int rcu_edt_set_slab_width(int slab_width);
+
 #ifdef __cplusplus
 }
 #endif

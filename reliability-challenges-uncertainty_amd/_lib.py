@@ -22,6 +22,9 @@ RCU_MAX_THRESHOLDS = 16
 RCU_UNC_HIST_MAX_LEVELS = 4096
 # connected components (include/rcu.h): the uncertainty source of rcu_cc_table
 RCU_CC_UNC_NONE, RCU_CC_UNC_F32, RCU_CC_UNC_F64, RCU_CC_UNC_P = 0, 1, 2, 3
+# distance transform (include/rcu.h): the squared distance of a volume without a feature voxel; the most bands of rcu_boundary_table
+RCU_EDT_NONE = 0xFFFFFFFF
+RCU_BOUNDARY_MAX_BANDS = 64
 # test-time augmentation (include/rcu.h): the element codes of D4 on (H, W)
 # temperature scaling (include/rcu.h): candidates per rcu_temperature_nll call
 RCU_TEMPERATURE_MAX_CANDIDATES = 128
@@ -130,6 +133,13 @@ SIGNATURES = {
     'rcu_cc_relabel': (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_cc_table': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'rcu_cc_set_tile': (c_int, [c_int, c_int, c_int]),
+    'rcu_edt_sq': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_border_mask': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_boundary_table': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_surface_distance_bins': (c_size_t, [c_int, c_int, c_int]),
+    'rcu_surface_distance_workspace_bytes': (c_size_t, [c_size_t, c_int]),
+    'rcu_surface_distance_hist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_edt_set_slab_width': (c_int, [c_int]),
     'rcu_tta_transform': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_mc_fold_transformed': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'rcu_unet_set_temperature': (c_int, [c_void_p, c_double]),

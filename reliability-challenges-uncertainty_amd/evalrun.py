@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves and components are extensions
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components and boundary are extensions
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -39,6 +39,10 @@ UE_LEVELS_PLACEHOLDER = 'eval_ue_levels_{}.csv'
 COMPONENTS_PLACEHOLDER = 'eval_components_{}.csv'
 COMPONENTS_POOLED_PLACEHOLDER = 'eval_components_pooled_{}.csv'
 COMPONENT_LIST_PLACEHOLDER = 'eval_component_list_{}.csv'
+# rcu_amd extension (the 'boundary' action), in UNCERTAINTY_NAME as well
+BOUNDARY_PLACEHOLDER = 'eval_boundary_{}.csv'
+BOUNDARY_POOLED_PLACEHOLDER = 'eval_boundary_pooled_{}.csv'
+BOUNDARY_BANDS_PLACEHOLDER = 'eval_boundary_bands_{}.csv'
 
 CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities', 'center': 'probabilities',
                     'center_mc': 'probabilities', 'ensemble': 'probabilities', 'auxiliary_feat': 'confidence',
@@ -249,11 +253,14 @@ class Loader:
     """Per-subject cached reads (analysis.py:15-125)."""
 
     class Params:
-        def __init__(self, misc_entry='probabilities', need_target=True, need_prediction=True, need_t2_mask=False):
+        def __init__(self, misc_entry='probabilities', need_target=True, need_prediction=True, need_t2_mask=False,
+                     need_gt_dist_and_boarder=False, need_prediction_dist_and_boarder=False):
             self.misc_entry = misc_entry
             self.need_target = need_target
             self.need_prediction = need_prediction
             self.need_t2_mask = need_t2_mask
+            self.need_gt_dist_and_boarder = need_gt_dist_and_boarder
+            self.need_prediction_dist_and_boarder = need_prediction_dist_and_boarder
 
     def __init__(self) -> None:
         self.cached = {}
@@ -264,18 +271,37 @@ class Loader:
             self.cached[key] = fn()
         return self.cached[key].copy()
 
+    def _get_dist_and_boarder(self, boarder_entry, dist_entry, read_label_map):
+        """analysis.py:109-116: the border shell (1, 1) and the distance map of a label map, on the GPU, cached per subject.  -> (mask, distance)"""
+        if boarder_entry not in self.cached or dist_entry not in self.cached:
+            distance, mask = ev.boarder_mask(read_label_map().astype(bool), 1, 1)
+            self.cached[boarder_entry] = mask
+            self.cached[dist_entry] = distance
+        return self.cached[boarder_entry].copy(), self.cached[dist_entry].copy()
+
     def get_data(self, sf: SubjectFiles, params):
         if sf.subject != self.cached_subject:
             self.cached.clear()
             self.cached_subject = sf.subject
         to_eval = {params.misc_entry: self._get(params.misc_entry,
                                                 lambda: nifti.read(sf.categories['misc'][params.misc_entry])[0])}
-        if params.need_target:   # labels 0..4 are binarised (analysis.py:88-89)
-            to_eval['target'] = self._get('target', lambda: (read_label_image(sf.categories['labels']['gt']) > 0)
-                                          .astype(np.uint8))
+
+        def read_target():       # labels 0..4 are binarised (analysis.py:88-89)
+            return self._get('target', lambda: (read_label_image(sf.categories['labels']['gt']) > 0).astype(np.uint8))
+
+        def read_prediction():
+            return self._get('prediction', lambda: nifti.read(sf.categories['labels']['prediction'], np.uint8)[0])
+
+        if params.need_target:
+            to_eval['target'] = read_target()
         if params.need_prediction:
-            to_eval['prediction'] = self._get('prediction', lambda: nifti.read(sf.categories['labels']['prediction'],
-                                                                               np.uint8)[0])
+            to_eval['prediction'] = read_prediction()
+        # analysis.py:54-64: the mask under *_boarder, the distance under *_distance
+        if getattr(params, 'need_gt_dist_and_boarder', False):
+            to_eval['target_boarder'], to_eval['target_distance'] = self._get_dist_and_boarder('target_boarder', 'target_distance', read_target)
+        if getattr(params, 'need_prediction_dist_and_boarder', False):
+            to_eval['prediction_boarder'], to_eval['prediction_distance'] = self._get_dist_and_boarder('prediction_boarder', 'prediction_distance',
+                                                                                                   read_prediction)
         if params.need_t2_mask:
             to_eval['mask'] = self._get('mask', lambda: nifti.read(sf.categories['images']['t2'])[0] > 0)
         return to_eval
@@ -547,12 +573,97 @@ class ComponentsAction(EvalAction):
             writer.writerows(self.list_rows)
 
 
+class BoundaryAction(EvalAction):
+    """EXTENSION (the reference prepares the border shell -- labelhelper.boarder_mask, analysis.py:54-64 -- but has no such action): where the
+    errors and the uncertainty sit relative to the target's boundary, from exact distance transforms on the GPU (evaluation.boundary_table,
+    surface_distance_histograms, boarder_mask).  The uncertainty is prepared exactly like ``UeCurvesAction``'s and ``ComponentsAction``'s,
+    and there is no brain mask.  Files in ``<base_dir>/uncertainty``:
+      eval_boundary_<id>.csv          one row per subject: evaluation.BOUNDARY_TABLE_KEYS, hd, hd95, assd, and the keys of
+                                      evaluation.UE_CURVE_KEYS with the suffix _off_border: the level histogram of the voxels outside the
+                                      target's border shell boarder_mask(target, 1, 1)
+      eval_boundary_pooled_<id>.csv   the same metrics of the SUM of the subjects' tables and off-border histograms (integers: whatever the
+                                      batching or the order; surface distances are per subject and do not pool)
+      eval_boundary_bands_<id>.csv    the pooled table, one row per (side, band): side, band, voxels, errors, unc_sum, unc_err_sum and
+                                      evaluation.BOUNDARY_BAND_KEYS"""
+
+    SURFACE_KEYS = ('hd', 'hd95', 'assd')
+    OFF_BORDER_KEYS = tuple(k + '_off_border' for k in ev.UE_CURVE_KEYS)
+    SUBJECT_KEYS = ev.BOUNDARY_TABLE_KEYS + SURFACE_KEYS + OFF_BORDER_KEYS
+    POOLED_KEYS = ev.BOUNDARY_TABLE_KEYS + OFF_BORDER_KEYS
+
+    def __init__(self, levels, bands, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        super().__init__()
+        self.levels, self.bands = int(levels), int(bands)
+        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
+            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        if not 1 <= self.bands <= ev._lib.RCU_BOUNDARY_MAX_BANDS:
+            raise ValueError('bands must be in 1..{}, got {}'.format(ev._lib.RCU_BOUNDARY_MAX_BANDS, bands))
+        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
+        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.pooled_table = self.pooled_hist = None
+
+    def setup_eval(self, eval_data):
+        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
+        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
+        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
+                                                                self.rescale_confidence, self.rescale_sigma, mm)
+        self.load_params = Loader.Params(eval_data.confidence_entry)
+        hook = WriteCsvHook(os.path.join(self.out_dir, BOUNDARY_PLACEHOLDER.format(self.id_)), entries=self.SUBJECT_KEYS)
+        self.eval_cases = [EvalCase(None, hook)]
+        self.pooled_table = np.zeros((2, self.bands + 1), dtype=ev.BOUNDARY_DTYPE)
+        self.pooled_hist = np.zeros((4, self.levels), dtype=np.uint64)
+
+    @staticmethod
+    def _row(table, off_border_hist):
+        metrics = ev.boundary_metrics(table)
+        row = {k: metrics[k] for k in ev.BOUNDARY_TABLE_KEYS}
+        curves = ev.ue_curve_metrics(off_border_hist)
+        row.update({k + '_off_border': curves[k] for k in ev.UE_CURVE_KEYS})
+        return row
+
+    def record_boundary(self, table, surface_hist, off_border_hist, subject_name):
+        """One subject's boundary table, surface histograms and off-border level histogram: its row, and its share of the pooled integers."""
+        row = self._row(table, off_border_hist)
+        surface = ev.surface_distance_metrics(surface_hist)
+        row.update({k: surface[k] for k in self.SURFACE_KEYS})
+        self.eval_cases[0].record({k: row[k] for k in self.SUBJECT_KEYS}, subject_name, self.id_)
+        self.pooled_table = ev.add_boundary_tables([self.pooled_table, table])
+        self.pooled_hist += np.asarray(off_border_hist, dtype=np.uint64)
+
+    def eval_subject(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        if self.prepare:
+            to_eval = self.prepare(to_eval)
+        pr, tg, unc = to_eval['prediction'], to_eval['target'], to_eval['uncertainty']
+        _, shell = ev.boarder_mask(tg, 1, 1)
+        self.record_boundary(ev.boundary_table(pr, tg, unc, bands=self.bands)[0], ev.surface_distance_histograms(pr, tg)[0],
+                             ev.uncertainty_histogram(pr, tg, unc, self.levels, mask=~shell)[0], sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        pooled = self._row(self.pooled_table, self.pooled_hist)
+        with open(os.path.join(self.out_dir, BOUNDARY_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id'] + list(self.POOLED_KEYS))
+            writer.writerow([self.id_] + [pooled[k] for k in self.POOLED_KEYS])
+        bands = ev.boundary_metrics(self.pooled_table)
+        with open(os.path.join(self.out_dir, BOUNDARY_BANDS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['side', 'band'] + list(ev.BOUNDARY_DTYPE.names) + list(ev.BOUNDARY_BAND_KEYS))
+            for side in range(2):
+                for band in range(self.bands + 1):
+                    writer.writerow([side, band] + [int(self.pooled_table[side, band][k]) for k in ev.BOUNDARY_DTYPE.names] +
+                                    [float(bands[k][side, band]) for k in ev.BOUNDARY_BAND_KEYS])
+
+
 ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
-def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26):
-    """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels) and 'components'
-    (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice)."""
+def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10):
+    """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
+    (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice) and 'boundary' (``bands``: its distance bands, 1..64;
+    ``levels``: of its off-border level histogram)."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -567,6 +678,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'components':
             actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'boundary':
+            actions.append(BoundaryAction(levels, bands, base_dir, 'subject', 'global', min_max_dir))
     return actions
 
 
@@ -634,6 +747,8 @@ class _LoaderAhead:
             union.need_target |= bool(p.need_target)
             union.need_prediction |= bool(p.need_prediction)
             union.need_t2_mask |= bool(p.need_t2_mask)
+            union.need_gt_dist_and_boarder |= bool(getattr(p, 'need_gt_dist_and_boarder', False))
+            union.need_prediction_dist_and_boarder |= bool(getattr(p, 'need_prediction_dist_and_boarder', False))
         self.reader = _ReadAhead(subject_files, union, depth)
         self.subject_files = subject_files
 
@@ -652,22 +767,24 @@ class _LoaderAhead:
 
 def _fusable(entry, actions):
     """The fused loop covers the runs whose confidence entry IS the probability map (baseline, baseline_mc, center, center_mc, ensemble:
-    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script, 'ue_curves' and 'components'."""
+    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script, 'ue_curves', 'components' and 'boundary'."""
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
-            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction) for a in actions) and
+            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction)
+                for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
 
 def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
     list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
-    by a ComponentsAction, which holds the `connectivity`)."""
+    by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
            (['ue'] if (CorrectionAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
            (['ue_hist'] if UeCurvesAction in by_type else []) + \
-           (['components'] if ComponentsAction in by_type else [])
+           (['components'] if ComponentsAction in by_type else []) + \
+           (['boundary'] if BoundaryAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -707,6 +824,8 @@ def record_subject(actions, subject, res, slot, n_dim):
             action.record_histogram(res['ue_hist'][slot], subject)
         elif isinstance(action, ComponentsAction):
             action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
+        elif isinstance(action, BoundaryAction):
+            action.record_boundary(*res['boundary'][slot], subject)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -716,7 +835,8 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     fn are ece_dice's confusion matrix), min / max -- and the results fanned out to the actions' CSV hooks in subject order.  The rows are
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
     want, thresholds, want_mask = metrics_wanted(actions)
-    levels = next((a.levels for a in actions if isinstance(a, UeCurvesAction)), ev.UE_LEVELS)
+    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction))), ev.UE_LEVELS)
+    bands = next((a.bands for a in actions if isinstance(a, BoundaryAction)), 10)
     connectivity = next((a.connectivity for a in actions if isinstance(a, ComponentsAction)), 26)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
     files = entry.subject_files
@@ -744,7 +864,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity)
+            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)
@@ -774,14 +894,14 @@ class _Done:
 
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
-                  connectivity=26):
+                  connectivity=26, bands=10):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
-    'components' actions; ``connectivity``: of the 'components' action."""
-    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity)
+    'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action."""
+    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

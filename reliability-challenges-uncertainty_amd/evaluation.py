@@ -188,7 +188,7 @@ class SubjectBatch:
                     dev[s_].copy_(host[s_], non_blocking=True)
         self._staged = set()
 
-    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26):
+    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26, bands=10):
         """-> dict of host arrays over the ``used`` subjects: ``min`` / ``max`` (float32), ``hist`` = (count, sum_conf, sum_pos) of the
         reliability histogram inside the mask, ``counts`` [used, len(thresholds), 8] of the uncertainty-error action on the WHOLE volume
         (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice) and, with
@@ -196,7 +196,10 @@ class SubjectBatch:
         volume like the counts.  One launch per scan for all subjects, one synchronisation for all results.  With ``'components'`` in
         ``want``, ``components`` = per subject the pair (table of the prediction's components with the target as the other map and the
         entropy of p as the uncertainty, table of the target's components with the prediction as the other map) of ``component_table``,
-        labelled under ``connectivity`` in the shapes the subjects were put with -- from the resident maps, all subjects in one call."""
+        labelled under ``connectivity`` in the shapes the subjects were put with -- from the resident maps, all subjects in one call.  With
+        ``'boundary'`` in ``want``, ``boundary`` = per subject the triple (``boundary_table`` of ``bands`` bands with the entropy of p as the
+        uncertainty, ``surface_distance_histograms``, the level histogram ``ue_hist_off_border`` [4, levels] of the voxels outside the
+        target's border shell ``boarder_mask(target, 1, 1)``), all subjects of one shape in one call per kernel."""
         v = self.used
         lib = _lib.load()
         out, keep = {}, []
@@ -224,6 +227,8 @@ class SubjectBatch:
             keep.append(('ue_hist', ue_hist))
         if 'components' in want:
             out['components'] = self._component_tables(v, connectivity)
+        if 'boundary' in want:
+            out['boundary'] = self._boundary(v, _check_bands(bands), levels)
         host = {k: t.cpu() for k, t in keep}          # (the first .cpu() waits for the stream: the others are ready by then)
         if 'minmax' in host:
             mm = host['minmax'].numpy()
@@ -253,6 +258,20 @@ class SubjectBatch:
             for k, slot in enumerate(slots):
                 pairs[slot] = (of_prediction[k], of_target[k])
         return pairs
+
+    def _boundary(self, v, bands, levels):
+        shapes = [self.shapes[slot] for slot in range(v)]
+        triples = [None] * v
+        for shape in sorted(set(shapes)):       # (one call per shape, as _component_tables)
+            slots = [slot for slot in range(v) if shapes[slot] == shape]
+            if len(slots) == v:
+                p, pr, tg = self.p[:v], self.prediction[:v], self.target[:v]
+            else:
+                index = torch.as_tensor(slots, device=self.device)
+                p, pr, tg = self.p[index], self.prediction[index], self.target[index]
+            for k, triple in enumerate(_boundary_on_device(p, pr, tg, _volume_dims(shape), bands, levels)):
+                triples[slots[k]] = triple
+        return triples
 
 
 # ---------------------------------------------------------------------- uncertainty-error counts
@@ -615,6 +634,253 @@ def component_metrics(pred_table, target_table, levels=UE_LEVELS):
     out['dice_filtered_max'] = best
     out['dice_filtered_max_threshold'] = best_k / levels
     return out
+
+
+# ------------------------------------------------ boundary-aware metrics from an exact distance transform on the GPU (EXTENSION)
+# one cell per (side of the target's boundary, distance band) (include/rcu.h, rcu_boundary_cell)
+BOUNDARY_DTYPE = np.dtype([('voxels', '<u8'), ('errors', '<u8'), ('unc_sum', '<u8'), ('unc_err_sum', '<u8')])
+BOUNDARY_BAND_KEYS = ('error_rate', 'mean_uncertainty', 'mean_uncertainty_of_errors', 'mean_uncertainty_of_correct')
+BOUNDARY_TABLE_KEYS = ('n', 'n_border', 'errors', 'errors_border_share', 'uncertainty_border_share')
+SURFACE_DISTANCE_KEYS = ('hd', 'hd95', 'assd', 'n_surface_prediction', 'n_surface_target')
+EDT_NONE = _lib.RCU_EDT_NONE       # the squared distance where the volume has no feature voxel
+
+
+def _edt_on_device(mask, dims, zero_is_feature):
+    """mask: device uint8 [V, n] -> device int32 [V, n] holding the uint32 squared distances (torch has no arithmetic on uint32: the bits)."""
+    v, n = mask.shape
+    out = torch.empty((v, n), device=mask.device, dtype=torch.int32)
+    _lib.check(_lib.load().rcu_edt_sq(_lib.ptr(mask), dims[0], dims[1], dims[2], v, int(zero_is_feature), _lib.ptr(out), _lib.current_stream()))
+    return out
+
+
+def distance_transform_sq(mask, n_volumes=1, invert=False):
+    """Exact squared Euclidean distance transform on the GPU -> uint32 array of the mask's shape: per voxel the squared distance (unit
+    spacing) to the nearest voxel of the same volume where ``mask`` is 0 -- ``scipy.ndimage.distance_transform_edt(mask) ** 2``, as an exact
+    integer -- or, with ``invert``, to the nearest voxel where it is not 0 (the transform of ``~mask``).  A volume without such a voxel is
+    ``EDT_NONE`` everywhere (scipy's values there are an artefact and are not copied).  The mask's own shape gives depth / height / width
+    (2-D arrays: the 2-D transform); ``n_volumes`` > 1 treats the leading axis as independent volumes.  A device tensor gets a device
+    tensor (int32 holding the uint32 bits where torch lacks uint32)."""
+    dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
+    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    out = _edt_on_device(m, dims, 0 if invert else 1).reshape(tuple(mask.shape))
+    if isinstance(mask, torch.Tensor) and mask.is_cuda:
+        return out.view(torch.uint32) if hasattr(torch, 'uint32') else out
+    return out.cpu().numpy().view(np.uint32)
+
+
+def _border_on_device(d_in, d_out, distance_in, distance_out, want_distance):
+    """Device squared distances [V, n] -> (device float64 distance or None, device uint8 border mask)."""
+    mask = torch.empty(d_in.shape, device=d_in.device, dtype=torch.uint8)
+    distance = torch.empty(d_in.shape, device=d_in.device, dtype=torch.float64) if want_distance else None
+    _lib.check(_lib.load().rcu_border_mask(_lib.ptr(d_in), _lib.ptr(d_out), d_in.numel(), int(distance_in), int(distance_out), _lib.ptr(mask),
+                                           _lib.ptr(distance), _lib.current_stream()))
+    return distance, mask
+
+
+def boarder_mask(binary_label_map, distance_in, distance_out):
+    """common/utils/labelhelper.py:12-20 on the GPU -> ``(distance float64, mask bool)``: the distance to the label map's boundary (inside: to
+    the nearest background voxel, outside: to the nearest foreground voxel) and the shell of the voxels at most ``distance_in`` inside and
+    ``distance_out`` outside of it.  From two exact squared transforms: the mask is compared in integers, the distance is the correctly
+    rounded float64 square root -- the reference's arrays bit for bit wherever the map holds both classes.  Where it holds one class only
+    the reference's values are scipy's artefact; here the distance is ``inf`` and the mask empty."""
+    dims = _volume_dims(binary_label_map.shape)
+    m = _to_dev(binary_label_map, torch.uint8).reshape(1, -1)
+    distance, mask = _border_on_device(_edt_on_device(m, dims, 1), _edt_on_device(m, dims, 0), distance_in, distance_out, True)
+    distance, mask = distance.reshape(tuple(binary_label_map.shape)), mask.reshape(tuple(binary_label_map.shape)).to(torch.bool)
+    if isinstance(binary_label_map, torch.Tensor) and binary_label_map.is_cuda:
+        return distance, mask
+    return distance.cpu().numpy(), mask.cpu().numpy()
+
+
+def _check_bands(bands):
+    bands = int(bands)
+    if not 1 <= bands <= _lib.RCU_BOUNDARY_MAX_BANDS:
+        raise ValueError('bands must be in 1..{}, got {}'.format(_lib.RCU_BOUNDARY_MAX_BANDS, bands))
+    return bands
+
+
+def _uncertainty_source(uncertainty, foreground_probability, n_volumes):
+    """-> (RCU_CC_UNC_* kind, device map [V, n] or None) of an uncertainty given as a float map, an ``EntropyOfProbability`` or a probability map."""
+    if foreground_probability is not None:
+        if uncertainty is not None:
+            raise ValueError('give uncertainty or foreground_probability, not both')
+        return _lib.RCU_CC_UNC_P, _to_dev(foreground_probability, torch.float32).reshape(n_volumes, -1)
+    if isinstance(uncertainty, EntropyOfProbability):
+        return _lib.RCU_CC_UNC_P, _to_dev(uncertainty.foreground_probability, torch.float32).reshape(n_volumes, -1)
+    if uncertainty is None:
+        return _lib.RCU_CC_UNC_NONE, None
+    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
+    return (_lib.RCU_CC_UNC_F64 if is64 else _lib.RCU_CC_UNC_F32), _to_dev(uncertainty, torch.float64 if is64 else torch.float32).reshape(n_volumes, -1)
+
+
+def _boundary_table_on_device(prediction, target, d_in, d_out, unc_kind, unc, bands):
+    """Device arrays [V, n] -> device uint8 buffer of V x 2 x (bands + 1) cells; asynchronous on the current stream."""
+    v, n = target.shape
+    table = torch.empty(v * 2 * (bands + 1) * BOUNDARY_DTYPE.itemsize, device=target.device, dtype=torch.uint8)
+    _lib.check(_lib.load().rcu_boundary_table(_lib.ptr(prediction), _lib.ptr(target), _lib.ptr(d_in), _lib.ptr(d_out), _lib.ptr(unc), int(unc_kind),
+                                              n, v, bands, _lib.ptr(table), _lib.current_stream()))
+    return table
+
+
+def boundary_table(prediction, target, uncertainty=None, foreground_probability=None, bands=10, n_volumes=1):
+    """Structured array (BOUNDARY_DTYPE) ``[n_volumes, 2, bands + 1]``: the voxels of every volume by side of the TARGET's boundary (0:
+    background, 1: foreground) and distance band -- with d the squared distance to the nearest voxel of the other class, band k < ``bands``
+    holds k^2 < d <= (k + 1)^2 and the last band d > bands^2 (and every voxel of a target with one class only).  Band 0 of both sides
+    together is ``boarder_mask(target, 1, 1)``'s shell.  Per cell ``voxels``, ``errors`` (prediction and target disagree), ``unc_sum`` = the
+    sum of q(u) over its voxels and ``unc_err_sum`` over its error voxels, q(u) = rint(clamp(u, 0, 1) * 2^24) as in ``component_table``.
+    Integer sums: the same bits whatever the batching.  The uncertainty is a float64 / float32 map or an ``EntropyOfProbability``
+    (``uncertainty``), or a float32 foreground-probability map whose entropy is computed in registers (``foreground_probability``)."""
+    bands = _check_bands(bands)
+    dims = _volume_dims(_split_volumes(target.shape, n_volumes))
+    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
+    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
+    if pr.shape != tg.shape:
+        raise ValueError('prediction and target differ in size')
+    kind, u = _uncertainty_source(uncertainty, foreground_probability, n_volumes)
+    if u is not None and u.shape != tg.shape:
+        raise ValueError('target and uncertainty differ in size')
+    table = _boundary_table_on_device(pr, tg, _edt_on_device(tg, dims, 1), _edt_on_device(tg, dims, 0), kind, u, bands)
+    return table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(n_volumes, 2, bands + 1).copy()
+
+
+def _surface_histograms_on_device(prediction, target, dims):
+    """Device uint8 [V, n] label maps -> (device (volume, bin) index pairs of the occupied bins [K, 2], their two counts [K, 2], bins);
+    asynchronous but for the size of the compaction."""
+    v, n = prediction.shape
+    lib = _lib.load()
+    bins = int(lib.rcu_surface_distance_bins(dims[0], dims[1], dims[2]))
+    hist = torch.empty((v, 2, bins), device=prediction.device, dtype=torch.int32)
+    ws = torch.empty(max(lib.rcu_surface_distance_workspace_bytes(n, v), 8), device=prediction.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_surface_distance_hist(_lib.ptr(prediction), _lib.ptr(target), dims[0], dims[1], dims[2], v, _lib.ptr(hist), _lib.ptr(ws),
+                                             _lib.current_stream()))
+    where = ((hist[:, 0] != 0) | (hist[:, 1] != 0)).nonzero()       # [K, 2]: volume, bin -- in ascending order of both
+    return where, hist[where[:, 0], :, where[:, 1]], bins
+
+
+def _surface_histograms_to_host(where, counts, bins, n_volumes):
+    where, counts = where.cpu().numpy(), counts.cpu().numpy().view(np.uint32).astype(np.int64)
+    out = []
+    for v in range(n_volumes):
+        rows = where[:, 0] == v
+        sq = where[rows, 1].astype(np.int64)
+        sq[sq == bins - 1] = EDT_NONE       # the last bin: the other surface is empty
+        out.append((sq, counts[rows, 0].copy(), counts[rows, 1].copy()))
+    return out
+
+
+def surface_distance_histograms(prediction, target, n_volumes=1):
+    """The directed surface distances of two label maps -> per volume ``(sq_values, count_p_to_t, count_t_to_p)``: the distinct squared
+    distances (int64, ascending) with the number of surface voxels of the prediction at that squared distance from the target's surface
+    and of the target's surface voxels from the prediction's.  The surface of a map A is the voxels of A that are face-adjacent to a voxel
+    outside A inside the volume (``A & ~scipy.ndimage.binary_erosion(A, border_value=1)``; medpy's ``border_value=0`` differs only where A
+    touches the volume face).  Where the other surface is empty the squared distance is ``EDT_NONE``, as ``distance_transform_sq``'s."""
+    dims = _volume_dims(_split_volumes(target.shape, n_volumes))
+    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
+    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
+    if pr.shape != tg.shape:
+        raise ValueError('prediction and target differ in size')
+    return _surface_histograms_to_host(*_surface_histograms_on_device(pr, tg, dims), n_volumes)
+
+
+def surface_distance_metrics(hist):
+    """Hausdorff distance, its 95th percentile and the average symmetric surface distance from ONE volume's ``surface_distance_histograms``
+    -> dict with the keys ``SURFACE_DISTANCE_KEYS``.  Host float64 arithmetic on the integers:
+      hd     the square root of the largest squared distance of either direction
+      hd95   ``numpy.percentile(.., 95)`` (linear interpolation) of both directions' distances together, from the counts
+      assd   the sum of sqrt(d^2) * count over both directions, added in ascending d^2, over the number of surface voxels of both
+    All three are NaN if either surface is empty."""
+    import math
+    sq, c_pt, c_tp = hist
+    sq = [int(s_) for s_ in sq]
+    count = [int(a) + int(b) for a, b in zip(c_pt, c_tp)]
+    n_p, n_t = sum(int(a) for a in c_pt), sum(int(b) for b in c_tp)
+    out = {'n_surface_prediction': n_p, 'n_surface_target': n_t}
+    if n_p == 0 or n_t == 0 or any(s_ == EDT_NONE and c for s_, c in zip(sq, count)):
+        out.update(hd=float('nan'), hd95=float('nan'), assd=float('nan'))
+        return out
+    present = [(math.sqrt(s_), c) for s_, c in zip(sq, count) if c]
+    n = n_p + n_t
+    total = 0.0
+    for d, c in present:
+        total += d * c
+    out['hd'] = present[-1][0]
+    out['assd'] = total / n
+    # numpy.percentile's default method: the virtual index (n - 1) * 0.95 between the two order statistics around it, numpy's _lerp
+    virtual = (n - 1) * (95 / 100)
+    lo = int(math.floor(virtual))
+    t = virtual - lo
+    hi = min(lo + 1, n - 1)
+
+    def order_statistic(k):
+        seen = 0
+        for d, c in present:
+            seen += c
+            if k < seen:
+                return d
+        return present[-1][0]
+    a, b = order_statistic(lo), order_statistic(hi)
+    out['hd95'] = b - (b - a) * (1 - t) if t >= 0.5 else a + (b - a) * t
+    return out
+
+
+def boundary_metrics(table):
+    """Host arithmetic on ONE boundary table ``[2, bands + 1]`` (a subject's, or the sum of several subjects': tables add) -> dict with
+      per side and band, float64 ``[2, bands + 1]`` (NaN for an empty denominator): ``error_rate`` = errors / voxels, ``mean_uncertainty`` =
+          unc_sum / (voxels * 2^24), ``mean_uncertainty_of_errors`` = unc_err_sum / (errors * 2^24), ``mean_uncertainty_of_correct`` =
+          (unc_sum - unc_err_sum) / ((voxels - errors) * 2^24)
+      per table: ``n``, ``n_border`` (band 0 of both sides: the border shell), ``errors``, ``errors_border_share`` = the share of the errors
+          that lie in the shell, ``uncertainty_border_share`` = the share of the summed uncertainty that lies there (NaN for 0 / 0)
+    Python integers, every ratio rounded once."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[0] != 2 or t.shape[1] < 2:
+        raise ValueError('expected one boundary table of shape [2, bands + 1], got {}'.format(t.shape))
+    nan = float('nan')
+
+    def ratio(num, den):
+        return num / den if den else nan
+    out = {k: np.full(t.shape, nan, dtype=np.float64) for k in BOUNDARY_BAND_KEYS}
+    n = n_border = errors = errors_border = unc = unc_border = 0
+    for s_ in range(2):
+        for b in range(t.shape[1]):
+            vox, err, us, ues = (int(t[s_, b][k]) for k in ('voxels', 'errors', 'unc_sum', 'unc_err_sum'))
+            out['error_rate'][s_, b] = ratio(err, vox)
+            out['mean_uncertainty'][s_, b] = ratio(us, vox * COMPONENT_UNC_ONE)
+            out['mean_uncertainty_of_errors'][s_, b] = ratio(ues, err * COMPONENT_UNC_ONE)
+            out['mean_uncertainty_of_correct'][s_, b] = ratio(us - ues, (vox - err) * COMPONENT_UNC_ONE)
+            n, errors, unc = n + vox, errors + err, unc + us
+            if b == 0:
+                n_border, errors_border, unc_border = n_border + vox, errors_border + err, unc_border + us
+    out.update(n=n, n_border=n_border, errors=errors, errors_border_share=ratio(errors_border, errors),
+               uncertainty_border_share=ratio(unc_border, unc))
+    return out
+
+
+def add_boundary_tables(tables):
+    """The sum of boundary tables of one shape (integers: whatever the order)."""
+    total = np.zeros(np.shape(tables[0]), dtype=BOUNDARY_DTYPE)
+    for t in tables:
+        for k in BOUNDARY_DTYPE.names:
+            total[k] += t[k]
+    return total
+
+
+def _boundary_on_device(p, prediction, target, dims, bands, levels):
+    """Everything the 'boundary' action needs of a batch of resident subjects of one shape (device arrays [V, n]; p: the float32 foreground
+    probability) -> per volume (boundary table, surface histograms, level histogram off the target's border shell)."""
+    v, n = target.shape
+    lib = _lib.load()
+    d_in, d_out = _edt_on_device(target, dims, 1), _edt_on_device(target, dims, 0)
+    table = _boundary_table_on_device(prediction, target, d_in, d_out, _lib.RCU_CC_UNC_P, p, bands)
+    _, shell = _border_on_device(d_in, d_out, 1, 1, False)
+    off_border = (shell == 0).to(torch.uint8)
+    ue_hist = torch.empty((v, 4, int(levels)), device=target.device, dtype=torch.int64)
+    ws = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(n, v, int(levels)), 8), device=target.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(p), _lib.ptr(prediction), _lib.ptr(target), _lib.ptr(off_border), n, v, int(levels), _lib.ptr(ue_hist),
+                                       _lib.ptr(ws), _lib.current_stream()))
+    surfaces = _surface_histograms_to_host(*_surface_histograms_on_device(prediction, target, dims), v)
+    tables = table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(v, 2, bands + 1)
+    hists = ue_hist.cpu().numpy().view(np.uint64)
+    return [(tables[k].copy(), surfaces[k], hists[k].copy()) for k in range(v)]
 
 
 def _counts(prediction, target, uncertainty, thresholds, mask=None):
