@@ -451,16 +451,6 @@ __global__ __launch_bounds__(CB_THREADS) void unc_counts_kernel(const U* __restr
 // Ascending thresholds: m = #{t : u > th_t} identifies the set of exceeded thresholds (the first m), so one
 // ds_add into the lane's private column [m][cell] records the voxel; count_uncertain[t][cell] = sum_{m > t} col[m][cell]
 // and the base counts are the column sums.  Writes the same partial layout as the general kernel.
-__device__ __forceinline__ void load4(const float* src, float (&q)[4])
-{
-    const float4 v = stream_load(reinterpret_cast<const float4*>(src));
-    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
-}
-__device__ __forceinline__ void load4(const double* src, double (&q)[4])
-{
-    const double2 a = stream_load(reinterpret_cast<const double2*>(src)), b = stream_load(reinterpret_cast<const double2*>(src + 2));
-    q[0] = a.x, q[1] = a.y, q[2] = b.x, q[3] = b.y;
-}
 
 // FROM_P: `unc` is the float32 foreground-probability map itself and "uncertain" is decided by the table of the reference's own
 // float32 -> {uncertain, not} sets (UePCell below): no entropy map, no log.

@@ -28,7 +28,7 @@
 // (u32 add / max, u64 add): exact whatever the order.
 #include "../../include/rcu.h"
 #include "rcu_kernels.h"
-#include "rcu_entropy.h"
+#include "rcu_unc_source.h"
 
 #include <string>
 #include <type_traits>
@@ -303,9 +303,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_relabel_kernel(const int* label
 }
 
 // ---- the table
-// q(u) = rint(clamp(u, 0, 1) * 2^24) in float64, ties to even, NaN -> 0 (fmax(NaN, 0) = 0)
-__device__ __forceinline__ unsigned quantise(double u) { return (unsigned)rint(fmin(fmax(u, 0.0), 1.0) * 16777216.0); }
-
 struct Entry {            // rcu_cc_entry
     int root;
     unsigned voxels, other_voxels, unc_max;
@@ -333,9 +330,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_table_kernel(const int* __restr
     bool oth = false;
     if (fg) {
         oth = other != nullptr && other[off + i] != 0;
-        if constexpr (KIND == RCU_CC_UNC_F32) q = quantise((double)reinterpret_cast<const float*>(unc)[off + i]);
-        if constexpr (KIND == RCU_CC_UNC_F64) q = quantise(reinterpret_cast<const double*>(unc)[off + i]);
-        if constexpr (KIND == RCU_CC_UNC_P) q = quantise(normalised_entropy_of_p(reinterpret_cast<const float*>(unc)[off + i]));
+        q = quantised_unc<KIND>(unc, off + i);
         if (l == (int)i + 1) table[row].root = (int)i;
     }
     const unsigned long long fg_lanes = __ballot(fg);
@@ -379,7 +374,6 @@ Dims dims_for(int d, int h, int w)
 }
 
 unsigned scan_blocks(size_t n) { return (unsigned)((n + CC_SCAN_BLOCK - 1) / CC_SCAN_BLOCK); }
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the workspace: [rank: n_volumes x n u32][block_first: n_volumes x scan_blocks u32][vol_first: n_volumes + 1 u32]
 struct Workspace {
@@ -396,19 +390,6 @@ Workspace carve(void* ws, size_t n, int n_volumes)
     w.vol_first = reinterpret_cast<unsigned*>(p);
     return w;
 }
-
-// n_per_volume < 2^31 - 1, n_volumes in 1..65535, the batch below 2^32 voxels (ranks are u32)
-int check_batch(const std::string& f, size_t n, int n_volumes)
-{
-    if (n == 0 || n >= (size_t)0x7fffffff) return report_error(RCU_ERR_INVALID, f + "n_per_volume must be in 1..2^31-2, got " + std::to_string(n));
-    if (n_volumes <= 0 || n_volumes > CC_MAX_VOLUMES)
-        return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(CC_MAX_VOLUMES) + ", got " + std::to_string(n_volumes));
-    if ((unsigned long long)n * (unsigned long long)n_volumes > 0xffffffffull)
-        return report_error(RCU_ERR_INVALID, f + "n_per_volume * n_volumes must be below 2^32");
-    return RCU_OK;
-}
-
-int hip_failed(const char* fn, hipError_t e) { return report_error(RCU_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e)); }
 
 }  // namespace
 }  // namespace rcu
@@ -433,8 +414,7 @@ extern "C" int rcu_cc_label(const uint8_t* mask_dev, int depth, int height, int 
     if (depth < 1 || height < 1 || width < 1) return report_error(RCU_ERR_INVALID, f + "depth, height and width must be >= 1");
     const unsigned long long n64 = (unsigned long long)depth * (unsigned long long)height * (unsigned long long)width;
     if (n64 >= 0x7fffffffull) return report_error(RCU_ERR_INVALID, f + "a volume must have fewer than 2^31 - 1 voxels");
-    if (n_volumes <= 0 || n_volumes > CC_MAX_VOLUMES)
-        return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(CC_MAX_VOLUMES) + ", got " + std::to_string(n_volumes));
+    if (int st = check_n_volumes(f, n_volumes, CC_MAX_VOLUMES)) return st;
     if (!mask_dev) return report_error(RCU_ERR_INVALID, f + "null mask_dev");
     if (!labels_dev) return report_error(RCU_ERR_INVALID, f + "null labels_dev");
     const size_t n = (size_t)n64;
@@ -457,9 +437,7 @@ extern "C" int rcu_cc_label(const uint8_t* mask_dev, int depth, int height, int 
 
 extern "C" size_t rcu_cc_workspace_bytes(size_t n_per_volume, int n_volumes)
 {
-    if (n_per_volume == 0 || n_per_volume >= (size_t)0x7fffffff || n_volumes <= 0 || n_volumes > CC_MAX_VOLUMES ||
-        (unsigned long long)n_per_volume * (unsigned long long)n_volumes > 0xffffffffull)
-        return 0;
+    if (!batch_ok(n_per_volume, n_volumes, CC_MAX_VOLUMES)) return 0;
     return round256((size_t)n_volumes * n_per_volume * sizeof(unsigned)) + round256((size_t)n_volumes * scan_blocks(n_per_volume) * sizeof(unsigned)) +
            round256(((size_t)n_volumes + 1) * sizeof(unsigned));
 }
@@ -467,7 +445,7 @@ extern "C" size_t rcu_cc_workspace_bytes(size_t n_per_volume, int n_volumes)
 extern "C" int rcu_cc_compact(const int32_t* labels_dev, size_t n_per_volume, int n_volumes, uint32_t* counts_dev, void* workspace_dev, void* stream)
 {
     const std::string f = "rcu_cc_compact: ";
-    if (int st = check_batch(f, n_per_volume, n_volumes)) return st;
+    if (int st = check_batch(f, n_per_volume, n_volumes, CC_MAX_VOLUMES)) return st;
     if (!labels_dev) return report_error(RCU_ERR_INVALID, f + "null labels_dev");
     if (!counts_dev) return report_error(RCU_ERR_INVALID, f + "null counts_dev");
     if (!workspace_dev) return report_error(RCU_ERR_INVALID, f + "null workspace_dev");
@@ -484,7 +462,7 @@ extern "C" int rcu_cc_compact(const int32_t* labels_dev, size_t n_per_volume, in
 extern "C" int rcu_cc_relabel(const int32_t* labels_dev, size_t n_per_volume, int n_volumes, const void* workspace_dev, int32_t* dense_dev, void* stream)
 {
     const std::string f = "rcu_cc_relabel: ";
-    if (int st = check_batch(f, n_per_volume, n_volumes)) return st;
+    if (int st = check_batch(f, n_per_volume, n_volumes, CC_MAX_VOLUMES)) return st;
     if (!labels_dev) return report_error(RCU_ERR_INVALID, f + "null labels_dev");
     if (!workspace_dev) return report_error(RCU_ERR_INVALID, f + "null workspace_dev");
     if (!dense_dev) return report_error(RCU_ERR_INVALID, f + "null dense_dev");
@@ -499,11 +477,8 @@ extern "C" int rcu_cc_table(const int32_t* labels_dev, const uint8_t* other_dev,
                             const void* workspace_dev, rcu_cc_entry* table_dev, size_t table_entries, void* stream)
 {
     const std::string f = "rcu_cc_table: ";
-    if (int st = check_batch(f, n_per_volume, n_volumes)) return st;
-    if (unc_kind != RCU_CC_UNC_NONE && unc_kind != RCU_CC_UNC_F32 && unc_kind != RCU_CC_UNC_F64 && unc_kind != RCU_CC_UNC_P)
-        return report_error(RCU_ERR_INVALID, f + "unc_kind must be one of RCU_CC_UNC_NONE, _F32, _F64, _P, got " + std::to_string(unc_kind));
-    if ((unc_kind == RCU_CC_UNC_NONE) != (unc_dev == nullptr))
-        return report_error(RCU_ERR_INVALID, f + "unc_dev must be null for RCU_CC_UNC_NONE and only then");
+    if (int st = check_batch(f, n_per_volume, n_volumes, CC_MAX_VOLUMES)) return st;
+    if (int st = check_unc_source(f, unc_kind, unc_dev)) return st;
     if (!labels_dev) return report_error(RCU_ERR_INVALID, f + "null labels_dev");
     if (!workspace_dev) return report_error(RCU_ERR_INVALID, f + "null workspace_dev");
     if (table_entries == 0) return RCU_OK;      // no component in the batch: nothing to fill
@@ -515,12 +490,9 @@ extern "C" int rcu_cc_table(const int32_t* labels_dev, const uint8_t* other_dev,
     if (e != hipSuccess) return hip_failed("rcu_cc_table", e);
     const dim3 grid((unsigned)((n_per_volume + CC_THREADS - 1) / CC_THREADS), n_volumes);
     Entry* t = reinterpret_cast<Entry*>(table_dev);
-    switch (unc_kind) {
-    case RCU_CC_UNC_F32: hipLaunchKernelGGL(cc_table_kernel<RCU_CC_UNC_F32>, grid, dim3(CC_THREADS), 0, s, labels_dev, other_dev, unc_dev, n_per_volume, w.rank, t, table_entries); break;
-    case RCU_CC_UNC_F64: hipLaunchKernelGGL(cc_table_kernel<RCU_CC_UNC_F64>, grid, dim3(CC_THREADS), 0, s, labels_dev, other_dev, unc_dev, n_per_volume, w.rank, t, table_entries); break;
-    case RCU_CC_UNC_P: hipLaunchKernelGGL(cc_table_kernel<RCU_CC_UNC_P>, grid, dim3(CC_THREADS), 0, s, labels_dev, other_dev, unc_dev, n_per_volume, w.rank, t, table_entries); break;
-    default: hipLaunchKernelGGL(cc_table_kernel<RCU_CC_UNC_NONE>, grid, dim3(CC_THREADS), 0, s, labels_dev, other_dev, unc_dev, n_per_volume, w.rank, t, table_entries); break;
-    }
+    with_unc_kind(unc_kind, [&](auto kind) {
+        hipLaunchKernelGGL(cc_table_kernel<decltype(kind)::value>, grid, dim3(CC_THREADS), 0, s, labels_dev, other_dev, unc_dev, n_per_volume, w.rank, t, table_entries);
+    });
     e = hipGetLastError();
     return e == hipSuccess ? RCU_OK : hip_failed("rcu_cc_table", e);
 }

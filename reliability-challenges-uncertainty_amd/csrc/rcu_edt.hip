@@ -19,7 +19,7 @@
 // alone, whatever the slab width or the batching.
 #include "../../include/rcu.h"
 #include "rcu_kernels.h"
-#include "rcu_entropy.h"
+#include "rcu_unc_source.h"
 
 #include <string>
 
@@ -128,8 +128,6 @@ __global__ __launch_bounds__(EDT_THREADS) void border_mask_kernel(const unsigned
 }
 
 // ---- the boundary table
-__device__ __forceinline__ unsigned quantise(double u) { return (unsigned)rint(fmin(fmax(u, 0.0), 1.0) * 16777216.0); }      // rcu_cc_table's q
-
 // band of the squared distance d: #{k in 1..bands : k^2 < d} = min(bands, floor(sqrt(d - 1))), in integers
 __device__ __forceinline__ int band_of(unsigned d, int bands)
 {
@@ -172,9 +170,7 @@ __global__ __launch_bounds__(EDT_THREADS) void boundary_table_kernel(const uint8
             const unsigned a = d_in[off + i], b = d_out[off + i];
             const int band = (a == NONE || b == NONE || a > NONE - b) ? bands : band_of(a + b, bands);
             key = (tg ? bands + 1 : 0) + band;
-            if constexpr (KIND == RCU_CC_UNC_F32) q = quantise((double)reinterpret_cast<const float*>(unc)[off + i]);
-            if constexpr (KIND == RCU_CC_UNC_F64) q = quantise(reinterpret_cast<const double*>(unc)[off + i]);
-            if constexpr (KIND == RCU_CC_UNC_P) q = quantise(normalised_entropy_of_p(reinterpret_cast<const float*>(unc)[off + i]));
+            q = quantised_unc<KIND>(unc, off + i);
         }
         // one group per distinct key of the wave: the lanes that share the first remaining lane's key are combined, one lane adds them in LDS
         unsigned long long remaining = __ballot(in);
@@ -254,8 +250,6 @@ __global__ __launch_bounds__(EDT_THREADS) void surface_hist_kernel(const uint8_t
 }
 
 // ---- host side
-int hip_failed(const char* fn, hipError_t e) { return report_error(RCU_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e)); }
-
 int check_volume(const std::string& f, int depth, int height, int width, int n_volumes)
 {
     const int extent[3] = {depth, height, width};
@@ -265,19 +259,8 @@ int check_volume(const std::string& f, int depth, int height, int width, int n_v
             return report_error(RCU_ERR_INVALID, f + name[a] + " must be in 1.." + std::to_string(EDT_MAX_EXTENT) + ", got " + std::to_string(extent[a]));
     const unsigned long long n = (unsigned long long)depth * (unsigned long long)height * (unsigned long long)width;
     if (n >= 0x7fffffffull) return report_error(RCU_ERR_INVALID, f + "a volume (depth * height * width) must have fewer than 2^31 - 1 voxels");
-    if (n_volumes < 1 || n_volumes > EDT_MAX_VOLUMES)
-        return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(EDT_MAX_VOLUMES) + ", got " + std::to_string(n_volumes));
-    if (n * (unsigned long long)n_volumes > 0xffffffffull) return report_error(RCU_ERR_INVALID, f + "n_per_volume * n_volumes must be below 2^32");
-    return RCU_OK;
-}
-
-int check_batch(const std::string& f, size_t n, int n_volumes)
-{
-    if (n == 0 || n >= (size_t)0x7fffffff) return report_error(RCU_ERR_INVALID, f + "n_per_volume must be in 1..2^31-2, got " + std::to_string(n));
-    if (n_volumes < 1 || n_volumes > EDT_MAX_VOLUMES)
-        return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(EDT_MAX_VOLUMES) + ", got " + std::to_string(n_volumes));
-    if ((unsigned long long)n * (unsigned long long)n_volumes > 0xffffffffull)
-        return report_error(RCU_ERR_INVALID, f + "n_per_volume * n_volumes must be below 2^32");
+    if (int st = check_n_volumes(f, n_volumes, EDT_MAX_VOLUMES)) return st;
+    if (!batch_total_ok((size_t)n, n_volumes)) return report_error(RCU_ERR_INVALID, f + "n_per_volume * n_volumes must be below 2^32");
     return RCU_OK;
 }
 
@@ -309,8 +292,6 @@ void launch_edt(const uint8_t* mask, int d, int h, int w, int n_volumes, int zer
     launch_lines(out, h, (size_t)w, d, (size_t)h * w, w, n, n_volumes, s);      // along the height: one slice per outer position
     launch_lines(out, d, (size_t)h * w, h, (size_t)w, w, n, n_volumes, s);      // along the depth: one row of the slice per outer position
 }
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace rcu
@@ -362,12 +343,9 @@ extern "C" int rcu_boundary_table(const uint8_t* prediction_dev, const uint8_t* 
                                   void* stream)
 {
     const std::string f = "rcu_boundary_table: ";
-    if (int st = check_batch(f, n_per_volume, n_volumes)) return st;
+    if (int st = check_batch(f, n_per_volume, n_volumes, EDT_MAX_VOLUMES)) return st;
     if (bands < 1 || bands > BT_MAX_BANDS) return report_error(RCU_ERR_INVALID, f + "bands must be in 1.." + std::to_string(BT_MAX_BANDS) + ", got " + std::to_string(bands));
-    if (unc_kind != RCU_CC_UNC_NONE && unc_kind != RCU_CC_UNC_F32 && unc_kind != RCU_CC_UNC_F64 && unc_kind != RCU_CC_UNC_P)
-        return report_error(RCU_ERR_INVALID, f + "unc_kind must be one of RCU_CC_UNC_NONE, _F32, _F64, _P, got " + std::to_string(unc_kind));
-    if ((unc_kind == RCU_CC_UNC_NONE) != (unc_dev == nullptr))
-        return report_error(RCU_ERR_INVALID, f + "unc_dev must be null for RCU_CC_UNC_NONE and only then");
+    if (int st = check_unc_source(f, unc_kind, unc_dev)) return st;
     if (!prediction_dev) return report_error(RCU_ERR_INVALID, f + "null prediction_dev");
     if (!target_dev) return report_error(RCU_ERR_INVALID, f + "null target_dev");
     if (!d_in_dev) return report_error(RCU_ERR_INVALID, f + "null d_in_dev");
@@ -379,12 +357,9 @@ extern "C" int rcu_boundary_table(const uint8_t* prediction_dev, const uint8_t* 
     const size_t per_group = (size_t)BT_ROUNDS * EDT_THREADS;
     const dim3 grid((unsigned)((n_per_volume + per_group - 1) / per_group), n_volumes);
     Cell* t = reinterpret_cast<Cell*>(table_dev);
-    switch (unc_kind) {
-    case RCU_CC_UNC_F32: hipLaunchKernelGGL(boundary_table_kernel<RCU_CC_UNC_F32>, grid, dim3(EDT_THREADS), 0, s, prediction_dev, target_dev, d_in_dev, d_out_dev, unc_dev, n_per_volume, bands, t); break;
-    case RCU_CC_UNC_F64: hipLaunchKernelGGL(boundary_table_kernel<RCU_CC_UNC_F64>, grid, dim3(EDT_THREADS), 0, s, prediction_dev, target_dev, d_in_dev, d_out_dev, unc_dev, n_per_volume, bands, t); break;
-    case RCU_CC_UNC_P: hipLaunchKernelGGL(boundary_table_kernel<RCU_CC_UNC_P>, grid, dim3(EDT_THREADS), 0, s, prediction_dev, target_dev, d_in_dev, d_out_dev, unc_dev, n_per_volume, bands, t); break;
-    default: hipLaunchKernelGGL(boundary_table_kernel<RCU_CC_UNC_NONE>, grid, dim3(EDT_THREADS), 0, s, prediction_dev, target_dev, d_in_dev, d_out_dev, unc_dev, n_per_volume, bands, t); break;
-    }
+    with_unc_kind(unc_kind, [&](auto kind) {
+        hipLaunchKernelGGL(boundary_table_kernel<decltype(kind)::value>, grid, dim3(EDT_THREADS), 0, s, prediction_dev, target_dev, d_in_dev, d_out_dev, unc_dev, n_per_volume, bands, t);
+    });
     e = hipGetLastError();
     return e == hipSuccess ? RCU_OK : hip_failed("rcu_boundary_table", e);
 }
@@ -399,9 +374,7 @@ extern "C" size_t rcu_surface_distance_bins(int depth, int height, int width)
 // the workspace: [surface of the prediction: n_volumes x n u8][surface of the target: the same][distances: n_volumes x n u32]
 extern "C" size_t rcu_surface_distance_workspace_bytes(size_t n_per_volume, int n_volumes)
 {
-    if (n_per_volume == 0 || n_per_volume >= (size_t)0x7fffffff || n_volumes < 1 || n_volumes > EDT_MAX_VOLUMES ||
-        (unsigned long long)n_per_volume * (unsigned long long)n_volumes > 0xffffffffull)
-        return 0;
+    if (!batch_ok(n_per_volume, n_volumes, EDT_MAX_VOLUMES)) return 0;
     const size_t all = n_per_volume * (size_t)n_volumes;
     return 2 * round256(all) + round256(all * sizeof(unsigned));
 }

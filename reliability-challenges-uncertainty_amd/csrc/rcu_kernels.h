@@ -6,10 +6,35 @@
 
 #include <string>
 
+#include "../../include/rcu.h"
+
 namespace rcu {
 
 // rcu_last_error() of the calling thread := msg; returns code (the entry points of the other translation units report through it, rcu_api.hip)
 int report_error(int code, const std::string& msg);
+
+// host helpers of the evaluation extensions' entry points (rcu_unc_hist.hip, rcu_cc.hip, rcu_edt.hip)
+inline int hip_failed(const char* fn, hipError_t e) { return report_error(RCU_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e)); }
+inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline int check_n_volumes(const std::string& f, int n_volumes, int max_volumes)
+{
+    if (n_volumes >= 1 && n_volumes <= max_volumes) return RCU_OK;
+    return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(max_volumes) + ", got " + std::to_string(n_volumes));
+}
+// a batch of label / distance maps: n_per_volume < 2^31 - 1, n_volumes in 1..max_volumes, the batch below 2^32 voxels (ranks and offsets are u32)
+inline bool batch_n_ok(size_t n) { return n != 0 && n < (size_t)0x7fffffff; }
+inline bool batch_total_ok(size_t n, int n_volumes) { return (unsigned long long)n * (unsigned long long)n_volumes <= 0xffffffffull; }
+inline bool batch_ok(size_t n, int n_volumes, int max_volumes)
+{
+    return batch_n_ok(n) && n_volumes >= 1 && n_volumes <= max_volumes && batch_total_ok(n, n_volumes);
+}
+inline int check_batch(const std::string& f, size_t n, int n_volumes, int max_volumes)
+{
+    if (!batch_n_ok(n)) return report_error(RCU_ERR_INVALID, f + "n_per_volume must be in 1..2^31-2, got " + std::to_string(n));
+    if (int st = check_n_volumes(f, n_volumes, max_volumes)) return st;
+    if (!batch_total_ok(n, n_volumes)) return report_error(RCU_ERR_INVALID, f + "n_per_volume * n_volumes must be below 2^32");
+    return RCU_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // conv3x3 implicit GEMM (rcu_conv.hip)
@@ -162,6 +187,17 @@ __device__ __forceinline__ double2 stream_load(const double2* p)
     typedef double v2 __attribute__((ext_vector_type(2)));
     const v2 v = stream_load_as<v2>(p);
     return double2{v.x, v.y};
+}
+// four consecutive values of a 16-byte-aligned float32 / float64 stream
+__device__ __forceinline__ void load4(const float* src, float (&q)[4])
+{
+    const float4 v = stream_load(reinterpret_cast<const float4*>(src));
+    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
+}
+__device__ __forceinline__ void load4(const double* src, double (&q)[4])
+{
+    const double2 a = stream_load(reinterpret_cast<const double2*>(src)), b = stream_load(reinterpret_cast<const double2*>(src + 2));
+    q[0] = a.x, q[1] = a.y, q[2] = b.x, q[3] = b.y;
 }
 #endif
 

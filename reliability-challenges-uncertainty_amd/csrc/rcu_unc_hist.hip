@@ -100,17 +100,6 @@ __device__ __forceinline__ void wave_add(unsigned* hist, unsigned key, bool acti
     if (other | (first & (count != 0u))) lds_add(hist + key, first ? count : 1u);
 }
 
-__device__ __forceinline__ void load4(const float* src, float (&q)[4])
-{
-    const float4 v = stream_load(reinterpret_cast<const float4*>(src));
-    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
-}
-__device__ __forceinline__ void load4(const double* src, double (&q)[4])
-{
-    const double2 a = stream_load(reinterpret_cast<const double2*>(src)), b = stream_load(reinterpret_cast<const double2*>(src + 2));
-    q[0] = a.x, q[1] = a.y, q[2] = b.x, q[3] = b.y;
-}
-
 // MASK = false: no mask array (the evaluation's uncertainty-error scans use none): every voxel counts, and the compiler knows it
 template <int SRC, int THREADS, bool MASK>
 __global__ __launch_bounds__(THREADS) void unc_hist_kernel(const void* __restrict__ src, const uint8_t* __restrict__ pred,
@@ -306,9 +295,7 @@ int check_args(const char* fn, const char* map_name, const void* map, const uint
     if (!hist) return report_error(RCU_ERR_INVALID, f + "null hist_dev");
     if (!workspace) return report_error(RCU_ERR_INVALID, f + "null workspace_dev");
     if (n == 0) return report_error(RCU_ERR_INVALID, f + "n_per_volume must be >= 1");
-    if (n_volumes <= 0 || n_volumes > UH_MAX_VOLUMES)
-        return report_error(RCU_ERR_INVALID, f + "n_volumes must be in 1.." + std::to_string(UH_MAX_VOLUMES) + ", got " + std::to_string(n_volumes));
-    return RCU_OK;
+    return check_n_volumes(f, n_volumes, UH_MAX_VOLUMES);
 }
 
 }  // namespace
@@ -338,8 +325,7 @@ extern "C" int rcu_unc_hist(const void* unc_dev, int unc_is_f64, const uint8_t* 
         return st;
     const hipError_t e = launch(unc_is_f64 ? SRC_F64 : SRC_F32, unc_dev, prediction_dev, target_dev, mask_dev, n_per_volume, n_volumes, levels,
                                 reinterpret_cast<unsigned long long*>(hist_dev), workspace_dev, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return report_error(RCU_ERR_HIP, std::string("rcu_unc_hist: ") + hipGetErrorString(e));
-    return RCU_OK;
+    return e == hipSuccess ? RCU_OK : hip_failed("rcu_unc_hist", e);
 }
 
 extern "C" int rcu_unc_hist_from_p(const float* p_foreground_dev, const uint8_t* prediction_dev, const uint8_t* target_dev, const uint8_t* mask_dev,
@@ -350,6 +336,5 @@ extern "C" int rcu_unc_hist_from_p(const float* p_foreground_dev, const uint8_t*
         return st;
     const hipError_t e = launch(SRC_P, p_foreground_dev, prediction_dev, target_dev, mask_dev, n_per_volume, n_volumes, levels,
                                 reinterpret_cast<unsigned long long*>(hist_dev), workspace_dev, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return report_error(RCU_ERR_HIP, std::string("rcu_unc_hist_from_p: ") + hipGetErrorString(e));
-    return RCU_OK;
+    return e == hipSuccess ? RCU_OK : hip_failed("rcu_unc_hist_from_p", e);
 }

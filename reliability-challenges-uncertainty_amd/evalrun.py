@@ -418,12 +418,13 @@ class EceCalibrationAction(EvalAction):
         self.eval_cases = [EvalCase(metric, hook)]
 
 
-class CorrectionAction(EvalAction):
-    """11 CSV files (one per threshold) from one GPU pass per subject."""
+class UncertaintyAction(EvalAction):
+    """What the actions on the prepared 'uncertainty' entry share: the rescale arguments and the output directory ``<base_dir>/uncertainty``,
+    the preparation of a run (``setup_run`` is the subclass's part of ``setup_eval``), a subject's prepared entries, the check of
+    ``levels`` and the one-row file of a pooled result."""
 
-    def __init__(self, thresholds, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+    def __init__(self, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
         super().__init__()
-        self.thresholds = list(thresholds)
         self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
         self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
         os.makedirs(self.out_dir, exist_ok=True)
@@ -434,6 +435,41 @@ class CorrectionAction(EvalAction):
         self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
                                                                 self.rescale_confidence, self.rescale_sigma, mm)
         self.load_params = Loader.Params(eval_data.confidence_entry)
+        self.setup_run()
+
+    @abc.abstractmethod
+    def setup_run(self):
+        """``eval_cases`` and whatever the run accumulates, once ``id_``, ``prepare`` and ``load_params`` are set."""
+
+    def subject_rows(self, placeholder, keys):
+        """The usual ``eval_cases``: one CSV file of one row per subject, filled through ``eval_cases[0].record``."""
+        self.eval_cases = [EvalCase(None, WriteCsvHook(os.path.join(self.out_dir, placeholder.format(self.id_)), entries=keys))]
+
+    def prepared(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        return self.prepare(to_eval) if self.prepare else to_eval
+
+    @staticmethod
+    def checked_levels(levels):
+        if not 2 <= int(levels) <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
+            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        return int(levels)
+
+    def write_pooled_row(self, path, keys, row):
+        with open(path, 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id'] + list(keys))
+            writer.writerow([self.id_] + [row[k] for k in keys])
+
+
+class CorrectionAction(UncertaintyAction):
+    """11 CSV files (one per threshold) from one GPU pass per subject."""
+
+    def __init__(self, thresholds, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
+        self.thresholds = list(thresholds)
+
+    def setup_run(self):
         self.sweep = ev.UncertaintyAndCorrectionSweep(self.thresholds)
         self.eval_cases = []
         for thr in self.thresholds:
@@ -442,16 +478,13 @@ class CorrectionAction(EvalAction):
             self.eval_cases.append(EvalCase(None, hook))
 
     def eval_subject(self, sf, loader):
-        to_eval = loader.get_data(sf, self.load_params)
-        if self.prepare:
-            to_eval = self.prepare(to_eval)
         results = {}
-        self.sweep(to_eval, results)
+        self.sweep(self.prepared(sf, loader), results)
         for thr, case in zip(self.thresholds, self.eval_cases):
             case.record(results[thr], sf.subject, self.id_)
 
 
-class UeCurvesAction(EvalAction):
+class UeCurvesAction(UncertaintyAction):
     """EXTENSION (the reference has no such action): threshold-free uncertainty-error metrics from one level histogram per subject
     (evaluation.uncertainty_histogram / ue_curve_metrics), prepared exactly like ``CorrectionAction`` and, like it, without a brain mask.
     Files in ``<base_dir>/uncertainty``:
@@ -462,23 +495,12 @@ class UeCurvesAction(EvalAction):
                                        uncertainty > k / levels, so risk-coverage and uncertainty-error Dice curves need no second run"""
 
     def __init__(self, levels, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
-        super().__init__()
-        self.levels = int(levels)
-        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
-            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
+        self.levels = self.checked_levels(levels)
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.pooled = None
 
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry)
-        hook = WriteCsvHook(os.path.join(self.out_dir, UE_CURVES_PLACEHOLDER.format(self.id_)), entries=ev.UE_CURVE_KEYS)
-        self.eval_cases = [EvalCase(None, hook)]
+    def setup_run(self):
+        self.subject_rows(UE_CURVES_PLACEHOLDER, ev.UE_CURVE_KEYS)
         self.pooled = np.zeros((4, self.levels), dtype=np.uint64)
 
     def record_histogram(self, hist, subject_name):
@@ -487,19 +509,14 @@ class UeCurvesAction(EvalAction):
         self.pooled += np.asarray(hist, dtype=np.uint64)
 
     def eval_subject(self, sf, loader):
-        to_eval = loader.get_data(sf, self.load_params)
-        if self.prepare:
-            to_eval = self.prepare(to_eval)
+        to_eval = self.prepared(sf, loader)
         self.record_histogram(ev.uncertainty_histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], self.levels)[0],
                               sf.subject)
 
     def finish_eval(self):
         super().finish_eval()
-        pooled = ev.ue_curve_metrics(self.pooled)
-        with open(os.path.join(self.out_dir, UE_CURVES_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id'] + list(ev.UE_CURVE_KEYS))
-            writer.writerow([self.id_] + [pooled[k] for k in ev.UE_CURVE_KEYS])
+        self.write_pooled_row(os.path.join(self.out_dir, UE_CURVES_POOLED_PLACEHOLDER.format(self.id_)), ev.UE_CURVE_KEYS,
+                              ev.ue_curve_metrics(self.pooled))
         with open(os.path.join(self.out_dir, UE_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
             writer = csv.writer(f)
             writer.writerow(['level', 'threshold', 'tp', 'tn', 'fp', 'fn'])
@@ -507,7 +524,7 @@ class UeCurvesAction(EvalAction):
                 writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]])
 
 
-class ComponentsAction(EvalAction):
+class ComponentsAction(UncertaintyAction):
     """EXTENSION (the reference has no such action): component-level uncertainty metrics from connected components labelled on the GPU
     (evaluation.component_table / component_metrics).  The uncertainty is prepared exactly like ``UeCurvesAction``'s -- the entropy of a
     probability map in registers, the rescaled map of a 'confidence' / 'sigma' run -- and there is no brain mask.  Files in
@@ -520,25 +537,14 @@ class ComponentsAction(EvalAction):
     LIST_HEADER = ('subject', 'component', 'root_index', 'voxels', 'target_voxels', 'mean_uncertainty', 'max_uncertainty', 'is_fp')
 
     def __init__(self, levels, connectivity, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
-        super().__init__()
-        self.levels, self.connectivity = int(levels), int(connectivity)
-        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
-            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        self.levels, self.connectivity = self.checked_levels(levels), int(connectivity)
         if self.connectivity not in (6, 26):
             raise ValueError('connectivity must be 6 or 26, got {}'.format(connectivity))
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.tables, self.list_rows = [], []
 
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry)
-        hook = WriteCsvHook(os.path.join(self.out_dir, COMPONENTS_PLACEHOLDER.format(self.id_)), entries=ev.COMPONENT_METRIC_KEYS)
-        self.eval_cases = [EvalCase(None, hook)]
+    def setup_run(self):
+        self.subject_rows(COMPONENTS_PLACEHOLDER, ev.COMPONENT_METRIC_KEYS)
         self.tables, self.list_rows = [], []
 
     def record_tables(self, pred_table, target_table, subject_name):
@@ -551,9 +557,7 @@ class ComponentsAction(EvalAction):
         self.tables.append((pred_table, target_table))
 
     def eval_subject(self, sf, loader):
-        to_eval = loader.get_data(sf, self.load_params)
-        if self.prepare:
-            to_eval = self.prepare(to_eval)
+        to_eval = self.prepared(sf, loader)
         pr, tg = to_eval['prediction'], to_eval['target']
         self.record_tables(ev.component_table(pr, tg, to_eval['uncertainty'], self.connectivity)[0],
                            ev.component_table(tg, pr, None, self.connectivity)[0], sf.subject)
@@ -563,17 +567,14 @@ class ComponentsAction(EvalAction):
         empty = np.zeros(0, dtype=ev.COMPONENT_DTYPE)
         pooled = ev.component_metrics(np.concatenate([empty] + [t[0] for t in self.tables]), np.concatenate([empty] + [t[1] for t in self.tables]),
                                       self.levels)
-        with open(os.path.join(self.out_dir, COMPONENTS_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id'] + list(ev.COMPONENT_METRIC_KEYS))
-            writer.writerow([self.id_] + [pooled[k] for k in ev.COMPONENT_METRIC_KEYS])
+        self.write_pooled_row(os.path.join(self.out_dir, COMPONENTS_POOLED_PLACEHOLDER.format(self.id_)), ev.COMPONENT_METRIC_KEYS, pooled)
         with open(os.path.join(self.out_dir, COMPONENT_LIST_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
             writer = csv.writer(f)
             writer.writerow(self.LIST_HEADER)
             writer.writerows(self.list_rows)
 
 
-class BoundaryAction(EvalAction):
+class BoundaryAction(UncertaintyAction):
     """EXTENSION (the reference prepares the border shell -- labelhelper.boarder_mask, analysis.py:54-64 -- but has no such action): where the
     errors and the uncertainty sit relative to the target's boundary, from exact distance transforms on the GPU (evaluation.boundary_table,
     surface_distance_histograms, boarder_mask).  The uncertainty is prepared exactly like ``UeCurvesAction``'s and ``ComponentsAction``'s,
@@ -592,25 +593,14 @@ class BoundaryAction(EvalAction):
     POOLED_KEYS = ev.BOUNDARY_TABLE_KEYS + OFF_BORDER_KEYS
 
     def __init__(self, levels, bands, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
-        super().__init__()
-        self.levels, self.bands = int(levels), int(bands)
-        if not 2 <= self.levels <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
-            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+        self.levels, self.bands = self.checked_levels(levels), int(bands)
         if not 1 <= self.bands <= ev._lib.RCU_BOUNDARY_MAX_BANDS:
             raise ValueError('bands must be in 1..{}, got {}'.format(ev._lib.RCU_BOUNDARY_MAX_BANDS, bands))
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.pooled_table = self.pooled_hist = None
 
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry)
-        hook = WriteCsvHook(os.path.join(self.out_dir, BOUNDARY_PLACEHOLDER.format(self.id_)), entries=self.SUBJECT_KEYS)
-        self.eval_cases = [EvalCase(None, hook)]
+    def setup_run(self):
+        self.subject_rows(BOUNDARY_PLACEHOLDER, self.SUBJECT_KEYS)
         self.pooled_table = np.zeros((2, self.bands + 1), dtype=ev.BOUNDARY_DTYPE)
         self.pooled_hist = np.zeros((4, self.levels), dtype=np.uint64)
 
@@ -632,9 +622,7 @@ class BoundaryAction(EvalAction):
         self.pooled_hist += np.asarray(off_border_hist, dtype=np.uint64)
 
     def eval_subject(self, sf, loader):
-        to_eval = loader.get_data(sf, self.load_params)
-        if self.prepare:
-            to_eval = self.prepare(to_eval)
+        to_eval = self.prepared(sf, loader)
         pr, tg, unc = to_eval['prediction'], to_eval['target'], to_eval['uncertainty']
         _, shell = ev.boarder_mask(tg, 1, 1)
         self.record_boundary(ev.boundary_table(pr, tg, unc, bands=self.bands)[0], ev.surface_distance_histograms(pr, tg)[0],
@@ -642,11 +630,8 @@ class BoundaryAction(EvalAction):
 
     def finish_eval(self):
         super().finish_eval()
-        pooled = self._row(self.pooled_table, self.pooled_hist)
-        with open(os.path.join(self.out_dir, BOUNDARY_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id'] + list(self.POOLED_KEYS))
-            writer.writerow([self.id_] + [pooled[k] for k in self.POOLED_KEYS])
+        self.write_pooled_row(os.path.join(self.out_dir, BOUNDARY_POOLED_PLACEHOLDER.format(self.id_)), self.POOLED_KEYS,
+                              self._row(self.pooled_table, self.pooled_hist))
         bands = ev.boundary_metrics(self.pooled_table)
         with open(os.path.join(self.out_dir, BOUNDARY_BANDS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
             writer = csv.writer(f)

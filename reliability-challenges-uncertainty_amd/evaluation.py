@@ -12,7 +12,9 @@ indices), the 8 confusion x uncertain counts for all thresholds in one pass, the
 What is left on the host is arithmetic on ~30 numbers (ECE from the histogram, Dice from counts).
 """
 import abc
+import bisect
 import ctypes
+import math
 import warnings
 
 import numpy as np
@@ -42,6 +44,76 @@ def _to_dev(a, dtype):
     return torch.from_numpy(a).to(device=_device(), dtype=dtype)
 
 
+def _flat(a, dtype, n_volumes, like=None, names=None):
+    """An array or tensor (or None) -> device ``[n_volumes, n]`` of ``dtype``; with ``like``, another size than that map's is refused."""
+    if a is None:
+        return None
+    a = _to_dev(a, dtype).reshape(n_volumes, -1)
+    if like is not None and a.shape != like.shape:
+        raise ValueError('{} differ in size'.format(names))
+    return a
+
+
+def _float_map(uncertainty, n_volumes):
+    """-> (device ``[n_volumes, n]`` map, is64): a float64 uncertainty map stays float64, everything else goes up as float32."""
+    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
+    return _flat(uncertainty, torch.float64 if is64 else torch.float32, n_volumes), is64
+
+
+# ------------------------------------------------ the per-voxel scans: device arrays [V, n] in, device result out, nothing waits
+def _thresholds_array(thresholds):
+    return (ctypes.c_double * len(thresholds))(*[float(t) for t in thresholds])
+
+
+def _ece_launch(p, target, mask, n_bins):
+    v, n = target.shape
+    lib = _lib.load()
+    raw = torch.empty(v * ctypes.sizeof(_lib.EceResult), device=p.device, dtype=torch.uint8)
+    ws = torch.empty(max(lib.rcu_ece_workspace_bytes(n, v), 8), device=p.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_ece_hist(_lib.ptr(p), _lib.ptr(target), _lib.ptr(mask), n, v, _lib.ece_thresholds(n_bins), n_bins, _lib.ptr(raw),
+                                _lib.ptr(ws), _lib.current_stream()))
+    return raw
+
+
+def _ece_unpack(raw, v, n_bins):
+    """``_ece_launch``'s result on the host -> (count int64 [v, n_bins], sum_conf float64, sum_pos int64)."""
+    raw = raw.numpy().view(np.uint64).reshape(v, 3, _lib.RCU_MAX_BINS)
+    return raw[:, 0, :n_bins].astype(np.int64), raw[:, 1, :n_bins].copy().view(np.float64), raw[:, 2, :n_bins].astype(np.int64)
+
+
+def _unc_counts_launch(unc, is64, prediction, target, mask, thresholds):
+    v, n = target.shape
+    lib = _lib.load()
+    out = torch.empty((v, len(thresholds), 8), device=unc.device, dtype=torch.int64)
+    ws = torch.empty(max(lib.rcu_unc_workspace_bytes(n, v), 8), device=unc.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_unc_counts(_lib.ptr(unc), int(is64), _lib.ptr(prediction), _lib.ptr(target), _lib.ptr(mask), n, v, _thresholds_array(thresholds),
+                                  len(thresholds), _lib.ptr(out), _lib.ptr(ws), _lib.current_stream()))
+    return out
+
+
+def _unc_counts_from_p_launch(p, prediction, target, mask, thresholds):
+    v, n = target.shape
+    lib = _lib.load()
+    out = torch.empty((v, len(thresholds), 8), device=p.device, dtype=torch.int64)
+    ws = torch.empty(lib.rcu_unc_from_p_workspace_bytes(n, v), device=p.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_unc_counts_from_p(_lib.ptr(p), _lib.ptr(prediction), _lib.ptr(target), _lib.ptr(mask), n, v, _thresholds_array(thresholds),
+                                         len(thresholds), _lib.ptr(out), _lib.ptr(ws), _lib.current_stream()))
+    return out
+
+
+def _unc_hist_launch(source, is64, prediction, target, mask, levels):
+    """``source``: an uncertainty map (``is64`` says which), or with ``is64`` None the float32 foreground probability (rcu_unc_hist_from_p).
+    -> device int64 [v, 4, levels] holding the uint64 counts."""
+    v, n = target.shape
+    levels = int(levels)
+    lib = _lib.load()
+    out = torch.empty((v, 4, max(levels, 1)), device=source.device, dtype=torch.int64)
+    ws = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(n, v, levels), 8), device=source.device, dtype=torch.uint8)
+    rest = (_lib.ptr(prediction), _lib.ptr(target), _lib.ptr(mask), n, v, levels, _lib.ptr(out), _lib.ptr(ws), _lib.current_stream())
+    _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(source), *rest) if is64 is None else lib.rcu_unc_hist(_lib.ptr(source), int(is64), *rest))
+    return out
+
+
 # ------------------------------------------------------------------------------------------- ECE
 def _foreground(probabilities, target_ndim):
     """numpyfunctions.py:27-33."""
@@ -59,25 +131,14 @@ def calibration_histogram(probabilities, target, n_bins=10, mask=None, threshold
     ``probabilities``: foreground probability (or ``[..., 2]``), float32; ``n_volumes`` > 1 treats the
     leading axis as independent volumes (one launch for a whole test split)."""
     p = _foreground(probabilities, np.ndim(target) if not isinstance(target, torch.Tensor) else target.dim())
-    p = _to_dev(p, torch.float32).reshape(n_volumes, -1)
-    t = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    m = None if mask is None else _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    p = _flat(p, torch.float32, n_volumes)
+    t = _flat(target, torch.uint8, n_volumes)
+    m = _flat(mask, torch.uint8, n_volumes)
     if threshold_range is not None:  # numpyfunctions.py:39-43: open interval on the confidence
         lo, hi = threshold_range
         keep = ((p < hi) & (p > lo)).to(torch.uint8)
         m = keep if m is None else (m != 0).to(torch.uint8) * keep
-    n = p.shape[1]
-    lib = _lib.load()
-    thr = _lib.ece_thresholds(n_bins)
-    result = torch.empty(n_volumes * ctypes.sizeof(_lib.EceResult), device=p.device, dtype=torch.uint8)
-    ws = torch.empty(max(lib.rcu_ece_workspace_bytes(n, n_volumes), 8), device=p.device, dtype=torch.uint8)
-    _lib.check(lib.rcu_ece_hist(_lib.ptr(p), _lib.ptr(t), _lib.ptr(m), n, n_volumes, thr, n_bins, _lib.ptr(result),
-                                _lib.ptr(ws), _lib.current_stream()))
-    raw = result.cpu().numpy().view(np.uint64).reshape(n_volumes, 3, _lib.RCU_MAX_BINS)
-    count = raw[:, 0, :n_bins].astype(np.int64)
-    sum_conf = raw[:, 1, :n_bins].copy().view(np.float64)
-    sum_pos = raw[:, 2, :n_bins].astype(np.int64)
-    return count, sum_conf, sum_pos
+    return _ece_unpack(_ece_launch(p, t, m, n_bins).cpu(), n_volumes, n_bins)
 
 
 def bin_ids(p, n_bins=10):
@@ -201,30 +262,17 @@ class SubjectBatch:
         uncertainty, ``surface_distance_histograms``, the level histogram ``ue_hist_off_border`` [4, levels] of the voxels outside the
         target's border shell ``boarder_mask(target, 1, 1)``), all subjects of one shape in one call per kernel."""
         v = self.used
-        lib = _lib.load()
         out, keep = {}, []
+        p, prediction, target = self.p[:v], self.prediction[:v], self.target[:v]
         if 'minmax' in want:
-            lo, hi = torch.aminmax(self.p[:v], dim=1)
+            lo, hi = torch.aminmax(p, dim=1)
             keep.append(('minmax', torch.stack([lo, hi])))
         if 'ece' in want:
-            result = torch.empty(v * ctypes.sizeof(_lib.EceResult), device=self.device, dtype=torch.uint8)
-            ws = torch.empty(max(lib.rcu_ece_workspace_bytes(self.n, v), 8), device=self.device, dtype=torch.uint8)
-            _lib.check(lib.rcu_ece_hist(_lib.ptr(self.p), _lib.ptr(self.target), _lib.ptr(self.mask), self.n, v, _lib.ece_thresholds(n_bins),
-                                        n_bins, _lib.ptr(result), _lib.ptr(ws), _lib.current_stream()))
-            keep.append(('ece', result))
+            keep.append(('ece', _ece_launch(p, target, None if self.mask is None else self.mask[:v], n_bins)))
         if 'ue' in want:
-            thr = (ctypes.c_double * len(thresholds))(*[float(t) for t in thresholds])
-            counts = torch.empty((v, len(thresholds), 8), device=self.device, dtype=torch.int64)
-            ws2 = torch.empty(lib.rcu_unc_from_p_workspace_bytes(self.n, v), device=self.device, dtype=torch.uint8)
-            _lib.check(lib.rcu_unc_counts_from_p(_lib.ptr(self.p), _lib.ptr(self.prediction), _lib.ptr(self.target), None, self.n, v, thr,
-                                                 len(thresholds), _lib.ptr(counts), _lib.ptr(ws2), _lib.current_stream()))
-            keep.append(('ue', counts))
+            keep.append(('ue', _unc_counts_from_p_launch(p, prediction, target, None, thresholds)))
         if 'ue_hist' in want:
-            ue_hist = torch.empty((v, 4, int(levels)), device=self.device, dtype=torch.int64)
-            ws3 = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(self.n, v, int(levels)), 8), device=self.device, dtype=torch.uint8)
-            _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(self.p), _lib.ptr(self.prediction), _lib.ptr(self.target), None, self.n, v, int(levels),
-                                               _lib.ptr(ue_hist), _lib.ptr(ws3), _lib.current_stream()))
-            keep.append(('ue_hist', ue_hist))
+            keep.append(('ue_hist', _unc_hist_launch(p, None, prediction, target, None, levels)))
         if 'components' in want:
             out['components'] = self._component_tables(v, connectivity)
         if 'boundary' in want:
@@ -234,42 +282,35 @@ class SubjectBatch:
             mm = host['minmax'].numpy()
             out['min'], out['max'] = mm[0].copy(), mm[1].copy()
         if 'ece' in host:
-            raw = host['ece'].numpy().view(np.uint64).reshape(v, 3, _lib.RCU_MAX_BINS)
-            out['hist'] = (raw[:, 0, :n_bins].astype(np.int64), raw[:, 1, :n_bins].copy().view(np.float64), raw[:, 2, :n_bins].astype(np.int64))
+            out['hist'] = _ece_unpack(host['ece'], v, n_bins)
         if 'ue' in host:
             out['counts'] = host['ue'].numpy()
         if 'ue_hist' in host:
             out['ue_hist'] = host['ue_hist'].numpy().view(np.uint64)
         return out
 
+    def _by_shape(self, v):
+        """(slots, dims, p, prediction, target) per distinct shape of the first ``v`` subjects: subjects of one size are of one shape but for
+        transposed images, so the scans that need the shape take one call per shape (the whole arrays, or a gathered copy)."""
+        shapes = [self.shapes[slot] for slot in range(v)]
+        for shape in sorted(set(shapes)):
+            slots = [slot for slot in range(v) if shapes[slot] == shape]
+            index = slice(v) if len(slots) == v else torch.as_tensor(slots, device=self.device)
+            yield slots, _volume_dims(shape), self.p[index], self.prediction[index], self.target[index]
 
     def _component_tables(self, v, connectivity):
-        shapes = [self.shapes[slot] for slot in range(v)]
         pairs = [None] * v
-        for shape in sorted(set(shapes)):       # (subjects of one size are of one shape but for transposed images: one call per shape)
-            slots = [slot for slot in range(v) if shapes[slot] == shape]
-            if len(slots) == v:
-                p, pr, tg = self.p[:v], self.prediction[:v], self.target[:v]
-            else:
-                index = torch.as_tensor(slots, device=self.device)
-                p, pr, tg = self.p[index], self.prediction[index], self.target[index]
-            of_prediction = _component_tables_on_device(pr, _volume_dims(shape), tg, _lib.RCU_CC_UNC_P, p, connectivity)
-            of_target = _component_tables_on_device(tg, _volume_dims(shape), pr, _lib.RCU_CC_UNC_NONE, None, connectivity)
+        for slots, dims, p, pr, tg in self._by_shape(v):
+            of_prediction = _component_tables_on_device(pr, dims, tg, _lib.RCU_CC_UNC_P, p, connectivity)
+            of_target = _component_tables_on_device(tg, dims, pr, _lib.RCU_CC_UNC_NONE, None, connectivity)
             for k, slot in enumerate(slots):
                 pairs[slot] = (of_prediction[k], of_target[k])
         return pairs
 
     def _boundary(self, v, bands, levels):
-        shapes = [self.shapes[slot] for slot in range(v)]
         triples = [None] * v
-        for shape in sorted(set(shapes)):       # (one call per shape, as _component_tables)
-            slots = [slot for slot in range(v) if shapes[slot] == shape]
-            if len(slots) == v:
-                p, pr, tg = self.p[:v], self.prediction[:v], self.target[:v]
-            else:
-                index = torch.as_tensor(slots, device=self.device)
-                p, pr, tg = self.p[index], self.prediction[index], self.target[index]
-            for k, triple in enumerate(_boundary_on_device(p, pr, tg, _volume_dims(shape), bands, levels)):
+        for slots, dims, p, pr, tg in self._by_shape(v):
+            for k, triple in enumerate(_boundary_on_device(p, pr, tg, dims, bands, levels)):
                 triples[slots[k]] = triple
         return triples
 
@@ -277,19 +318,9 @@ class SubjectBatch:
 # ---------------------------------------------------------------------- uncertainty-error counts
 def _uncertainty_counts_device(prediction, target, uncertainty, thresholds, mask, n_volumes):
     """-> device int64 ``[n_volumes, len(thresholds), 8]`` (see ``uncertainty_counts``); asynchronous on the current stream."""
-    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
-    u = _to_dev(uncertainty, torch.float64 if is64 else torch.float32).reshape(n_volumes, -1)
-    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
-    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    m = None if mask is None else _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    n = u.shape[1]
-    thr = (ctypes.c_double * len(thresholds))(*[float(t) for t in thresholds])
-    lib = _lib.load()
-    out = torch.empty((n_volumes, len(thresholds), 8), device=u.device, dtype=torch.int64)
-    ws = torch.empty(max(lib.rcu_unc_workspace_bytes(n, n_volumes), 8), device=u.device, dtype=torch.uint8)
-    _lib.check(lib.rcu_unc_counts(_lib.ptr(u), int(is64), _lib.ptr(pr), _lib.ptr(tg), _lib.ptr(m), n, n_volumes, thr,
-                                  len(thresholds), _lib.ptr(out), _lib.ptr(ws), _lib.current_stream()))
-    return out
+    u, is64 = _float_map(uncertainty, n_volumes)
+    return _unc_counts_launch(u, is64, _flat(prediction, torch.uint8, n_volumes), _flat(target, torch.uint8, n_volumes),
+                              _flat(mask, torch.uint8, n_volumes), thresholds)
 
 
 def uncertainty_counts(prediction, target, uncertainty, thresholds=UE_THRESHOLDS, mask=None, n_volumes=1):
@@ -304,26 +335,15 @@ def from_p_supported(thresholds):
     thresholds = [float(t) for t in thresholds]
     if not 1 <= len(thresholds) <= _lib.RCU_MAX_THRESHOLDS:
         return False
-    thr = (ctypes.c_double * len(thresholds))(*thresholds)
-    return bool(_lib.load().rcu_unc_from_p_supported(thr, len(thresholds)))
+    return bool(_lib.load().rcu_unc_from_p_supported(_thresholds_array(thresholds), len(thresholds)))
 
 
 def uncertainty_counts_from_p(prediction, target, foreground_probability, thresholds=UE_THRESHOLDS, mask=None, n_volumes=1):
     """``uncertainty_counts`` for uncertainty = ToEntropy([1 - p, p]) (the 'probabilities' confidence entry, analysis.py:249-252) computed
     from the float32 probability map itself: "uncertain" is looked up in the table of the reference's own float32 sets (include/rcu.h,
     rcu_unc_counts_from_p; fixture g20), so neither an entropy map nor a device log enters -- the counts are the reference's."""
-    p = _to_dev(foreground_probability, torch.float32).reshape(n_volumes, -1)
-    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
-    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    m = None if mask is None else _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    n = p.shape[1]
-    thr = (ctypes.c_double * len(thresholds))(*[float(t) for t in thresholds])
-    lib = _lib.load()
-    out = torch.empty((n_volumes, len(thresholds), 8), device=p.device, dtype=torch.int64)
-    ws = torch.empty(lib.rcu_unc_from_p_workspace_bytes(n, n_volumes), device=p.device, dtype=torch.uint8)
-    _lib.check(lib.rcu_unc_counts_from_p(_lib.ptr(p), _lib.ptr(pr), _lib.ptr(tg), _lib.ptr(m), n, n_volumes, thr, len(thresholds),
-                                         _lib.ptr(out), _lib.ptr(ws), _lib.current_stream()))
-    return out.cpu().numpy()
+    return _unc_counts_from_p_launch(_flat(foreground_probability, torch.float32, n_volumes), _flat(prediction, torch.uint8, n_volumes),
+                                     _flat(target, torch.uint8, n_volumes), _flat(mask, torch.uint8, n_volumes), thresholds).cpu().numpy()
 
 
 class EntropyOfProbability:
@@ -365,18 +385,9 @@ UE_LEVELS = 1000        # default number of levels: every threshold of UE_THRESH
 UE_CURVE_KEYS = ('n', 'n_errors', 'auroc', 'auprc', 'aurc', 'eaurc', 'ue_dice_max', 'ue_dice_max_threshold')
 
 
-def _histogram_on_device(fn_name, source, source_dtype, extra, prediction, target, levels, mask, n_volumes):
-    u = _to_dev(source, source_dtype).reshape(n_volumes, -1)
-    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
-    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    m = None if mask is None else _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    n, levels = u.shape[1], int(levels)
-    lib = _lib.load()
-    out = torch.empty((n_volumes, 4, max(levels, 1)), device=u.device, dtype=torch.int64)
-    ws = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(n, n_volumes, levels), 8), device=u.device, dtype=torch.uint8)
-    _lib.check(getattr(lib, fn_name)(_lib.ptr(u), *extra, _lib.ptr(pr), _lib.ptr(tg), _lib.ptr(m), n, n_volumes, levels, _lib.ptr(out),
-                                     _lib.ptr(ws), _lib.current_stream()))
-    return out.cpu().numpy().view(np.uint64)
+def _histogram(source, is64, prediction, target, levels, mask, n_volumes):
+    return _unc_hist_launch(source, is64, _flat(prediction, torch.uint8, n_volumes), _flat(target, torch.uint8, n_volumes),
+                            _flat(mask, torch.uint8, n_volumes), levels).cpu().numpy().view(np.uint64)
 
 
 def uncertainty_histogram(prediction, target, uncertainty, levels=UE_LEVELS, mask=None, n_volumes=1):
@@ -387,16 +398,36 @@ def uncertainty_histogram(prediction, target, uncertainty, levels=UE_LEVELS, mas
     ``uncertainty_histogram_from_p`` (no entropy volume)."""
     if isinstance(uncertainty, EntropyOfProbability):
         return uncertainty_histogram_from_p(prediction, target, uncertainty.foreground_probability, levels, mask, n_volumes)
-    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
-    return _histogram_on_device('rcu_unc_hist', uncertainty, torch.float64 if is64 else torch.float32, (int(is64),), prediction, target,
-                                levels, mask, n_volumes)
+    return _histogram(*_float_map(uncertainty, n_volumes), prediction, target, levels, mask, n_volumes)
 
 
 def uncertainty_histogram_from_p(prediction, target, foreground_probability, levels=UE_LEVELS, mask=None, n_volumes=1):
     """``uncertainty_histogram`` for uncertainty = ToEntropy([1 - p, p]), from the float32 foreground-probability map itself: the entropy
     is computed in registers with ``normalised_entropy``'s arithmetic, so the result equals
     ``uncertainty_histogram(..., normalised_entropy(p))`` integer for integer and the float64 map is never made."""
-    return _histogram_on_device('rcu_unc_hist_from_p', foreground_probability, torch.float32, (), prediction, target, levels, mask, n_volumes)
+    return _histogram(_flat(foreground_probability, torch.float32, n_volumes), None, prediction, target, levels, mask, n_volumes)
+
+
+def _rank_metrics(groups):
+    """(auroc, auprc) of ranking positives above negatives by a score, ties counted half, from the ascending sequence of (positives,
+    negatives) per distinct score.  Python integers, every ratio rounded once:
+      auroc   sum_g pos_g (neg_{<g} + neg_g / 2) / (P N): twice the numerator is an integer, one division
+      auprc   sum_{g: pos_g > 0} (pos_g / P) (pos_{>=g} / n_{>=g}): scores descending, math.fsum of the terms
+    NaN where undefined (P = 0 or N = 0 for auroc, P = 0 for auprc)."""
+    groups = list(groups)
+    n_pos, n_neg = sum(pos for pos, _ in groups), sum(neg for _, neg in groups)
+    below, twice = 0, 0
+    for pos, neg in groups:
+        twice += pos * (2 * below + neg)
+        below += neg
+    terms, pos_ge, n_ge = [], 0, 0
+    for pos, neg in reversed(groups):
+        pos_ge += pos
+        n_ge += pos + neg
+        if pos:
+            terms.append((pos * pos_ge) / (n_pos * n_ge))
+    nan = float('nan')
+    return twice / (2 * n_pos * n_neg) if n_pos and n_neg else nan, math.fsum(terms) if n_pos else nan
 
 
 def ue_curve_metrics(hist):
@@ -412,7 +443,6 @@ def ue_curve_metrics(hist):
       ue_dice_max, ue_dice_max_threshold   the maximum over k = 1..B-1 of ``error_dice`` on the counts at the threshold k / B, and the
               smallest such threshold that attains it
     Undefined cases (E = 0 or C = 0 for auroc, E = 0 for auprc, N = 0 for all four) are ``float('nan')``."""
-    import math
     h = np.asarray(hist)
     if h.ndim != 2 or h.shape[0] != 4 or h.shape[1] < 2:
         raise ValueError('expected one level histogram of shape [4, levels >= 2], got {}'.format(h.shape))
@@ -424,20 +454,7 @@ def ue_curve_metrics(hist):
     n = n_errors + n_correct
     nan = float('nan')
     out = {'n': n, 'n_errors': n_errors}
-    # auroc: twice the numerator is an integer
-    below, twice = 0, 0
-    for l in range(levels):
-        twice += e[l] * (2 * below + c[l])
-        below += c[l]
-    out['auroc'] = twice / (2 * n_errors * n_correct) if n_errors and n_correct else nan
-    # auprc: levels descending
-    terms, e_ge, n_ge = [], 0, 0
-    for l in range(levels - 1, -1, -1):
-        e_ge += e[l]
-        n_ge += e[l] + c[l]
-        if e[l]:
-            terms.append((e[l] * e_ge) / (n_errors * n_ge))
-    out['auprc'] = math.fsum(terms) if n_errors else nan
+    out['auroc'], out['auprc'] = _rank_metrics(zip(e, c))
     # aurc / eaurc: levels ascending
     risk, ideal, e_le, n_le = [], [], 0, 0
     for l in range(levels):
@@ -526,7 +543,7 @@ def connected_components(mask, connectivity=26, n_volumes=1):
     int64 ``[n_volumes]`` = K per volume.  The mask's own shape gives depth / height / width (2-D arrays: depth 1, where connectivity 6 / 26
     are the 4- / 8-neighbourhoods); ``n_volumes`` > 1 treats the leading axis as independent volumes.  A device tensor gets a device tensor."""
     dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
-    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
+    m = _flat(mask, torch.uint8, n_volumes)
     labels = _labels_on_device(m, dims, connectivity)
     counts, ws = _compact_on_device(labels)
     dense = torch.empty_like(labels)
@@ -539,8 +556,7 @@ def canonical_labels(mask, connectivity=26, n_volumes=1):
     """The labelling before it is made dense (include/rcu.h, rcu_cc_label): int32 of the mask's shape, 0 for background, else 1 + the
     smallest linear index (C order within the volume) of the voxel's component.  Host array."""
     dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
-    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    return _labels_on_device(m, dims, connectivity).cpu().numpy().reshape(tuple(mask.shape))
+    return _labels_on_device(_flat(mask, torch.uint8, n_volumes), dims, connectivity).cpu().numpy().reshape(tuple(mask.shape))
 
 
 def component_table(mask, other=None, uncertainty=None, connectivity=26, n_volumes=1):
@@ -553,19 +569,9 @@ def component_table(mask, other=None, uncertainty=None, connectivity=26, n_volum
     ``EntropyOfProbability`` whose entropy is computed in registers (the table of its materialised map, integer for integer); numpy
     arrays or device tensors."""
     dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
-    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    o = None if other is None else _to_dev(other, torch.uint8).reshape(n_volumes, -1)
-    if o is not None and o.shape != m.shape:
-        raise ValueError('mask and other differ in size')
-    kind, u = _lib.RCU_CC_UNC_NONE, None
-    if isinstance(uncertainty, EntropyOfProbability):
-        kind, u = _lib.RCU_CC_UNC_P, _to_dev(uncertainty.foreground_probability, torch.float32).reshape(n_volumes, -1)
-    elif uncertainty is not None:
-        is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
-        kind = _lib.RCU_CC_UNC_F64 if is64 else _lib.RCU_CC_UNC_F32
-        u = _to_dev(uncertainty, torch.float64 if is64 else torch.float32).reshape(n_volumes, -1)
-    if u is not None and u.shape != m.shape:
-        raise ValueError('mask and uncertainty differ in size')
+    m = _flat(mask, torch.uint8, n_volumes)
+    o = _flat(other, torch.uint8, n_volumes, m, 'mask and other')
+    kind, u = _uncertainty_source(uncertainty, None, n_volumes, m, 'mask and uncertainty')
     return _component_tables_on_device(m, dims, o, kind, u, connectivity)
 
 
@@ -581,8 +587,6 @@ def component_metrics(pred_table, target_table, levels=UE_LEVELS):
       dice_filtered_max, dice_filtered_max_threshold   over the thresholds k / levels, k = 0..levels, the predicted components with
                            m_k > k / levels (float64) removed: 2 (TP - removed other_voxels) / (P - removed voxels + T); the maximum and the
                            smallest threshold that attains it"""
-    import bisect
-    import math
     levels = int(levels)
     if levels < 1:
         raise ValueError('levels must be >= 1, got {}'.format(levels))
@@ -591,7 +595,6 @@ def component_metrics(pred_table, target_table, levels=UE_LEVELS):
     mean = [int(s_) / (v_ * COMPONENT_UNC_ONE) for s_, v_ in zip(pred_table['unc_sum'], voxels)]
     is_fp = [o == 0 for o in overlap]
     p_all, tp, t_all = sum(voxels), sum(overlap), sum(int(x) for x in target_table['voxels'])
-    nan = float('nan')
     out = {'n_components': len(voxels), 'n_fp_components': sum(is_fp), 'fp_voxels': sum(v_ for v_, f in zip(voxels, is_fp) if f),
            'n_target_components': len(target_table), 'n_missed_target_components': int(sum(1 for x in target_table['other_voxels'] if int(x) == 0))}
     # the distinct scores ascending, with their false-positive and true-positive component counts
@@ -599,22 +602,7 @@ def component_metrics(pred_table, target_table, levels=UE_LEVELS):
     for m_, f in zip(mean, is_fp):
         g = groups.setdefault(m_, [0, 0])
         g[0 if f else 1] += 1
-    scores = sorted(groups)
-    n_pos, n_neg = out['n_fp_components'], len(voxels) - out['n_fp_components']
-    below, twice = 0, 0
-    for sc in scores:
-        pos, neg = groups[sc]
-        twice += pos * (2 * below + neg)
-        below += neg
-    out['auroc_fp'] = twice / (2 * n_pos * n_neg) if n_pos and n_neg else nan
-    terms, pos_ge, n_ge = [], 0, 0
-    for sc in reversed(scores):
-        pos, neg = groups[sc]
-        pos_ge += pos
-        n_ge += pos + neg
-        if pos:
-            terms.append((pos * pos_ge) / (n_pos * n_ge))
-    out['auprc_fp'] = math.fsum(terms) if n_pos else nan
+    out['auroc_fp'], out['auprc_fp'] = _rank_metrics(groups[score] for score in sorted(groups))
     out['dice'] = _dice(tp, p_all - tp, t_all - tp)
     # component k is removed at the thresholds below m_k: at k' / levels for k' < c_k = #{k' : k' / levels < m_k}
     grid = [k / levels for k in range(levels + 1)]
@@ -661,8 +649,7 @@ def distance_transform_sq(mask, n_volumes=1, invert=False):
     (2-D arrays: the 2-D transform); ``n_volumes`` > 1 treats the leading axis as independent volumes.  A device tensor gets a device
     tensor (int32 holding the uint32 bits where torch lacks uint32)."""
     dims = _volume_dims(_split_volumes(mask.shape, n_volumes))
-    m = _to_dev(mask, torch.uint8).reshape(n_volumes, -1)
-    out = _edt_on_device(m, dims, 0 if invert else 1).reshape(tuple(mask.shape))
+    out = _edt_on_device(_flat(mask, torch.uint8, n_volumes), dims, 0 if invert else 1).reshape(tuple(mask.shape))
     if isinstance(mask, torch.Tensor) and mask.is_cuda:
         return out.view(torch.uint32) if hasattr(torch, 'uint32') else out
     return out.cpu().numpy().view(np.uint32)
@@ -684,7 +671,7 @@ def boarder_mask(binary_label_map, distance_in, distance_out):
     rounded float64 square root -- the reference's arrays bit for bit wherever the map holds both classes.  Where it holds one class only
     the reference's values are scipy's artefact; here the distance is ``inf`` and the mask empty."""
     dims = _volume_dims(binary_label_map.shape)
-    m = _to_dev(binary_label_map, torch.uint8).reshape(1, -1)
+    m = _flat(binary_label_map, torch.uint8, 1)
     distance, mask = _border_on_device(_edt_on_device(m, dims, 1), _edt_on_device(m, dims, 0), distance_in, distance_out, True)
     distance, mask = distance.reshape(tuple(binary_label_map.shape)), mask.reshape(tuple(binary_label_map.shape)).to(torch.bool)
     if isinstance(binary_label_map, torch.Tensor) and binary_label_map.is_cuda:
@@ -699,18 +686,21 @@ def _check_bands(bands):
     return bands
 
 
-def _uncertainty_source(uncertainty, foreground_probability, n_volumes):
-    """-> (RCU_CC_UNC_* kind, device map [V, n] or None) of an uncertainty given as a float map, an ``EntropyOfProbability`` or a probability map."""
-    if foreground_probability is not None:
-        if uncertainty is not None:
-            raise ValueError('give uncertainty or foreground_probability, not both')
-        return _lib.RCU_CC_UNC_P, _to_dev(foreground_probability, torch.float32).reshape(n_volumes, -1)
+def _uncertainty_source(uncertainty, foreground_probability, n_volumes, like, names):
+    """-> (RCU_CC_UNC_* kind, device map [V, n] or None) of an uncertainty given as a float map, an ``EntropyOfProbability`` or a probability
+    map; a map of another size than ``like`` is refused (``names`` differ in size)."""
+    if foreground_probability is not None and uncertainty is not None:
+        raise ValueError('give uncertainty or foreground_probability, not both')
     if isinstance(uncertainty, EntropyOfProbability):
-        return _lib.RCU_CC_UNC_P, _to_dev(uncertainty.foreground_probability, torch.float32).reshape(n_volumes, -1)
+        foreground_probability = uncertainty.foreground_probability
+    if foreground_probability is not None:
+        return _lib.RCU_CC_UNC_P, _flat(foreground_probability, torch.float32, n_volumes, like, names)
     if uncertainty is None:
         return _lib.RCU_CC_UNC_NONE, None
-    is64 = uncertainty.dtype == (torch.float64 if isinstance(uncertainty, torch.Tensor) else np.float64)
-    return (_lib.RCU_CC_UNC_F64 if is64 else _lib.RCU_CC_UNC_F32), _to_dev(uncertainty, torch.float64 if is64 else torch.float32).reshape(n_volumes, -1)
+    u, is64 = _float_map(uncertainty, n_volumes)
+    if u.shape != like.shape:
+        raise ValueError('{} differ in size'.format(names))
+    return (_lib.RCU_CC_UNC_F64 if is64 else _lib.RCU_CC_UNC_F32), u
 
 
 def _boundary_table_on_device(prediction, target, d_in, d_out, unc_kind, unc, bands):
@@ -732,13 +722,9 @@ def boundary_table(prediction, target, uncertainty=None, foreground_probability=
     (``uncertainty``), or a float32 foreground-probability map whose entropy is computed in registers (``foreground_probability``)."""
     bands = _check_bands(bands)
     dims = _volume_dims(_split_volumes(target.shape, n_volumes))
-    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
-    if pr.shape != tg.shape:
-        raise ValueError('prediction and target differ in size')
-    kind, u = _uncertainty_source(uncertainty, foreground_probability, n_volumes)
-    if u is not None and u.shape != tg.shape:
-        raise ValueError('target and uncertainty differ in size')
+    tg = _flat(target, torch.uint8, n_volumes)
+    pr = _flat(prediction, torch.uint8, n_volumes, tg, 'prediction and target')
+    kind, u = _uncertainty_source(uncertainty, foreground_probability, n_volumes, tg, 'target and uncertainty')
     table = _boundary_table_on_device(pr, tg, _edt_on_device(tg, dims, 1), _edt_on_device(tg, dims, 0), kind, u, bands)
     return table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(n_volumes, 2, bands + 1).copy()
 
@@ -775,10 +761,8 @@ def surface_distance_histograms(prediction, target, n_volumes=1):
     outside A inside the volume (``A & ~scipy.ndimage.binary_erosion(A, border_value=1)``; medpy's ``border_value=0`` differs only where A
     touches the volume face).  Where the other surface is empty the squared distance is ``EDT_NONE``, as ``distance_transform_sq``'s."""
     dims = _volume_dims(_split_volumes(target.shape, n_volumes))
-    pr = _to_dev(prediction, torch.uint8).reshape(n_volumes, -1)
-    tg = _to_dev(target, torch.uint8).reshape(n_volumes, -1)
-    if pr.shape != tg.shape:
-        raise ValueError('prediction and target differ in size')
+    tg = _flat(target, torch.uint8, n_volumes)
+    pr = _flat(prediction, torch.uint8, n_volumes, tg, 'prediction and target')
     return _surface_histograms_to_host(*_surface_histograms_on_device(pr, tg, dims), n_volumes)
 
 
@@ -789,7 +773,6 @@ def surface_distance_metrics(hist):
       hd95   ``numpy.percentile(.., 95)`` (linear interpolation) of both directions' distances together, from the counts
       assd   the sum of sqrt(d^2) * count over both directions, added in ascending d^2, over the number of surface voxels of both
     All three are NaN if either surface is empty."""
-    import math
     sq, c_pt, c_tp = hist
     sq = [int(s_) for s_ in sq]
     count = [int(a) + int(b) for a, b in zip(c_pt, c_tp)]
@@ -867,16 +850,12 @@ def add_boundary_tables(tables):
 def _boundary_on_device(p, prediction, target, dims, bands, levels):
     """Everything the 'boundary' action needs of a batch of resident subjects of one shape (device arrays [V, n]; p: the float32 foreground
     probability) -> per volume (boundary table, surface histograms, level histogram off the target's border shell)."""
-    v, n = target.shape
-    lib = _lib.load()
+    v = target.shape[0]
     d_in, d_out = _edt_on_device(target, dims, 1), _edt_on_device(target, dims, 0)
     table = _boundary_table_on_device(prediction, target, d_in, d_out, _lib.RCU_CC_UNC_P, p, bands)
     _, shell = _border_on_device(d_in, d_out, 1, 1, False)
     off_border = (shell == 0).to(torch.uint8)
-    ue_hist = torch.empty((v, 4, int(levels)), device=target.device, dtype=torch.int64)
-    ws = torch.empty(max(lib.rcu_unc_hist_workspace_bytes(n, v, int(levels)), 8), device=target.device, dtype=torch.uint8)
-    _lib.check(lib.rcu_unc_hist_from_p(_lib.ptr(p), _lib.ptr(prediction), _lib.ptr(target), _lib.ptr(off_border), n, v, int(levels), _lib.ptr(ue_hist),
-                                       _lib.ptr(ws), _lib.current_stream()))
+    ue_hist = _unc_hist_launch(p, None, prediction, target, off_border, levels)
     surfaces = _surface_histograms_to_host(*_surface_histograms_on_device(prediction, target, dims), v)
     tables = table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(v, 2, bands + 1)
     hists = ue_hist.cpu().numpy().view(np.uint64)

@@ -179,6 +179,37 @@ def test_quantisation_is_the_stated_rounding():
     assert int(quantise(np.array([f]))[0]) == int(np.rint(np.float64(f) * ONE))
 
 
+def test_quantisation_has_one_definition():
+    """q(u) lives in one header that the component table and the boundary table both include."""
+    csrc = os.path.join(ROOT, 'reliability-challenges-uncertainty_amd', 'csrc')
+    shared = open(os.path.join(csrc, 'rcu_unc_source.h')).read()
+    assert re.search(r'\bquantise\s*\(\s*double\b', shared) and '16777216' in shared and '#include "rcu_entropy.h"' in shared
+    for name in ('rcu_cc.hip', 'rcu_edt.hip'):
+        text = open(os.path.join(csrc, name)).read()
+        assert '#include "rcu_unc_source.h"' in text, name
+        assert '16777216' not in text, name        # no second copy of the arithmetic
+
+
+def test_host_metric_floats_are_the_stored_bits_g25():
+    """Every float of the four host metric functions on the integers of G22, G23 and G24, as float.hex() (NaN as 'nan'): what the
+    actions' CSV files print.  The generator's own ``compute`` is run again and compared entry by entry."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location('generate_metric_floats', os.path.join(ROOT, 'tests', 'golden', 'generate_metric_floats.py'))
+    generator = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(generator)
+    with open(generator.PATH) as f:
+        stored = json.load(f)
+    now = generator.compute()
+    assert sorted(now) == sorted(stored) == ['boundary', 'components', 'surface', 'ue_curves']
+    assert [len(stored[k]) for k in sorted(stored)] == [12, 22, 5, 7]
+    for section in stored:
+        assert sorted(now[section]) == sorted(stored[section]), section
+        for table, expect in stored[section].items():
+            assert now[section][table] == expect, (section, table)      # (hex strings and integers: NaN is the string 'nan')
+    assert stored['ue_curves']['sum']['auroc'].startswith('0x1.') and stored['components']['diag_c26_l1000']['auroc_fp'] == 'nan'
+
+
 # ------------------------------------------------------------------------------------------------------- component_metrics
 def brute_force_filtered_dice(pred, target, unc, conn, levels):
     """Remove the components with mean uncertainty > k / levels from the MASK, count voxels, take the Dice: every k, no tables."""

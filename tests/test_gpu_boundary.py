@@ -312,6 +312,48 @@ def test_subject_batch_metrics_with_boundary(dev):
         batch.metrics(want=('boundary',), bands=0)
 
 
+def test_subject_batch_all_scans_in_one_call_over_two_shapes(dev):
+    """Every scan of ``metrics`` in ONE call on a batch of two shapes, the odd shape in the middle slot (the gathered copy of the per-shape
+    grouping): each entry is what the public one-volume function returns for that subject in its own shape, integer for integer, and
+    the floats (min / max, the reliability histogram's confidence sums) bit for bit.  4320 voxels per subject: more than one labelling
+    tile (4 x 8 x 32) along every axis, more than one line per slab of the distance transform."""
+    from rcu_amd import evaluation as ev
+    rng = np.random.RandomState(11)
+    shapes = ((6, 20, 36), (6, 36, 20), (6, 20, 36))
+    batch = ev.SubjectBatch(3, 6 * 20 * 36)
+    subjects = []
+    for slot, shape in enumerate(shapes):
+        p = rng.rand(*shape).astype(np.float32)
+        pr = (p > 0.5).astype(np.uint8)
+        blob = np.zeros(shape, dtype=np.uint8)
+        blob[1:5, shape[1] // 4:shape[1] // 4 * 3, shape[2] // 4:shape[2] // 4 * 3] = 1
+        tg = np.roll(blob, (slot % 2, 2 + slot, -3), axis=(0, 1, 2))       # a shifted blob: both classes, and errors of both kinds
+        assert 0 < int(tg.sum()) < tg.size and ((pr != tg) & (tg != 0)).any() and ((pr != tg) & (tg == 0)).any()
+        batch.put(slot, p, pr, tg)
+        subjects.append((p, pr, tg))
+    batch.upload()
+    res = batch.metrics(want=('minmax', 'ece', 'ue', 'ue_hist', 'components', 'boundary'), levels=1000, bands=3, connectivity=26)
+    assert set(res) == {'min', 'max', 'hist', 'counts', 'ue_hist', 'components', 'boundary'}
+    for slot, (p, pr, tg) in enumerate(subjects):
+        assert res['min'][slot].tobytes() == p.min().tobytes() and res['max'][slot].tobytes() == p.max().tobytes(), slot
+        count, sum_conf, sum_pos = ev.calibration_histogram(p, tg, 10)
+        print(slot, 'sum_conf', [v.hex() for v in res['hist'][1][slot]], [v.hex() for v in sum_conf[0]])
+        assert np.array_equal(res['hist'][0][slot], count[0]) and np.array_equal(res['hist'][2][slot], sum_pos[0]), slot
+        assert res['hist'][1][slot].dtype == np.float64 and res['hist'][1][slot].tobytes() == sum_conf[0].tobytes(), slot
+        assert int(count.sum()) == tg.size
+        assert np.array_equal(res['counts'][slot], ev.uncertainty_counts_from_p(pr, tg, p)[0]), slot
+        expect = ev.uncertainty_histogram_from_p(pr, tg, p, 1000)[0]
+        assert res['ue_hist'][slot].dtype == expect.dtype and np.array_equal(res['ue_hist'][slot], expect), slot
+        of_prediction, of_target = res['components'][slot]
+        assert of_prediction.tobytes() == ev.component_table(pr, tg, ev.EntropyOfProbability(p), 26)[0].tobytes() and len(of_prediction) >= 1, slot
+        assert of_target.tobytes() == ev.component_table(tg, pr, None, 26)[0].tobytes() and len(of_target) >= 1, slot
+        table, surface, off_border = res['boundary'][slot]
+        assert table.tobytes() == ev.boundary_table(pr, tg, foreground_probability=p, bands=3)[0].tobytes(), slot
+        assert same_histogram(surface, ev.surface_distance_histograms(pr, tg)[0]), slot
+        expect = ev.uncertainty_histogram_from_p(pr, tg, p, 1000, mask=~ev.boarder_mask(tg, 1, 1)[1])[0]
+        assert off_border.dtype == expect.dtype and np.array_equal(off_border, expect) and 0 < int(off_border.sum()) < tg.size, slot
+
+
 # ----------------------------------------------------------------------------------------------------------- 9. end to end
 def test_boundary_action_end_to_end(dev, tmp_path):
     from rcu_amd import evalrun, evaluation as ev
