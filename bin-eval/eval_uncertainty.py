@@ -16,7 +16,8 @@ if __name__ == '__main__':
     parser.add_argument('--act', type=str, nargs='*', help='the names of the evaluation configuration: minmax, ece_dice, calib, bnf_ue (the default: '
                         'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) components '
                         '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice) and '
-                        'boundary (errors and uncertainty by distance to the target\'s boundary, surface distances, metrics off the border shell)')
+                        'boundary (errors and uncertainty by distance to the target\'s boundary, surface distances, metrics off the border shell), agreement '
+                        '(the run\'s agreement.csv -- written under others.agreement: true -- against each subject\'s Dice: correlations, failure detection)')
     parser.add_argument('--pred_dir', type=str, default=None, help='root with one sub-directory per dataset and run id '
                         '(default: directories.PREDICT_DIR and the per-run *_PREDICT names)')
     parser.add_argument('--gt_dir', type=str, default=None, help='BraTS training tree / ISIC dataset prefix '
@@ -27,6 +28,8 @@ if __name__ == '__main__':
                         'components action (2..4096)')
     parser.add_argument('--connectivity', type=int, default=26, choices=(6, 26), help='rcu_amd: neighbourhood of the components action (2-D images: 4 / 8)')
     parser.add_argument('--bands', type=int, default=10, help='rcu_amd: distance bands of the boundary action (1..64)')
+    parser.add_argument('--dice_fail', type=float, default=0.8, help='rcu_amd: the agreement action counts a subject with Dice below this as a failed '
+                        'segmentation')
     parser.add_argument('--plain', action='store_true', help='rcu_amd: the reference\'s subject-by-subject, action-by-action loop for every run')
     args = parser.parse_args()
     from rcu_amd import directories as dirs
@@ -48,4 +51,4 @@ if __name__ == '__main__':
     runs = {i: (os.path.join(args.pred_dir, ds, i) if args.pred_dir else dirs.prediction_dir(ds, i)) for i in ids}
     out_dir = os.path.join(args.out_dir, ds) if args.out_dir else dirs.eval_dir(ds)
     scripts.eval_uncertainty(ds, runs, gt_dir, out_dir, acts, fused=not args.plain, batch_subjects=args.batch_subjects,
-                             levels=args.levels, connectivity=args.connectivity, bands=args.bands)
+                             levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail)

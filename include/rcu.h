@@ -589,6 +589,41 @@ int rcu_surface_distance_hist(const uint8_t* prediction_dev, const uint8_t* targ
  * Process-wide. */
 int rcu_edt_set_slab_width(int slab_width);
 
+/* ------------------------------------------------------------------------------------------
+ * Sample agreement (EXTENSION: the reference's uncertainties are per-voxel moments of the pass probabilities; rcu_amd.steps.McPredictStep with
+ * agreement=True, SampleAgreementStep, rcu_amd.evaluation.agreement_tables / agreement_metrics and the 'agreement' evaluation action look at
+ * the T samples as whole segmentations -- the structure-wise uncertainties of Roy et al., Bayesian QuickNAT, 2019)
+ *   Vote plane.  votes_dev is uint32 [n_words][V] over the voxels v = image * hw + pixel of a batch, V = n * hw, zeroed by its owner before the
+ *   first pass.  Pass j (1-based) owns bit (j - 1) % 32 of word (j - 1) / 32; RCU_VOTES_MAX_PASSES = 64 passes, so n_words is 1 or 2.  The bit
+ *   at v is set iff the arg-max of the vector the pass adds to the MC statistics at v is not class 0, ties going to the lower class as in
+ *   rcu_prediction_and_foreground (two classes: p[1] > p[0]).  The entries below only ever OR bits in; they leave every other bit alone.
+ *   Tables.  A volume is a run of n_per_volume consecutive voxels of the plane.  With A_i the set of voxels of the volume pass i + 1 voted for:
+ *       hist[vol][c],      c = 0..T        voxels with exactly c of the bits 0..T-1 set                          (uint64 [n_volumes][T + 1])
+ *       pairs[vol][i][j],  0 <= i <= j < T |A_i & A_j|, row-major upper triangle with the diagonal (= the |A_i|) (uint64 [n_volumes][T (T + 1) / 2])
+ *   Bits at or above T are ignored.  All integers: the tables are a function of the plane alone and the tables of slices add up to their subject's.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_VOTES_MAX_PASSES 64
+
+/* rcu_unet_forward_accumulate_passes that also votes: pass t of the group (masks as there; passes == 1: one pass) ORs bit bits_host[t] (int32
+ * [passes] on the host, read before the call returns; bit b lives in word b / 32 at bit b % 32) of votes_dev.  The statistics receive what
+ * rcu_unet_forward_accumulate_passes gives them, bit for bit.  The forward takes the separate head kernel (as under rcu_unet_set_fuse_head(h,
+ * 0)); the voxel's word is read and written once per launch beside its statistics entries, a group whose bits straddle a word (or of more than
+ * 32 passes) runs as one head launch per word, in pass order.  No atomics: launches that share a plane must share a stream.
+ * RCU_ERR_INVALID, before anything is launched, for a null handle / x_dev / stats_dev / votes_dev / bits_host, n_words outside 1..2, a bit
+ * outside [0, 32 * n_words), nb_classes outside 1..8 and n * passes outside 1..max_batch. */
+int rcu_unet_forward_accumulate_votes(rcu_unet* h, const float* x_dev, int n, int passes, const float* masks_dev, void* stats_dev, int flags,
+                                      uint32_t* votes_dev, int n_words, const int32_t* bits_host, void* stream);
+/* The vote of one pass over a materialised [n][nb_classes][hw] float32 volume: probabilities (flags = RCU_MC_INPUT_PROBS), or logits (flags = 0),
+ * which go through the softmax of rcu_mc_accumulate first -- the vote is the arg-max of what the statistics would receive.  ORs bit `bit` of
+ * votes_dev ([n_words][n * hw]).  RCU_ERR_INVALID for null pointers, n_words outside 1..2, bit outside [0, 32 * n_words), nb_classes outside
+ * 1..8; n * hw == 0 is a no-op. */
+int rcu_mc_votes(const float* in_dev, size_t n, size_t hw, int nb_classes, int flags, uint32_t* votes_dev, int n_words, int bit, void* stream);
+/* hist_dev and pairs_dev (zeroed here, then filled on `stream`) of the n_volumes volumes of n_per_volume voxels of votes_dev
+ * ([n_words][n_per_volume * n_volumes]) for T = passes.  RCU_ERR_INVALID for null pointers, n_words outside 1..2, passes outside
+ * 1..32 * n_words, n_per_volume outside 1..2^31-2, n_volumes outside 1..65535, n_per_volume * n_volumes >= 2^32. */
+int rcu_agreement_tables(const uint32_t* votes_dev, int n_words, size_t n_per_volume, int n_volumes, int passes, uint64_t* hist_dev,
+                         uint64_t* pairs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ RCU_BOUNDARY_MAX_BANDS = 64
 RCU_TEMPERATURE_MAX_CANDIDATES = 128
 # test-time logit sampling (include/rcu.h): samples per voxel
 RCU_LOGIT_MAX_SAMPLES = 1024
+# sample agreement (include/rcu.h): passes a vote plane holds (32 per uint32 word)
+RCU_VOTES_MAX_PASSES = 64
 TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
@@ -152,6 +154,10 @@ SIGNATURES = {
                                    c_void_p]),
     'rcu_unet_forward_sample_sigma_passes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, POINTER(c_uint64), c_uint64, c_int, c_void_p,
                                                      c_int, c_void_p, c_int, c_void_p]),
+    'rcu_unet_forward_accumulate_votes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, POINTER(c_int32),
+                                                  c_void_p]),
+    'rcu_mc_votes': (c_int, [c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'rcu_agreement_tables': (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

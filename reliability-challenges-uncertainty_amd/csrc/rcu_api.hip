@@ -1040,9 +1040,16 @@ struct HeadSampling {
     int samples;
 };
 
+// sample votes in the head (rcu_unet_forward_accumulate_votes): bit bits[t] of the plane for pass t
+struct HeadVotes {
+    uint32_t* plane;
+    int n_words;
+    const int32_t* bits;
+};
+
 static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, float* logits, float* sigma, void* stats,
                         int flags, hipStream_t stream, int passes = 1, float* sigma_sum = nullptr, int sigma_log = 0,
-                        const HeadSampling* sampling = nullptr)
+                        const HeadSampling* sampling = nullptr, const HeadVotes* votes = nullptr)
 {
     if (!h || !x) return fail(RCU_ERR_INVALID, "rcu_unet_forward: null argument");
     if (!h->finalized) return fail(RCU_ERR_STATE, "rcu_unet_forward before rcu_unet_finalize_weights");
@@ -1066,7 +1073,8 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     // rcu_unet_set_fuse_head keep them apart): two classes, no sigma twin, 32-cout Winograd tile; the passes of a pass group run back to back on the
     // workgroup that owns the tile, so their read-modify-writes of the statistics are ordered (pass 0 first, as head_kernel adds them)
     const ConvLayer& last = h->layers.back();
-    const bool fuse = head_fusable(h) && sigma == nullptr && (logits != nullptr || stats != nullptr) && h->opt.fuse_head != 0 && sampling == nullptr;
+    const bool fuse = head_fusable(h) && sigma == nullptr && (logits != nullptr || stats != nullptr) && h->opt.fuse_head != 0 && sampling == nullptr &&
+                      votes == nullptr;      // (the voting head is the separate kernel: same statistics bits, fused == unfused)
     for (const ConvLayer& L : h->layers) {
         const FusedHead fh{logits, stats, flags, passes};
         int rc = run_layer(h, L, n, masks, stream, (fuse && &L == &last) ? &fh : nullptr, direct_input ? x : nullptr, n_one);
@@ -1093,6 +1101,8 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     if (sampling) {
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "pass keys");
         RCU_HIP(launch_head_sampled(a, reinterpret_cast<const unsigned long long*>(sampling->keys), sampling->first_sample, sampling->samples, stream));
+    } else if (votes) {
+        RCU_HIP(launch_head_votes(a, votes->plane, votes->n_words, votes->bits, stream));
     } else {
         RCU_HIP(launch_head(a, stream));
     }
@@ -1348,6 +1358,46 @@ extern "C" int rcu_unet_forward_accumulate_passes(rcu_unet* h, const float* x_de
     if (!stats_dev) return fail(RCU_ERR_INVALID, "rcu_unet_forward_accumulate_passes: null stats");
     return forward_impl(h, x_dev, n, masks_dev, nullptr, nullptr, stats_dev, flags & (RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT),
                         static_cast<hipStream_t>(stream), passes);
+}
+
+static int check_vote_plane(const std::string& fn, int n_words)
+{
+    if (n_words < 1 || n_words > RCU_VOTES_MAX_PASSES / 32) return fail(RCU_ERR_INVALID, fn + ": n_words must be in 1..2, got " + std::to_string(n_words));
+    return RCU_OK;
+}
+static int check_vote_bit(const std::string& fn, int bit, int n_words)
+{
+    if (bit < 0 || bit >= 32 * n_words)
+        return fail(RCU_ERR_INVALID, fn + ": bit " + std::to_string(bit) + " outside [0, " + std::to_string(32 * n_words) + ")");
+    return RCU_OK;
+}
+
+extern "C" int rcu_unet_forward_accumulate_votes(rcu_unet* h, const float* x_dev, int n, int passes, const float* masks_dev, void* stats_dev,
+                                                 int flags, uint32_t* votes_dev, int n_words, const int32_t* bits_host, void* stream)
+{
+    const std::string fn = "rcu_unet_forward_accumulate_votes";
+    if (!h) return fail(RCU_ERR_INVALID, fn + ": null handle");
+    if (!x_dev || !stats_dev || !votes_dev || !bits_host) return fail(RCU_ERR_INVALID, fn + ": null x_dev / stats_dev / votes_dev / bits_host");
+    if (int st = check_vote_plane(fn, n_words)) return st;
+    if (h->d.nb_classes < 1 || h->d.nb_classes > MAX_CLASSES) return fail(RCU_ERR_INVALID, fn + ": nb_classes must be in 1..8");
+    if (n < 1 || passes < 1 || (long)n * passes > h->d.max_batch) return fail(RCU_ERR_INVALID, fn + ": batch size (times passes) outside 1..max_batch");
+    for (int t = 0; t < passes; ++t)
+        if (int st = check_vote_bit(fn, bits_host[t], n_words)) return st;
+    const HeadVotes votes{votes_dev, n_words, bits_host};
+    return forward_impl(h, x_dev, n, masks_dev, nullptr, nullptr, stats_dev, flags & (RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT),
+                        static_cast<hipStream_t>(stream), passes, nullptr, 0, nullptr, &votes);
+}
+
+extern "C" int rcu_mc_votes(const float* in_dev, size_t n, size_t hw, int nb_classes, int flags, uint32_t* votes_dev, int n_words, int bit, void* stream)
+{
+    const std::string fn = "rcu_mc_votes";
+    if (!in_dev || !votes_dev) return fail(RCU_ERR_INVALID, fn + ": null in_dev / votes_dev");
+    if (int st = check_vote_plane(fn, n_words)) return st;
+    if (int st = check_vote_bit(fn, bit, n_words)) return st;
+    if (nb_classes < 1 || nb_classes > MAX_CLASSES) return fail(RCU_ERR_INVALID, fn + ": nb_classes must be in 1..8");
+    if (n * hw == 0) return RCU_OK;
+    RCU_HIP(launch_mc_votes(in_dev, nb_classes, n, hw, flags & RCU_MC_INPUT_PROBS, votes_dev, bit, static_cast<hipStream_t>(stream)));
+    return RCU_OK;
 }
 
 extern "C" int rcu_unet_num_layers(const rcu_unet* h) { return h ? (int)h->layers.size() : 0; }

@@ -254,6 +254,20 @@ struct SampleArgs {
 };
 hipError_t launch_head_sampled(const HeadArgs& a, const unsigned long long* keys_host, unsigned long long first_sample, int samples,
                                hipStream_t stream);
+// sample votes (include/rcu.h "Sample agreement"): the head kernels' VOTES variant also ORs, for every pass of the launch, the bit "this pass's
+// arg-max at the voxel is not class 0" into the voxel's word of a vote plane.  All passes of one launch vote into ONE word;
+// launch_head_votes splits a pass group at word boundaries (and at SAMPLE_MAX_PASSES passes), in pass order.  bits_host: a.passes bit
+// indices in [0, 32 * n_words).  a.stats is required, logits / sigma outputs and the sigma sum are not part of this form.
+constexpr int VOTES_MAX_PASSES = RCU_VOTES_MAX_PASSES;
+struct VoteArgs {
+    uint32_t* plane;                              // [n_words][V]
+    int n_words;
+    int word;                                     // the word the passes of this launch vote into
+    unsigned char bit[SAMPLE_MAX_PASSES];         // bit of pass t of the launch inside that word
+};
+hipError_t launch_head_votes(const HeadArgs& a, uint32_t* votes, int n_words, const int32_t* bits_host, hipStream_t stream);
+// the standalone form over a materialised [n][C][hw] volume of logits or (MC_INPUT_PROBS) probabilities
+hipError_t launch_mc_votes(const float* in_nchw, int C, size_t N, size_t HW, int flags, uint32_t* votes, int bit, hipStream_t stream);
 // standalone forms over materialised [n][C][hw] logits and raw sigma (rcu_logit_sampling.hip)
 hipError_t launch_logit_normals(unsigned long long key, unsigned long long first_sample, size_t n, size_t hw, int C, int samples, float* out,
                                 hipStream_t stream);

@@ -305,8 +305,20 @@ __global__ __launch_bounds__(PW_THREADS) void head_stream_sample_kernel(const He
     head_stream_body<C, true, true>(a, &sa);
 }
 
-template <int C, bool SIG, int CPH, bool SAMPLE>
-__device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* sa)
+// the vote of a pass at a voxel: 1 where the arg-max of the vector it adds to the statistics is not class 0 (first maximum, as argmax_fg_kernel)
+template <int C>
+__device__ __forceinline__ uint32_t head_vote(const float (&p)[C])
+{
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < C; ++c) best = (p[c] > p[best]) ? c : best;
+    return best != 0 ? 1u : 0u;
+}
+
+// VOTES (launch_head_votes; statistics required): the voxel's word of the vote plane is loaded beside the statistics entries, every pass of the
+// launch ORs its bit in registers, and the word is stored once.  Launches of a lane are stream-ordered and a lane has its own plane: no atomics.
+template <int C, bool SIG, int CPH, bool SAMPLE, bool VOTES = false>
+__device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* sa, const VoteArgs* va = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const size_t wave_id = ((size_t)blockIdx.x * PW_THREADS + threadIdx.x) >> 6;
@@ -318,12 +330,14 @@ __device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* s
         VoxelStats<C> st;
         const size_t n = v / a.HW, hw = v % a.HW;
         float ssum[C];   // sigma-head extension: the voxel's running sigma sum, added to in pass order like the statistics
+        uint32_t word = 0u;
         if (v < a.V) {
             st.load(a.stats, v, a.V, a.stats_flags);
             if (SIG && a.sigma_sum != nullptr) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) ssum[c] = a.sigma_sum[(n * C + c) * a.HW + hw];
             }
+            if constexpr (VOTES) word = va->plane[(size_t)va->word * a.V + v];
         }
         for (int t = 0; t < a.passes; ++t) {
             head_logits<C, SIG, CPH>(a, a.act + (size_t)t * a.V * a.CP, v0, lane, l, s);
@@ -334,6 +348,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* s
             for (int c = 0; c < C; ++c) sg[c] = SIG ? sigma_of_raw(s[c] + a.b_sig[c], a.sigma_log) : 0.f;
             head_predictive<C, SAMPLE>(l, sg, sa, t, n, hw);
             st.add(a.stats_flags, l);
+            if constexpr (VOTES) word |= head_vote<C>(l) << va->bit[t];
             if (SIG && a.sigma_sum != nullptr) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) ssum[c] += sg[c];
@@ -341,6 +356,7 @@ __device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* s
         }
         if (v < a.V) {
             st.store(a.stats, v, a.V, a.stats_flags);
+            if constexpr (VOTES) va->plane[(size_t)va->word * a.V + v] = word;
             if (SIG && a.sigma_sum != nullptr) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) a.sigma_sum[(n * C + c) * a.HW + hw] = ssum[c];
@@ -352,8 +368,15 @@ __device__ __forceinline__ void head_body(const HeadArgs& a, const SampleArgs* s
     // instead of behind the softmax (load all planes, add, store all planes: the operations -- and bits -- of accumulate_voxel)
     VoxelStats<C> st;
     if (a.stats != nullptr && v < a.V) st.load(a.stats, v, a.V, a.stats_flags);
+    uint32_t word = 0u;
+    if constexpr (VOTES) {
+        if (v < a.V) word = va->plane[(size_t)va->word * a.V + v];
+    }
     head_logits<C, SIG, CPH>(a, a.act, v0, lane, l, s);
     head_finish<C, SIG, SAMPLE>(a, v, l, s, st, sa);
+    if constexpr (VOTES) {      // (head_finish has left the pass's predictive in l: the statistics are required here)
+        if (v < a.V) va->plane[(size_t)va->word * a.V + v] = word | (head_vote<C>(l) << va->bit[0]);
+    }
 }
 
 template <int C, bool SIG, int CPH>
@@ -367,6 +390,13 @@ template <int C, int CPH>
 __global__ __launch_bounds__(PW_THREADS) void head_sample_kernel(const HeadArgs a, const SampleArgs sa)
 {
     head_body<C, true, CPH, true>(a, &sa);
+}
+
+// the voting instantiation (no sigma twin; pass t of the launch votes bit va.bit[t] of word va.word)
+template <int C, int CPH>
+__global__ __launch_bounds__(PW_THREADS) void head_votes_kernel(const HeadArgs a, const VoteArgs va)
+{
+    head_body<C, false, CPH, false, true>(a, nullptr, &va);
 }
 
 #define RCU_DISPATCH_C(Cval, ...)                                    \
@@ -439,6 +469,65 @@ hipError_t launch_head_sampled(const HeadArgs& a, const unsigned long long* keys
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_head_votes(const HeadArgs& a, uint32_t* votes, int n_words, const int32_t* bits_host, hipStream_t stream)
+{
+    if (a.stats == nullptr || votes == nullptr || bits_host == nullptr || a.logits != nullptr || a.sigma != nullptr || a.sigma_sum != nullptr)
+        return hipErrorInvalidValue;
+    const bool c32 = a.CPh == 32 && a.V > 0;
+    const int passes = a.passes < 1 ? 1 : a.passes;
+    // one launch per run of passes that share a word (at most SAMPLE_MAX_PASSES of them), in pass order: each adds its passes into the statistics
+    // the previous one stored
+    for (int first = 0; first < passes;) {
+        VoteArgs va{};
+        va.plane = votes;
+        va.n_words = n_words;
+        va.word = bits_host[first] / 32;
+        int count = 0;
+        while (first + count < passes && count < SAMPLE_MAX_PASSES && bits_host[first + count] / 32 == va.word) {
+            va.bit[count] = (unsigned char)(bits_host[first + count] % 32);
+            ++count;
+        }
+        HeadArgs b = a;
+        b.act = a.act + (size_t)first * a.V * a.CP;
+        b.passes = count;
+        if (c32) {
+            RCU_DISPATCH_C(b.C, hipLaunchKernelGGL((head_votes_kernel<C_, 32>), dim3(grid_for(b.V)), dim3(PW_THREADS), 0, stream, b, va));
+        } else {
+            RCU_DISPATCH_C(b.C, hipLaunchKernelGGL((head_votes_kernel<C_, 0>), dim3(grid_for(b.V)), dim3(PW_THREADS), 0, stream, b, va));
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        first += count;
+    }
+    return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------- standalone votes
+// bit `bit` of the voxel's vote word |= (arg-max of the pass's probabilities != 0); logits go through softmax first, as they do on their way into
+// the statistics (mc_accumulate_kernel): the vote is the arg-max of the vector the statistics receive
+template <int C>
+__global__ __launch_bounds__(PW_THREADS) void mc_votes_kernel(const float* __restrict__ in, size_t HW, size_t V, int flags, uint32_t* __restrict__ plane,
+                                                               int bit)
+{
+    const size_t v = (size_t)blockIdx.x * PW_THREADS + threadIdx.x;
+    if (v >= V) return;
+    const size_t n = v / HW, hw = v % HW;
+    float l[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) l[c] = in[(n * C + c) * HW + hw];
+    const uint32_t word = plane[v];
+    if (!(flags & MC_INPUT_PROBS)) softmax_inplace<C>(l);
+    plane[v] = word | (head_vote<C>(l) << bit);
+}
+
+hipError_t launch_mc_votes(const float* in, int C, size_t N, size_t HW, int flags, uint32_t* votes, int bit, hipStream_t stream)
+{
+    const size_t V = N * HW;
+    RCU_DISPATCH_C(C, hipLaunchKernelGGL(mc_votes_kernel<C_>, dim3(grid_for(V)), dim3(PW_THREADS), 0, stream, in, HW, V, flags,
+                                         votes + (size_t)(bit / 32) * V, bit % 32));
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------- standalone accumulate

@@ -473,8 +473,11 @@ class ShardedMcPredictStep(_ShardedStepBase):
     the step with the SAME batch; the root's batch context receives what ``McPredictStep`` leaves there."""
 
     def __init__(self, mc_steps, world, do_mi=False, do_var=False, masks=None, ws_pass=True, group_pixels=None, lanes=None, seed=0,
-                 exact=True, ws_transport=None, engine_factory=None) -> None:
+                 exact=True, ws_transport=None, engine_factory=None, agreement=False) -> None:
         super().__init__(world, do_mi, do_var, lanes, exact, engine_factory)
+        if agreement:
+            raise ValueError('agreement (others.agreement, sample votes) is not sharded: a vote plane lives on the one process that runs all passes '
+                             '(steps.McPredictStep)')
         if seed is None:
             raise ValueError('a sharded MC step needs a seed: the masks of a pass must not depend on the rank that runs it')
         self.mc_steps, self.masks, self.ws_pass, self.seed = mc_steps, masks, ws_pass, seed

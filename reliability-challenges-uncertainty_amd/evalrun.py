@@ -44,6 +44,13 @@ BOUNDARY_PLACEHOLDER = 'eval_boundary_{}.csv'
 BOUNDARY_POOLED_PLACEHOLDER = 'eval_boundary_pooled_{}.csv'
 BOUNDARY_BANDS_PLACEHOLDER = 'eval_boundary_bands_{}.csv'
 
+# rcu_amd extension (the 'agreement' action), in UNCERTAINTY_NAME as well; AGREEMENT_FILE is what the test script wrote into the run directory
+AGREEMENT_PLACEHOLDER = 'eval_agreement_{}.csv'
+AGREEMENT_POOLED_PLACEHOLDER = 'eval_agreement_pooled_{}.csv'
+AGREEMENT_FILE = 'agreement.csv'
+# score -> whether a HIGH value points at a failed segmentation (the agreement scores are low there, the volume spread is high)
+AGREEMENT_SCORES = {'mean_pairwise_dice': False, 'min_pairwise_dice': False, 'pooled_pairwise_dice': False, 'iou_all': False, 'volume_cv': True}
+
 CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities', 'center': 'probabilities',
                     'center_mc': 'probabilities', 'ensemble': 'probabilities', 'auxiliary_feat': 'confidence',
                     'auxiliary_segm': 'confidence', 'aleatoric': 'sigma'}   # evaldata.py:21-47
@@ -642,10 +649,80 @@ class BoundaryAction(UncertaintyAction):
                                     [float(bands[k][side, band]) for k in ev.BOUNDARY_BAND_KEYS])
 
 
+def read_agreement_csv(path):
+    """``agreement.csv`` of a test run (scripts.AgreementCsvHook) -> {subject: {column: float}}."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError('{} is missing: the agreement action reads what the default test scripts write with "others.agreement: true" '
+                                '(next to others.mc) in the YAML file'.format(path))
+    with open(path, newline='') as f:
+        return {row['subject']: {k: float(v) for k, v in row.items() if k != 'subject'} for row in csv.DictReader(f)}
+
+
+def agreement_pooled_rows(dice, scores, dice_fail):
+    """Per score of ``scores`` ({name: values in subject order}): Pearson and Spearman correlation with ``dice`` and the AUROC of detecting
+    ``dice < dice_fail`` by the score (evaluation.failure_auroc; NaN where undefined) -> rows (score, pearson, spearman, auroc, subjects, failed)."""
+    dice = np.asarray(dice, dtype=np.float64)
+    failed = dice < float(dice_fail)
+    rows = []
+    for name, values in scores.items():
+        values = np.asarray(values, dtype=np.float64)
+        rows.append([name, ev.pearson(values, dice), ev.spearman(values, dice), ev.failure_auroc(values, failed, AGREEMENT_SCORES.get(name, False)),
+                     int(dice.size), int(failed.sum())])
+    return rows
+
+
+class AgreementAction(EvalAction):
+    """EXTENSION (the reference has no such action): do the structure-wise uncertainties of the MC samples (``agreement.csv`` of the run, written
+    by the default test scripts under ``others.agreement: true``) flag the failed segmentations?  Files in ``<base_dir>/uncertainty``:
+      eval_agreement_<id>.csv          one row per subject: dice (prediction against ground truth), then the scores of agreement.csv
+      eval_agreement_pooled_<id>.csv   one row per score: Pearson and Spearman correlation with Dice over the subjects, AUROC of detecting
+                                       dice < ``dice_fail`` by the score (low agreement / high volume spread = failure; ties count half)"""
+
+    def __init__(self, base_dir, dice_fail=0.8):
+        super().__init__()
+        self.dice_fail = float(dice_fail)
+        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.table, self.dice, self.scores = {}, [], {}
+
+    def setup_eval(self, eval_data):
+        self.id_ = eval_data.id_
+        self.prepare = None
+        self.load_params = Loader.Params(eval_data.confidence_entry)
+        self.table = read_agreement_csv(os.path.join(eval_data.eval_path, AGREEMENT_FILE))
+        self.dice, self.scores = [], {k: [] for k in AGREEMENT_SCORES}
+        hook = WriteCsvHook(os.path.join(self.out_dir, AGREEMENT_PLACEHOLDER.format(self.id_)), entries=('dice',) + tuple(AGREEMENT_SCORES))
+        self.eval_cases = [EvalCase(None, hook)]
+
+    def record_dice(self, dice, subject_name):
+        row = self.table.get(str(subject_name))
+        if row is None:
+            raise ValueError('{} has no row for subject {}'.format(AGREEMENT_FILE, subject_name))
+        results = {'dice': dice}
+        results.update({k: row[k] for k in AGREEMENT_SCORES})
+        self.eval_cases[0].record(results, subject_name, self.id_)
+        self.dice.append(dice)
+        for k in AGREEMENT_SCORES:
+            self.scores[k].append(row[k])
+
+    def eval_subject(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        tp, _, fp, fn, _ = ev.confusion_matrx(to_eval['prediction'], to_eval['target'])
+        self.record_dice(ev._dice(tp, fp, fn), sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        with open(os.path.join(self.out_dir, AGREEMENT_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id', 'score', 'pearson', 'spearman', 'auroc_dice_below_{}'.format(self.dice_fail), 'subjects', 'failed'])
+            for row in agreement_pooled_rows(self.dice, self.scores, self.dice_fail):
+                writer.writerow([self.id_] + row)
+
+
 ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
-def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10):
+def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8):
     """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
     (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice) and 'boundary' (``bands``: its distance bands, 1..64;
     ``levels``: of its off-border level histogram)."""
@@ -665,6 +742,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'boundary':
             actions.append(BoundaryAction(levels, bands, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'agreement':      # (``dice_fail``: the Dice below which a segmentation counts as failed)
+            actions.append(AgreementAction(base_dir, dice_fail))
     return actions
 
 
@@ -755,7 +834,8 @@ def _fusable(entry, actions):
     evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script, 'ue_curves', 'components' and 'boundary'."""
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
-            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction)
+            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction,
+                            AgreementAction)
                 for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
@@ -766,7 +846,7 @@ def metrics_wanted(actions):
     by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
-           (['ue'] if (CorrectionAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
+           (['ue'] if (CorrectionAction in by_type or AgreementAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
            (['ue_hist'] if UeCurvesAction in by_type else []) + \
            (['components'] if ComponentsAction in by_type else []) + \
            (['boundary'] if BoundaryAction in by_type else [])
@@ -811,6 +891,9 @@ def record_subject(actions, subject, res, slot, n_dim):
             action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
         elif isinstance(action, BoundaryAction):
             action.record_boundary(*res['boundary'][slot], subject)
+        elif isinstance(action, AgreementAction):      # (the counts are there whenever the action is: metrics_wanted)
+            tp, _, fp, fn = (int(v) for v in counts[0][:4])
+            action.record_dice(ev._dice(tp, fp, fn), subject)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -879,14 +962,14 @@ class _Done:
 
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
-                  connectivity=26, bands=10):
+                  connectivity=26, bands=10, dice_fail=0.8):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
     'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action."""
-    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands)
+    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

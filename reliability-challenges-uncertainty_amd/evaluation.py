@@ -897,6 +897,139 @@ def error_precision(tpu, tnu, fpu, fnu):
     return (fnu + fpu) / (fnu + fpu + tpu + tnu)
 
 
+# ------------------------------------------------ sample agreement (EXTENSION; include/rcu.h "Sample agreement")
+AGREEMENT_KEYS = ('passes', 'mean_pairwise_dice', 'min_pairwise_dice', 'pooled_pairwise_dice', 'iou_all', 'volume_mean', 'volume_cv', 'union',
+                  'intersection')
+
+
+def agreement_row_length(passes):
+    """Entries of one ``hist`` + ``pairs`` row for T passes: (T + 1) + T (T + 1) / 2."""
+    return (passes + 1) + passes * (passes + 1) // 2
+
+
+def agreement_tables_on_device(plane, passes, n_volumes=1):
+    """A device int32 vote plane ``[n_words, ...]`` of ``n_volumes`` equal volumes -> device int64 (hist ``[n_volumes, T + 1]``, pairs
+    ``[n_volumes, T (T + 1) / 2]``, the packed upper triangle), asynchronous on the current stream (rcu_agreement_tables)."""
+    passes, n_volumes = int(passes), int(n_volumes)
+    if not 1 <= passes <= _lib.RCU_VOTES_MAX_PASSES:
+        raise ValueError('passes must be in 1..{}, got {}'.format(_lib.RCU_VOTES_MAX_PASSES, passes))
+    if plane.dtype != torch.int32 or not plane.is_contiguous() or plane.dim() < 2:
+        raise ValueError('a vote plane is a contiguous int32 tensor [n_words, ...]')
+    n_words, total = plane.shape[0], plane[0].numel()
+    if n_words != (passes + 31) // 32:
+        raise ValueError('{} passes need a plane of {} words, got {}'.format(passes, (passes + 31) // 32, n_words))
+    if n_volumes < 1 or total % n_volumes:
+        raise ValueError('the plane does not split into {} equal volumes'.format(n_volumes))
+    hist = torch.empty((n_volumes, passes + 1), device=plane.device, dtype=torch.int64)
+    pairs = torch.empty((n_volumes, passes * (passes + 1) // 2), device=plane.device, dtype=torch.int64)
+    _lib.check(_lib.load().rcu_agreement_tables(_lib.ptr(plane), n_words, total // n_volumes, n_volumes, passes, _lib.ptr(hist), _lib.ptr(pairs),
+                                                _lib.current_stream()))
+    return hist, pairs
+
+
+def unpack_pairs(packed, passes):
+    """The packed upper triangle(s) ``[..., T (T + 1) / 2]`` -> symmetric ``[..., T, T]`` int64."""
+    packed = np.asarray(packed, dtype=np.int64)
+    iu = np.triu_indices(passes)
+    full = np.zeros(packed.shape[:-1] + (passes, passes), dtype=np.int64)
+    full[..., iu[0], iu[1]] = packed
+    full[..., iu[1], iu[0]] = packed
+    return full
+
+
+def agreement_tables(votes, passes, n_volumes=1):
+    """The agreement tables of a vote plane (a ``steps.SampleVotes``, or an int32 / uint32 array or tensor ``[n_words, ...]``) split into
+    ``n_volumes`` equal volumes -> numpy int64 (hist ``[n_volumes, T + 1]``, pairs ``[n_volumes, T, T]`` symmetric with the sample volumes on
+    the diagonal)."""
+    plane = getattr(votes, 'plane', votes)
+    if not isinstance(plane, torch.Tensor):
+        plane = np.ascontiguousarray(plane)
+        if plane.dtype == np.uint32:
+            plane = plane.view(np.int32)
+        plane = torch.from_numpy(plane)
+    plane = plane.to(device=_device(), dtype=torch.int32).contiguous()
+    hist, pairs = agreement_tables_on_device(plane, passes, n_volumes)
+    return hist.cpu().numpy(), unpack_pairs(pairs.cpu().numpy(), int(passes))
+
+
+def agreement_metrics(hist, pairs):
+    """The structure-wise uncertainties (Roy et al., Bayesian QuickNAT, 2019) of ONE table -- a subject's, or the sum of its slices': ``hist``
+    ``[T + 1]`` and ``pairs`` ``[T, T]`` symmetric (or the packed upper triangle) -> dict with ``AGREEMENT_KEYS``.  Host float64 arithmetic;
+    n_i = pairs[i][i] the sample volumes, I_ij = pairs[i][j]."""
+    hist = np.asarray(hist, dtype=np.int64).reshape(-1)
+    t = hist.size - 1
+    pairs = np.asarray(pairs, dtype=np.int64)
+    if pairs.ndim == 1:
+        pairs = unpack_pairs(pairs, t)
+    if t < 1 or pairs.shape != (t, t):
+        raise ValueError('agreement_metrics takes hist [T + 1] and pairs [T, T] of one table')
+    n = np.diag(pairs).astype(np.float64)
+    dices = []
+    for i in range(t):
+        for j in range(i + 1, t):
+            den = n[i] + n[j]
+            dices.append(2.0 * float(pairs[i, j]) / den if den > 0 else 1.0)
+    inter_sum = float(sum(int(pairs[i, j]) for i in range(t) for j in range(i + 1, t)))
+    total = float(n.sum())
+    union = int(hist[1:].sum())
+    mean = total / t
+    return {
+        'passes': t,
+        'mean_pairwise_dice': float(np.mean(dices)) if dices else 1.0,
+        'min_pairwise_dice': float(np.min(dices)) if dices else 1.0,
+        'pooled_pairwise_dice': 2.0 * inter_sum / ((t - 1) * total) if (t > 1 and total > 0) else 1.0,
+        'iou_all': float(hist[t]) / union if union > 0 else 1.0,
+        'volume_mean': mean,
+        'volume_cv': float(np.std(n)) / mean if mean > 0 else 0.0,
+        'union': union,
+        'intersection': int(hist[t]),
+    }
+
+
+def spearman(a, b):
+    """Spearman's rank correlation of two equally long sequences: Pearson's r of the average ranks (ties share the mean of their ranks);
+    NaN for fewer than two points or a constant sequence."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return pearson(average_ranks(a), average_ranks(b))
+
+
+def average_ranks(x):
+    x = np.asarray(x, dtype=np.float64)
+    order = np.argsort(x, kind='mergesort')
+    ranks = np.empty(x.size, dtype=np.float64)
+    i = 0
+    while i < x.size:
+        j = i
+        while j + 1 < x.size and x[order[j + 1]] == x[order[i]]:
+            j += 1
+        ranks[order[i:j + 1]] = 0.5 * (i + j) + 1.0
+        i = j + 1
+    return ranks
+
+
+def pearson(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.size != b.size:
+        raise ValueError('sequences differ in length')
+    if a.size < 2:
+        return float('nan')
+    da, db = a - a.mean(), b - b.mean()
+    den = math.sqrt(float(da @ da) * float(db @ db))
+    return float(da @ db) / den if den > 0 else float('nan')
+
+
+def failure_auroc(score, failed, higher_is_worse):
+    """AUROC of detecting the subjects with ``failed`` true by ranking them on ``score`` (through ``_rank_metrics``: ties count half);
+    ``higher_is_worse`` false ranks by -score (an agreement score is LOW where the segmentation fails).  NaN without both classes."""
+    score = np.asarray(score, dtype=np.float64) * (1.0 if higher_is_worse else -1.0)
+    failed = np.asarray(failed, dtype=bool)
+    groups = []
+    for value in np.unique(score):
+        here = score == value
+        groups.append((int((here & failed).sum()), int((here & ~failed).sum())))
+    return _rank_metrics(groups)[0]
+
+
 # pymia 0.2.1 ConfusionMatrix / DiceCoefficient / Accuracy are absent from the reference tree: restated from the call sites
 # (numpyfunctions.py:128-151) and pinned against scikit-learn's confusion_matrix / f1_score / accuracy_score (fixture g19); the 0 / 0
 # Dice (no foreground in prediction and target) is 1, pymia's convention.

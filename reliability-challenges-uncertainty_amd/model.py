@@ -374,35 +374,44 @@ class UNet(nn.Module):
         nhwc = _lib.device_view(ptr.value, (n, h, w, pitch.value), device, owner=self)
         return nhwc[..., :ch.value].permute(0, 3, 1, 2)
 
-    def forward_accumulate(self, x, stats, masks=None, passes=1, lane=0):
+    def forward_accumulate(self, x, stats, masks=None, passes=1, lane=0, votes=None, bits=None):
         """One pass -- or ``passes`` stochastic passes as ONE batch of N * passes samples -- fused with softmax +
         accumulation into ``stats`` (rcu_amd.steps.McStatistics): neither logits nor probabilities reach HBM.
         ``masks`` for a pass group: a concatenated device tensor with N * passes rows per site, or a list of
-        ``passes`` mask sets (each a concatenated tensor or a list of per-site ``[N, C_site]`` arrays)."""
+        ``passes`` mask sets (each a concatenated tensor or a list of per-site ``[N, C_site]`` arrays).
+        ``votes`` (rcu_amd.steps.SampleVotes) with ``bits`` (one bit index per pass; pass j of a step owns bit j - 1): every pass also sets its
+        bit of the vote plane where its arg-max is not background (include/rcu.h rcu_unet_forward_accumulate_votes; same statistics)."""
         x = self._check_input(x)
         n, _, h, w = x.shape
         if (n, self.nb_classes, h * w) != (stats.n, stats.nb_classes, stats.hw):
             raise ValueError('statistics blob shape does not match the batch')
         if passes < 1:
             raise ValueError('passes must be >= 1')
+        if votes is not None:
+            bits = [int(b) for b in (bits if bits is not None else ())]
+            if len(bits) != passes:
+                raise ValueError('a voting pass needs one bit per pass (bits)')
+            if tuple(votes.plane.shape[1:]) != (n, h, w) or votes.plane.device != x.device:
+                raise ValueError('vote plane shape does not match the batch')
+            if any(not 0 <= b < 32 * votes.n_words for b in bits):
+                raise ValueError('vote bits must be in [0, {})'.format(32 * votes.n_words))
         handle = self._handle(h, w, n * passes, lane)
-        if passes == 1:
-            if masks is None and self.mc_active():
-                masks = self.sample_masks(n, x.device)
-            elif isinstance(masks, (list, tuple)):
-                masks = self.pack_masks(masks, n, x.device)
-            _lib.check(_lib.load().rcu_unet_forward_accumulate(handle, _lib.ptr(x), n, _lib.ptr(masks),
-                                                               _lib.ptr(stats.blob), stats.flags, _lib.current_stream()))
+        if masks is None:
+            if passes > 1 and not self.mc_active():
+                raise ValueError('a pass group needs stochastic passes: set_dropout_mode(model, True) or inject masks')
+            masks = self.sample_masks(n * passes, x.device) if self.mc_active() else None
+        elif isinstance(masks, (list, tuple)):
+            masks = self.group_masks(masks, n, x.device) if passes > 1 else self.pack_masks(masks, n, x.device)
+        lib, stream = _lib.load(), _lib.current_stream()
+        if votes is not None:
+            status = lib.rcu_unet_forward_accumulate_votes(handle, _lib.ptr(x), n, passes, _lib.ptr(masks), _lib.ptr(stats.blob), stats.flags,
+                                                           _lib.ptr(votes.plane), votes.n_words, (ctypes.c_int32 * passes)(*bits), stream)
+        elif passes == 1:
+            status = lib.rcu_unet_forward_accumulate(handle, _lib.ptr(x), n, _lib.ptr(masks), _lib.ptr(stats.blob), stats.flags, stream)
         else:
-            if masks is None:
-                if not self.mc_active():
-                    raise ValueError('a pass group needs stochastic passes: set_dropout_mode(model, True) or inject masks')
-                masks = self.sample_masks(n * passes, x.device)
-            elif isinstance(masks, (list, tuple)):
-                masks = self.group_masks(masks, n, x.device)
-            _lib.check(_lib.load().rcu_unet_forward_accumulate_passes(handle, _lib.ptr(x), n, passes, _lib.ptr(masks),
-                                                                      _lib.ptr(stats.blob), stats.flags,
-                                                                      _lib.current_stream()))
+            status = lib.rcu_unet_forward_accumulate_passes(handle, _lib.ptr(x), n, passes, _lib.ptr(masks), _lib.ptr(stats.blob), stats.flags,
+                                                            stream)
+        _lib.check(status)
         stats.count += passes
 
     def forward_accumulate_sigma(self, x, stats, sigma_sum, masks=None, is_log_sigma=False, lane=0, passes=1):

@@ -12,6 +12,7 @@ Each function is the ``main`` of the same-named reference script (flags unchange
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
 """
+import csv
 import json
 import logging
 import os
@@ -387,6 +388,62 @@ def _refuse_logit_samples(context, script):
                          .format(script))
 
 
+def _refuse_agreement(context, script):
+    if hasattr(context.config.others, 'agreement'):
+        raise ValueError('others.agreement (MC sample agreement) applies to the default test scripts with others.mc only; the {} script does not '
+                         'take it'.format(script))
+
+
+def _agreement(context, world):
+    """``others.agreement: true`` (an rcu_amd extension, include/rcu.h "Sample agreement"): the T = ``others.mc`` samples of a subject compared as
+    whole segmentations -> ``<test_dir>/agreement.csv``.  One process, MC dropout alone: a ValueError that names the key otherwise."""
+    if not hasattr(context.config.others, 'agreement'):
+        return False
+    value = context.config.others.agreement
+    if not isinstance(value, bool):
+        raise ValueError('others.agreement must be true or false, got {!r}'.format(value))
+    if not value:
+        return False
+    if hasattr(context.config.others, 'tta'):
+        raise ValueError('others.agreement does not compose with others.tta (test-time augmentation): the vote plane holds the passes of MC dropout alone')
+    if not hasattr(context.config.others, 'mc'):
+        raise ValueError('others.agreement needs others.mc: there are no samples to compare without MC dropout passes')
+    if world.world > 1:
+        raise ValueError('others.agreement is not sharded: run the script in one process (a vote plane lives where all passes of a batch run)')
+    steps.check_agreement_passes(context.config.others.mc)
+    return True
+
+
+class AgreementCsvHook(loops.TestLoopHook):
+    """``others.agreement``: ``<test_dir>/agreement.csv``, one row per subject -- subject, the metrics of ``evaluation.agreement_metrics`` on the sum
+    of the subject's slice rows (``output['agreement']``, assembled like ``'confusion'``), then the sample volumes volume_1..volume_T."""
+
+    def __init__(self, passes, file_name='agreement.csv'):
+        self.passes, self.file_name = int(passes), file_name
+        self.rows = []
+
+    def on_test_start(self, task_context, context):
+        self.rows.clear()
+
+    def on_test_subject_end(self, subject_context, task_context, context):
+        data = subject_context.subject_data
+        rows = data.get('agreement')
+        if rows is None:
+            raise ValueError('others.agreement: subject {} came without its agreement rows'.format(subject_context.subject_index))
+        t = self.passes
+        total = np.asarray(rows, dtype=np.int64).reshape(-1, ev.agreement_row_length(t)).sum(axis=0)
+        hist, pairs = total[:t + 1], ev.unpack_pairs(total[t + 1:], t)
+        metrics = ev.agreement_metrics(hist, pairs)
+        subject = data.get('subject', subject_context.subject_index)
+        self.rows.append([subject] + [metrics[k] for k in ev.AGREEMENT_KEYS] + [int(pairs[i, i]) for i in range(t)])
+
+    def on_test_end(self, task_context, context):
+        with open(os.path.join(context.test_dir, self.file_name), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['subject'] + list(ev.AGREEMENT_KEYS) + ['volume_{}'.format(i + 1) for i in range(self.passes)])
+            writer.writerows(self.rows)
+
+
 def _logit_samples(context):
     """``others.logit_samples`` (an rcu_amd extension): S in 1..RCU_LOGIT_MAX_SAMPLES, or None when the key is absent."""
     if not hasattr(context.config.others, 'logit_samples'):
@@ -445,7 +502,10 @@ def _temperature_hooks(context):
 
 def _default_steps(context, world):
     if hasattr(context.config.others, 'tta'):
+        _agreement(context, world)      # (refuses others.agreement: true)
         return _tta_steps(context, world)
+    if not hasattr(context.config.others, 'mc'):
+        _agreement(context, world)
     if hasattr(context.config.others, 'mc'):
         lanes = _other(context, 'stream_lanes')
         # ``others.group_pixels`` / ``others.exact`` (rcu_amd extensions): the memory / reproducibility trade of the MC step.  Every stream lane of every
@@ -453,6 +513,10 @@ def _default_steps(context, world):
         # batch) and ``exact`` keeps the statistics as exact float64 sums; a smaller ``group_pixels`` (or ``stream_lanes: 1``) shrinks the workspace,
         # ``exact: false`` halves the statistics and the reduce at the price of byte-identity across lanes, groups and world sizes.
         group_pixels, exact = _other(context, 'group_pixels'), bool(_other(context, 'exact', True))
+        if _agreement(context, world):      # (one process: refused above otherwise)
+            return [steps.McPredictStep(context.config.others.mc, seed=_mask_seed(context, world), lanes=lanes, group_pixels=group_pixels, exact=exact,
+                                        agreement=True),
+                    steps.MultiPredictionSummary(), steps.SampleAgreementStep()]
         if world.world > 1:     # the T + 1 passes of every batch sharded over the ranks, one sum-reduce per batch (rcu_amd.distributed)
             return [rdist.ShardedMcPredictStep(context.config.others.mc, world, seed=_mask_seed(context, world), lanes=lanes,
                                                group_pixels=group_pixels, exact=exact),
@@ -505,7 +569,8 @@ def _context(device, config_file):
     return context, world
 
 
-def _run(context, dataset, test_steps, write_hook, entries, world=None, startup_hooks=()):
+def _run(context, dataset, test_steps, write_hook, entries, world=None, startup_hooks=(), subject_hooks=()):
+    """``startup_hooks`` run on every rank; ``subject_hooks`` (per-subject writers such as AgreementCsvHook) on the root alone, behind the write hook."""
     world = world if world is not None else rdist.World()
     sharded = [s_ for s_ in test_steps if isinstance(s_, rdist._ShardedStepBase)]
     if world.world > 1 and not sharded:
@@ -515,7 +580,7 @@ def _run(context, dataset, test_steps, write_hook, entries, world=None, startup_
             return context
     build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
     options = _loop_options(context)
-    extra_hooks = list(startup_hooks)
+    extra_hooks = list(startup_hooks) + list(subject_hooks)
     spec = _other(context, 'device_metrics')
     if spec and world.is_root:      # opt-in: the evaluation's metrics on the maps while they are in HBM (DeviceMetricsHook)
         store = {}
@@ -587,14 +652,20 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     _refuse_logit_samples(context, 'default')
     entries = ('probabilities',) if dataset == 'brats' else None
-    return _run(context, dataset, _default_steps(context, world), WriteHook(link_inputs=dataset == 'isic'), entries, world,
-                startup_hooks=_temperature_hooks(context))
+    test_steps = _default_steps(context, world)
+    extra = []
+    if any(isinstance(s_, steps.SampleAgreementStep) for s_ in test_steps):
+        entries = None if entries is None else entries + ('agreement',)
+        extra.append(AgreementCsvHook(context.config.others.mc))
+    return _run(context, dataset, test_steps, WriteHook(link_inputs=dataset == 'isic'), entries, world,
+                startup_hooks=_temperature_hooks(context), subject_hooks=extra)
 
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_ensemble.yaml'.format(dataset)))
     _refuse_tta(context, 'ensemble')
     _refuse_temperature(context, 'ensemble')
+    _refuse_agreement(context, 'ensemble')
     _refuse_logit_samples(context, 'ensemble')
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
@@ -609,6 +680,7 @@ def test_aleatoric(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_aleatoric.yaml'.format(dataset)))
     _refuse_tta(context, 'aleatoric')
     _refuse_temperature(context, 'aleatoric')
+    _refuse_agreement(context, 'aleatoric')
     return _run(context, dataset, _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world)
 
@@ -751,6 +823,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_feat.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_feat')
     _refuse_temperature(context, 'auxiliary_feat')
+    _refuse_agreement(context, 'auxiliary_feat')
     _refuse_logit_samples(context, 'auxiliary_feat')
     if not _single_rank_only(world):
         return context
@@ -774,6 +847,7 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_segm.yaml'.format(dataset)))
     _refuse_tta(context, 'auxiliary_segm')
     _refuse_temperature(context, 'auxiliary_segm')
+    _refuse_agreement(context, 'auxiliary_segm')
     _refuse_logit_samples(context, 'auxiliary_segm')
     if not _single_rank_only(world):
         return context
@@ -837,6 +911,7 @@ def fit_temperature(dataset, config_file, device='cuda'):
         raise ValueError('others.tta: the temperature fit does not run under test-time augmentation')
     _refuse_temperature(context, 'fit_temperature')
     _refuse_logit_samples(context, 'fit_temperature')
+    _refuse_agreement(context, 'fit_temperature')
     mc = int(getattr(others, 'mc', 0) or 0)
     seed = 0 if context.config.seed is None else int(context.config.seed)
     context.load_from_checkpoint(context.get_test_at())
@@ -871,7 +946,7 @@ for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, te
 
 
 def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, actions=('minmax', 'ece_dice', 'calib', 'bnf_ue'),
-                     expected_subjects=None, fused=True, batch_subjects=8, timing=None, levels=1000, connectivity=26, bands=10):
+                     expected_subjects=None, fused=True, batch_subjects=8, timing=None, levels=1000, connectivity=26, bands=10, dice_fail=0.8):
     """``run_dirs``: run id (baseline, baseline_mc, ..., aleatoric) -> prediction directory.  BraTS evaluates
     inside the T2 brain mask (``ece_details='foreground'``), ISIC on all pixels (eval_uncertainty.py:19-26).
     ``ground_truth_dir``: the BraTS tree of ``<subject>/<subject>_{t2,seg,...}.nii.gz`` or, for ISIC, the dataset
@@ -885,7 +960,7 @@ def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, action
         gts = evalrun.collect_isic_ground_truth(ground_truth_dir)
         details = ''
     entries = [evalrun.get_eval_data(run_id, path, gts, expected_subjects) for run_id, path in run_dirs.items()]
-    # (levels: of the extension actions 'ue_curves' and 'components', connectivity: of 'components'; bands: of 'boundary'; fused / batch_subjects / timing: rcu_amd.evalrun.evaluate_runs -- one upload per subject shared by all actions, subjects batched per launch)
+    # (levels: of the extension actions 'ue_curves' and 'components', connectivity: of 'components'; bands: of 'boundary'; dice_fail: of 'agreement'; fused / batch_subjects / timing: rcu_amd.evalrun.evaluate_runs -- one upload per subject shared by all actions, subjects batched per launch)
     evalrun.evaluate_runs(entries, list(actions), base_dir, details, fused=fused, batch_subjects=batch_subjects, timing=timing, levels=levels,
-                          connectivity=connectivity, bands=bands)
+                          connectivity=connectivity, bands=bands, dice_fail=dice_fail)
     return entries

@@ -560,6 +560,103 @@ class AleatoricHipEngine(HipEngine):
         return {'ws_probabilities': ws[0], 'ws_sigma': ws[1]}
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# sample agreement (EXTENSION; include/rcu.h "Sample agreement"): the T samples as whole segmentations
+# ------------------------------------------------------------------------------------------------------------------------------
+def check_agreement_passes(passes):
+    """T of a vote plane: an int in 2..RCU_VOTES_MAX_PASSES (agreement is between samples); ValueError otherwise."""
+    try:
+        value = None if isinstance(passes, bool) else operator.index(passes)
+    except TypeError:
+        value = None
+    if value is None or not 2 <= value <= _lib.RCU_VOTES_MAX_PASSES:
+        raise ValueError('agreement needs mc_steps in 2..{} (one vote bit per pass), got {!r}'.format(_lib.RCU_VOTES_MAX_PASSES, passes))
+    return value
+
+
+def vote_bit(job):
+    """Bit of MC pass ``job`` (1..T, the job numbers of ``launch_plan``) in a vote plane: bit (job - 1) % 32 of word (job - 1) // 32.  The
+    weight-scaling pass (job 0) casts no vote."""
+    if not 1 <= int(job) <= _lib.RCU_VOTES_MAX_PASSES:
+        raise ValueError('only passes 1..{} vote, got job {}'.format(_lib.RCU_VOTES_MAX_PASSES, job))
+    return int(job) - 1
+
+
+class SampleVotes:
+    """The vote plane of a batch (include/rcu.h): int32 ``[n_words, N, H, W]``, bit (j - 1) % 32 of word (j - 1) // 32 set where pass j's
+    arg-max is not background.  4 bytes per voxel for T <= 32 passes; zeroed on the stream it is created on."""
+
+    def __init__(self, n, height, width, passes, device):
+        self.passes = int(passes)
+        if not 1 <= self.passes <= _lib.RCU_VOTES_MAX_PASSES:
+            raise ValueError('a vote plane holds 1..{} passes, got {}'.format(_lib.RCU_VOTES_MAX_PASSES, passes))
+        self.n, self.height, self.width = int(n), int(height), int(width)
+        self.plane = torch.zeros(((self.passes + 31) // 32, self.n, self.height, self.width), device=device, dtype=torch.int32)
+
+    @property
+    def n_words(self):
+        return self.plane.shape[0]
+
+    def cast(self, volume, job, is_probabilities=True):
+        """Pass ``job``'s vote over one ``[N, C, H, W]`` probability (or logits) volume (rcu_mc_votes)."""
+        t = volume.to(torch.float32).contiguous()
+        if t.dim() != 4 or (t.shape[0], t.shape[2], t.shape[3]) != (self.n, self.height, self.width) or t.device != self.plane.device:
+            raise ValueError('expected a [{}, C, {}, {}] volume on the plane\'s device'.format(self.n, self.height, self.width))
+        bit = vote_bit(job)
+        if bit >= 32 * self.n_words:
+            raise ValueError('pass {} does not fit a plane of {} passes'.format(job, self.passes))
+        _lib.check(_lib.load().rcu_mc_votes(_lib.ptr(t), self.n, self.height * self.width, t.shape[1],
+                                            _lib.RCU_MC_INPUT_PROBS if is_probabilities else 0, _lib.ptr(self.plane), self.n_words, bit,
+                                            _lib.current_stream()))
+
+    def merge(self, side):
+        """OR another plane of the same batch in (a side lane's: its passes own other bits)."""
+        self.plane.bitwise_or_(side.plane)
+
+
+def sample_votes(multi_probabilities):
+    """A stacked ``[T, N, C, H, W]`` probability tensor (what ``materialize=True`` / ``McStatistics.as_tensor()`` give) -> its ``SampleVotes``:
+    volume t votes as pass t + 1."""
+    if not torch.is_tensor(multi_probabilities) or multi_probabilities.dim() != 5:
+        raise ValueError('sample_votes takes a [T, N, C, H, W] tensor of probabilities')
+    t, n, _, h, w = multi_probabilities.shape
+    votes = SampleVotes(n, h, w, t, multi_probabilities.device)
+    for i in range(t):
+        votes.cast(multi_probabilities[i], i + 1)
+    return votes
+
+
+class VotingHipEngine(HipEngine):
+    """HipEngine whose statistics each carry a vote plane of their own (``stats.votes``): a lane's launches are stream-ordered, so the head
+    kernel reads and writes the voxel's word without atomics; ``merge`` ORs the side lanes' planes into lane 0's.  The engine ``takes_jobs``:
+    pass j of a launch votes bit ``vote_bit(j)``."""
+
+    takes_jobs = True
+
+    def __init__(self, model, passes, do_mi=False, do_var=False, exact=True):
+        super().__init__(model, do_mi, do_var, exact)
+        self.passes = check_agreement_passes(passes)
+
+    def side_statistics(self, x):
+        stats = super().side_statistics(x)
+        stats.votes = SampleVotes(x.shape[0], x.shape[2], x.shape[3], self.passes, x.device)
+        return stats
+
+    def mc_pass(self, x, stats, masks=None, passes=1, lane=0, jobs=None):
+        if jobs is None or len(jobs) != passes:
+            raise ValueError('a voting pass needs the pass numbers of its launch (jobs)')
+        set_dropout_mode(self.model, True)
+        try:
+            self.model.forward_accumulate(x, stats, masks, passes=passes, lane=lane, votes=stats.votes, bits=[vote_bit(j) for j in jobs])
+        finally:
+            set_dropout_mode(self.model, False)
+
+    def merge(self, stats, side):
+        merge_statistics(stats, side)
+        stats.votes.merge(side.votes)
+        side.votes.plane.record_stream(torch.cuda.current_stream(side.votes.plane.device))
+
+
 def check_logit_samples(samples):
     """``logit_samples`` of the aleatoric steps: an int in 0..RCU_LOGIT_MAX_SAMPLES (0: softmax(mu), no sampling); ValueError otherwise."""
     try:
@@ -636,6 +733,20 @@ class SegmentationPredictStep(BatchStep):
             batch_context.output['probabilities'] = softmax(logits)
 
 
+class SampleAgreementStep(BatchStep):
+    """Behind the summary: pops ``sample_votes`` (McPredictStep with ``agreement=True``) and writes ``output['agreement']``, one int64 row
+    ``[(T + 1) + T (T + 1) / 2]`` per slice -- ``hist`` then the upper triangle ``pairs`` of include/rcu.h's rcu_agreement_tables, one image per
+    volume.  Integers: the rows of a subject's slices add up to the subject's table (``evaluation.agreement_metrics`` on the sum)."""
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        from . import evaluation
+        votes = batch_context.output.pop('sample_votes', None)
+        if votes is None:
+            return
+        hist, pairs = evaluation.agreement_tables_on_device(votes.plane, votes.passes, votes.n)
+        batch_context.output['agreement'] = torch.cat([hist, pairs], dim=1)
+
+
 class McPredictStep(BatchStep):
     """T stochastic passes (plus the deterministic 'weight scaling' pass the reference always runs
     first, customsteps.py:22-25).
@@ -658,8 +769,14 @@ class McPredictStep(BatchStep):
     LANES = 2      # HIP streams the pass groups of a batch alternate over (StreamLanes); the ``lanes`` argument overrides it
 
     def __init__(self, mc_steps, do_mi=False, do_var=False, materialize=False, masks=None, ws_pass=True,
-                 group_pixels=None, lanes=None, seed=None, exact=True) -> None:
+                 group_pixels=None, lanes=None, seed=None, exact=True, agreement=False) -> None:
         super().__init__()
+        # EXTENSION ``agreement`` (include/rcu.h "Sample agreement"): ``output['sample_votes']`` (SampleVotes) -- one bit per (voxel, pass), set
+        # where the pass's arg-max is not background; written by the head kernel of the fused path (every lane votes into a plane of its own,
+        # OR-merged at the end), by ``sample_votes`` on the materialised one.  The weight-scaling pass casts no vote.
+        self.agreement = bool(agreement)
+        if self.agreement:
+            check_agreement_passes(mc_steps)
         self.mc_steps = mc_steps
         self.do_mi, self.do_var = do_mi, do_var
         self.materialize = materialize
@@ -692,7 +809,10 @@ class McPredictStep(BatchStep):
             ws = torch.empty((n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
             if ws is not None:
                 batch_context.output['ws_probabilities'] = ws
-            batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, ws)
+            stats = self._fused(model, images, self.do_mi, self.do_var, k, ws, votes=self.agreement)
+            batch_context.output['multi_probabilities'] = stats
+            if self.agreement:
+                batch_context.output['sample_votes'] = stats.votes
             return
         unet = isinstance(model, model_mod.UNet)
         if unet:      # the canonical plan of the fused path (reserve_canonical_plans): a pass's bits are a property of the plan
@@ -707,10 +827,12 @@ class McPredictStep(BatchStep):
                 masks = self._pass_masks(model, images, k, j) if unet else None
                 probs.append(softmax(model(images) if masks is None else model(images, masks)))
             batch_context.output['multi_probabilities'] = torch.stack(probs)
+            if self.agreement:
+                batch_context.output['sample_votes'] = sample_votes(batch_context.output['multi_probabilities'])
         finally:
             set_dropout_mode(model, is_train=False)   # reset to eval for the next batch (customsteps.py:39)
 
-    def _fused(self, model, images, do_mi, do_var, first_sample=0, ws=None):
+    def _fused(self, model, images, do_mi, do_var, first_sample=0, ws=None, votes=False):
         """The T passes (and, into ``ws``, the weight-scaling pass) into per-voxel statistics, on ``run_plan``.  The statistics carry a recipe
         that replays the passes -- same images, same masks (seeded: the same draws again; unseeded: the device generator is put back to where
         the sampling started) -- so that ``MultiPredictionSummary(do_mi / do_var)`` decides alone which outputs exist, as in the reference
@@ -719,7 +841,8 @@ class McPredictStep(BatchStep):
         dev = images.device
         unseeded = self.masks is None and self.seed is None
         rng_state = torch.cuda.get_rng_state(dev) if (unseeded and dev.type == 'cuda') else None
-        engine = HipEngine(model, do_mi, do_var, self.exact)
+        # (``votes``: the statistics carry the vote plane of the passes, ``stats.votes``; a replay through the recipe does not vote again)
+        engine = VotingHipEngine(model, self.mc_steps, do_mi, do_var, self.exact) if votes else HipEngine(model, do_mi, do_var, self.exact)
         stats = engine.side_statistics(images)
         group = pass_group_size(model, n, h, w, self.group_pixels)
         # (every lane gets work whenever there are two passes: T = 20 on batches of 32 slices is 10 | 10 on two lanes, not one launch of 20 on one)
