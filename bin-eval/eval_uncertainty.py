@@ -30,6 +30,12 @@ if __name__ == '__main__':
     parser.add_argument('--bands', type=int, default=10, help='rcu_amd: distance bands of the boundary action (1..64)')
     parser.add_argument('--dice_fail', type=float, default=0.8, help='rcu_amd: the agreement action counts a subject with Dice below this as a failed '
                         'segmentation')
+    parser.add_argument('--calib_bins', type=int, default=10, help='rcu_amd: equal-width bins of the ECE / MCE of the calib_curves action (--act calib_curves: '
+                        'Brier, NLL, Brier decomposition, equal-width / equal-mass / maximum / Kolmogorov-Smirnov calibration errors and a reliability '
+                        'curve from a histogram of --levels levels); must divide --levels')
+    parser.add_argument('--mass_bins', type=int, default=10, help='rcu_amd: equal-mass bins of the calib_curves action')
+    parser.add_argument('--recalibrate_from', type=str, default=None, help='rcu_amd: an eval_calib_levels_<id>.csv of another run (the validation run, '
+                        'evaluated with the same --levels): the calib_curves action also reports Brier, NLL and ECE under that run\'s isotonic map')
     parser.add_argument('--plain', action='store_true', help='rcu_amd: the reference\'s subject-by-subject, action-by-action loop for every run')
     args = parser.parse_args()
     from rcu_amd import directories as dirs
@@ -51,4 +57,5 @@ if __name__ == '__main__':
     runs = {i: (os.path.join(args.pred_dir, ds, i) if args.pred_dir else dirs.prediction_dir(ds, i)) for i in ids}
     out_dir = os.path.join(args.out_dir, ds) if args.out_dir else dirs.eval_dir(ds)
     scripts.eval_uncertainty(ds, runs, gt_dir, out_dir, acts, fused=not args.plain, batch_subjects=args.batch_subjects,
-                             levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail)
+                             levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail,
+                             calib_bins=args.calib_bins, mass_bins=args.mass_bins, recalibrate_from=args.recalibrate_from)

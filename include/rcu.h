@@ -372,6 +372,44 @@ int rcu_unc_hist_from_p(const float* p_foreground_dev, const uint8_t* prediction
  * histogram takes, at most 64; 0 = the launcher's choice (default).  Integer sums: every value gives the same histogram.  Process-wide. */
 int rcu_unc_hist_set_blocks_per_workgroup(int blocks);
 
+/* EXTENSION (the reference's calibration measure is one ECE over at most RCU_MAX_BINS equal-width bins; rcu_amd.evaluation.calibration_levels,
+ * calibration_curve_metrics, isotonic_levels): the calibration level histogram of n_volumes volumes of n_per_volume voxels each (volume v at
+ * offset v * n_per_volume in every array, which need not be a multiple of 4; the bases need not be 16-byte aligned), from which the proper
+ * scoring rules (Brier, NLL), Murphy's decomposition, equal-width / equal-mass / maximum / Kolmogorov-Smirnov calibration errors, a reliability
+ * curve and an isotonic recalibration map are host arithmetic on integers.  Integer sums: the outputs do not depend on the launch geometry,
+ * and those of disjoint voxel sets add.
+ *   levels B        2 <= B <= RCU_CALIB_CURVE_MAX_LEVELS
+ *   thresholds      t_k, k = 1 .. B-1: exactly what rcu_ece_thresholds would give for n_bins = B -- the smallest float32 >= k * ((1 + 1e-8) / B),
+ *                   the edges of np.linspace(0, 1 + 1e-8, B + 1) the reference's _binary_calibration digitises against.  For every divisor
+ *                   n of B the thresholds t_{k B / n} of B levels are bit-equal to the thresholds t_k of n bins (checked for every B in
+ *                   2..4096): merging B / n consecutive levels gives the reference's n-bin histogram for every float32 p.
+ *   level(p)        #{k : p >= t_k}: p = 1 (and anything above) -> B-1; NaN and negative p -> 0; p = 0.5 -> level 499 of 1000, bin 4 of 10
+ *   levels_dev      [n_volumes][3][B] uint64, written (not added to): plane 0 the voxels with target == 0 per level, plane 1 those with
+ *                   target != 0, plane 2 the sum of Q(p) over all voxels of the level,
+ *                   Q(p) = rint(c(p) * 2^32), c(p) = clamp((double)p, 0, 1), ties to even, NaN -> 0.  (double)p * 2^32 is an integer for
+ *                   float32 p >= 2^-9: the confidence sums are exact there; below, each voxel is off by at most 2^-33.
+ *   totals_dev      [n_volumes][2][4] uint64, written: per target class y (0: target == 0) n_y, sum Q(p), sum Q2(p), sum N(p, y) with
+ *                   Q2(p) = rint(c(p) * c(p) * 2^32) (the product is exact in float64; for p in [0, 1] c(p) is p itself) and the NLL term
+ *                   N = rint(l * 2^20), l = -logf(fmaxf(p_y, 2^-23)) clamped to [0, 23 ln 2], p_y = y ? p : 1.0f - p in float32 --
+ *                   the convention of rcu_temperature_nll (NaN p: p_y counts as 2^-23)
+ *   mask            voxels with mask == 0 are skipped; mask_dev NULL = all voxels
+ * Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it): levels outside
+ * 2..RCU_CALIB_CURVE_MAX_LEVELS, a null pointer (mask_dev may be NULL), n_per_volume == 0, n_volumes outside 1..65535.
+ * workspace_dev: rcu_calib_curve_workspace_bytes(...) bytes (the threshold table; 0 for levels out of range).
+ * rcu_calib_curve_thresholds writes the levels - 1 thresholds to host memory and touches no device.
+ * rcu_calib_curve_terms (test aid, as rcu_ece_bin_ids and rcu_temperature_nll_terms) writes every voxel's level and its float32 l (clamped,
+ * before the rounding to N) with the scan's arithmetic bit for bit; it takes no mask. */
+#define RCU_CALIB_CURVE_MAX_LEVELS 4096
+int rcu_calib_curve_thresholds(int levels, float* thr_host);
+size_t rcu_calib_curve_workspace_bytes(size_t n_per_volume, int n_volumes, int levels);
+int rcu_calib_curve(const float* p_foreground_dev, const uint8_t* target_dev, const uint8_t* mask_dev, size_t n_per_volume, int n_volumes,
+                    int levels, uint64_t* levels_dev, uint64_t* totals_dev, void* workspace_dev, void* stream);
+int rcu_calib_curve_terms(const float* p_foreground_dev, const uint8_t* target_dev, size_t n, int levels, int32_t* level_dev, float* nll_dev,
+                          void* stream);
+/* Test / tuning aid (as rcu_unc_hist_set_blocks_per_workgroup): consecutive blocks (16,384 voxels; 65,536 for levels > 1365) a workgroup of the
+ * calibration level histogram takes, at most 64; 0 = the launcher's choice (default).  Integer sums: every value gives the same result.  Process-wide. */
+int rcu_calib_curve_set_blocks_per_workgroup(int blocks);
+
 /* ------------------------------------------------------------------------------------------
  * Test-time augmentation (EXTENSION: the reference has no TTA; rcu_amd.steps.TtaMcPredictStep)
  *   The network runs on transformed copies g(x) of every slice, the statistics of those passes are mapped back with g^-1 and added to

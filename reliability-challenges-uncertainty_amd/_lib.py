@@ -20,6 +20,7 @@ RCU_MC_EXACT_MAX_PASSES = 2048
 RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
 RCU_UNC_HIST_MAX_LEVELS = 4096
+RCU_CALIB_CURVE_MAX_LEVELS = 4096
 # connected components (include/rcu.h): the uncertainty source of rcu_cc_table
 RCU_CC_UNC_NONE, RCU_CC_UNC_F32, RCU_CC_UNC_F64, RCU_CC_UNC_P = 0, 1, 2, 3
 # distance transform (include/rcu.h): the squared distance of a volume without a feature voxel; the most bands of rcu_boundary_table
@@ -129,6 +130,11 @@ SIGNATURES = {
     'rcu_unc_hist': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_unc_hist_from_p': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_unc_hist_set_blocks_per_workgroup': (c_int, [c_int]),
+    'rcu_calib_curve_thresholds': (c_int, [c_int, POINTER(c_float)]),
+    'rcu_calib_curve_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int]),
+    'rcu_calib_curve': (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_calib_curve_terms': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_calib_curve_set_blocks_per_workgroup': (c_int, [c_int]),
     'rcu_cc_label': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_cc_workspace_bytes': (c_size_t, [c_size_t, c_int]),
     'rcu_cc_compact': (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
@@ -218,4 +224,11 @@ def current_stream():
 def ece_thresholds(n_bins=10):
     arr = (c_float * max(n_bins - 1, 1))()
     check(load().rcu_ece_thresholds(n_bins, arr))
+    return arr
+
+
+def calib_curve_thresholds(levels):
+    """The ``levels - 1`` float32 thresholds of the calibration level histogram (include/rcu.h, rcu_calib_curve_thresholds) as a ctypes array."""
+    arr = (c_float * max(int(levels) - 1, 1))()
+    check(load().rcu_calib_curve_thresholds(int(levels), arr))
     return arr

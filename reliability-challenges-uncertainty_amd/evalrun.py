@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components and boundary are extensions
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components, boundary, agreement and calib_curves are extensions
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -35,6 +35,11 @@ MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
 UE_CURVES_PLACEHOLDER = 'eval_ue_curves_{}.csv'
 UE_CURVES_POOLED_PLACEHOLDER = 'eval_ue_curves_pooled_{}.csv'
 UE_LEVELS_PLACEHOLDER = 'eval_ue_levels_{}.csv'
+# rcu_amd extension (the 'calib_curves' action), next to the reliability bins in CALIB_NAME
+CALIB_CURVES_PLACEHOLDER = 'eval_calib_curves_{}.csv'
+CALIB_CURVES_POOLED_PLACEHOLDER = 'eval_calib_curves_pooled_{}.csv'
+CALIB_LEVELS_PLACEHOLDER = 'eval_calib_levels_{}.csv'
+CALIB_LEVELS_COLUMNS = ('level', 'threshold', 'n_neg', 'n_pos', 'mean_confidence', 'positive_fraction', 'isotonic')
 # rcu_amd extension (the 'components' action), in UNCERTAINTY_NAME as well
 COMPONENTS_PLACEHOLDER = 'eval_components_{}.csv'
 COMPONENTS_POOLED_PLACEHOLDER = 'eval_components_pooled_{}.csv'
@@ -649,6 +654,94 @@ class BoundaryAction(UncertaintyAction):
                                     [float(bands[k][side, band]) for k in ev.BOUNDARY_BAND_KEYS])
 
 
+def read_recalibration_map(path, levels):
+    """The ``isotonic`` column of an ``eval_calib_levels_<id>.csv`` (another run's pooled level histogram, typically the validation run's) as a
+    float64 [levels] map; a file of another number of levels is refused."""
+    with open(path, newline='') as f:
+        rows = list(csv.DictReader(f))
+    if len(rows) != levels or [int(r['level']) for r in rows] != list(range(levels)):
+        raise ValueError('{} holds {} levels, this evaluation uses {}: evaluate both runs with the same --levels'.format(path, len(rows), levels))
+    return np.array([float(r['isotonic']) for r in rows], dtype=np.float64)
+
+
+class CalibCurvesAction(EvalAction):
+    """EXTENSION (the reference's calibration measure is a 10-bin ECE): proper scoring rules, the Brier decomposition, equal-width /
+    equal-mass / maximum / Kolmogorov-Smirnov calibration errors and a reliability curve from one calibration level histogram per subject
+    (evaluation.calibration_levels / calibration_curve_metrics), prepared exactly like ``EceCalibrationAction`` -- every confidence entry,
+    inside the brain mask with ``details == 'foreground'``.  Files in ``<base_dir>/calibration``:
+      eval_calib_curves_<id>.csv          one row per subject: the keys of evaluation.CALIB_CURVE_KEYS
+      eval_calib_curves_pooled_<id>.csv   the same metrics of the SUM of the subjects' integers (whatever the batching or the order)
+      eval_calib_levels_<id>.csv          that pooled histogram, one row per level: level, threshold (the lower edge t_level, 0 for level 0),
+                                          n_neg, n_pos, mean_confidence, positive_fraction (empty for an empty level), isotonic
+                                          (evaluation.isotonic_levels: the monotone recalibration map fitted on this run)
+    ``recalibrate_from``: such a levels file of ANOTHER run evaluated with the same ``levels``; its isotonic map adds the columns
+    ``brier_recal``, ``nll_recal``, ``ece_recal`` to the two metrics files."""
+
+    def __init__(self, levels, base_dir, details='', calib_bins=10, mass_bins=10, recalibrate_from=None, rescale_confidence='subject',
+                 rescale_sigma='subject', min_max_dir=None):
+        super().__init__()
+        self.levels, self.calib_bins, self.mass_bins = int(levels), int(calib_bins), int(mass_bins)
+        if not 2 <= self.levels <= ev._lib.RCU_CALIB_CURVE_MAX_LEVELS:
+            raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_CALIB_CURVE_MAX_LEVELS, levels))
+        if self.calib_bins < 1 or self.levels % self.calib_bins:
+            raise ValueError('calib_bins = {} does not divide levels = {}'.format(calib_bins, levels))
+        if self.mass_bins < 1:
+            raise ValueError('mass_bins must be >= 1, got {}'.format(mass_bins))
+        self.recalibration = None if recalibrate_from is None else read_recalibration_map(recalibrate_from, self.levels)
+        self.keys = ev.CALIB_CURVE_KEYS + (ev.CALIB_RECAL_KEYS if self.recalibration is not None else ())
+        self.need_mask = details == 'foreground'
+        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
+        self.out_dir = os.path.join(base_dir, CALIB_NAME)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.pooled_levels = self.pooled_totals = None
+
+    def setup_eval(self, eval_data):
+        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
+        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
+        self.prepare, self.id_ = ev.get_probability_preparation(eval_data.confidence_entry, eval_data.id_,
+                                                                self.rescale_confidence, self.rescale_sigma, mm)
+        self.load_params = Loader.Params(eval_data.confidence_entry, need_t2_mask=self.need_mask)
+        self.eval_cases = [EvalCase(None, WriteCsvHook(os.path.join(self.out_dir, CALIB_CURVES_PLACEHOLDER.format(self.id_)), entries=self.keys))]
+        # Python integers: the pooled sum of Q(p) of a few hundred BraTS subjects can pass 2^63
+        self.pooled_levels = np.zeros((3, self.levels), dtype=object)
+        self.pooled_totals = np.zeros((2, 4), dtype=object)
+
+    def metrics(self, levels, totals):
+        return ev.calibration_curve_metrics(levels, totals, self.calib_bins, self.mass_bins, self.recalibration)
+
+    def record_levels(self, levels, totals, subject_name):
+        """One subject's level histogram ``[3, levels]`` and class totals ``[2, 4]``: its metrics row, and its share of the pooled integers."""
+        self.eval_cases[0].record(self.metrics(levels, totals), subject_name, self.id_)
+        self.pooled_levels += np.asarray(levels).astype(object)
+        self.pooled_totals += np.asarray(totals).astype(object)
+
+    def eval_subject(self, sf, loader):
+        to_eval = loader.get_data(sf, self.load_params)
+        if self.prepare:
+            to_eval = self.prepare(to_eval)
+        levels, totals = ev.calibration_levels(to_eval['probabilities'], to_eval['target'], self.levels,
+                                               mask=to_eval['mask'] if self.need_mask else None)
+        self.record_levels(levels[0], totals[0], sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        row = self.metrics(self.pooled_levels, self.pooled_totals)
+        with open(os.path.join(self.out_dir, CALIB_CURVES_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['test_id'] + list(self.keys))
+            writer.writerow([self.id_] + [row[k] for k in self.keys])
+        thresholds = [0.0] + [float(t) for t in ev.calibration_thresholds(self.levels)]
+        isotonic = ev.isotonic_levels(self.pooled_levels)
+        with open(os.path.join(self.out_dir, CALIB_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(CALIB_LEVELS_COLUMNS)
+            for level in range(self.levels):
+                n_neg, n_pos, conf = (int(v) for v in self.pooled_levels[:, level])
+                n = n_neg + n_pos
+                writer.writerow([level, thresholds[level], n_neg, n_pos, conf / (n << 32) if n else '', n_pos / n if n else '',
+                                 float(isotonic[level])])
+
+
 def read_agreement_csv(path):
     """``agreement.csv`` of a test run (scripts.AgreementCsvHook) -> {subject: {column: float}}."""
     if not os.path.isfile(path):
@@ -722,10 +815,13 @@ class AgreementAction(EvalAction):
 ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
-def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8):
+def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8, calib_bins=10,
+                mass_bins=10, recalibrate_from=None):
     """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
-    (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice) and 'boundary' (``bands``: its distance bands, 1..64;
-    ``levels``: of its off-border level histogram)."""
+    (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice), 'boundary' (``bands``: its distance bands, 1..64;
+    ``levels``: of its off-border level histogram) and 'calib_curves' (``levels``: of its calibration level histogram; ``calib_bins``: the
+    equal-width bins of its ECE, a divisor of ``levels``; ``mass_bins``: of its equal-mass ECE; ``recalibrate_from``: the levels file of
+    another run whose isotonic map is to be judged)."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -744,6 +840,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(BoundaryAction(levels, bands, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'agreement':      # (``dice_fail``: the Dice below which a segmentation counts as failed)
             actions.append(AgreementAction(base_dir, dice_fail))
+        elif name == 'calib_curves':
+            actions.append(CalibCurvesAction(levels, base_dir, ece_details, calib_bins, mass_bins, recalibrate_from, 'subject', 'global', min_max_dir))
     return actions
 
 
@@ -831,11 +929,12 @@ class _LoaderAhead:
 
 def _fusable(entry, actions):
     """The fused loop covers the runs whose confidence entry IS the probability map (baseline, baseline_mc, center, center_mc, ensemble:
-    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script, 'ue_curves', 'components' and 'boundary'."""
-    masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES}
+    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script and the extension actions; the
+    actions that use the brain mask ('ece_dice', 'calib', 'calib_curves') must agree on it: the batch holds one mask."""
+    masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES | {CalibCurvesAction}}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
             all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction,
-                            AgreementAction)
+                            AgreementAction, CalibCurvesAction)
                 for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
@@ -843,13 +942,15 @@ def _fusable(entry, actions):
 def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
     list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
-    by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`)."""
+    by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`, 'calib_levels' by a
+    CalibCurvesAction, which holds `levels` as well)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
            (['ue'] if (CorrectionAction in by_type or AgreementAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
            (['ue_hist'] if UeCurvesAction in by_type else []) + \
            (['components'] if ComponentsAction in by_type else []) + \
-           (['boundary'] if BoundaryAction in by_type else [])
+           (['boundary'] if BoundaryAction in by_type else []) + \
+           (['calib_levels'] if CalibCurvesAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -894,6 +995,8 @@ def record_subject(actions, subject, res, slot, n_dim):
         elif isinstance(action, AgreementAction):      # (the counts are there whenever the action is: metrics_wanted)
             tp, _, fp, fn = (int(v) for v in counts[0][:4])
             action.record_dice(ev._dice(tp, fp, fn), subject)
+        elif isinstance(action, CalibCurvesAction):
+            action.record_levels(res['calib_levels'][slot], res['calib_totals'][slot], subject)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -903,7 +1006,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     fn are ece_dice's confusion matrix), min / max -- and the results fanned out to the actions' CSV hooks in subject order.  The rows are
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
     want, thresholds, want_mask = metrics_wanted(actions)
-    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction))), ev.UE_LEVELS)
+    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction, CalibCurvesAction))), ev.UE_LEVELS)
     bands = next((a.bands for a in actions if isinstance(a, BoundaryAction)), 10)
     connectivity = next((a.connectivity for a in actions if isinstance(a, ComponentsAction)), 26)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
@@ -962,14 +1065,16 @@ class _Done:
 
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
-                  connectivity=26, bands=10, dice_fail=0.8):
+                  connectivity=26, bands=10, dice_fail=0.8, calib_bins=10, mass_bins=10, recalibrate_from=None):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
-    'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action."""
-    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail)
+    'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action; ``calib_bins``, ``mass_bins``,
+    ``recalibrate_from``: of the 'calib_curves' action (``get_actions``)."""
+    actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail, calib_bins,
+                          mass_bins, recalibrate_from)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

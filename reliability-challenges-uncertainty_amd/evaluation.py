@@ -114,6 +114,19 @@ def _unc_hist_launch(source, is64, prediction, target, mask, levels):
     return out
 
 
+def _calib_curve_launch(p, target, mask, levels):
+    """-> device int64 (levels [v, 3, levels], totals [v, 2, 4]) holding the uint64 integers of rcu_calib_curve."""
+    v, n = target.shape
+    levels = int(levels)
+    lib = _lib.load()
+    out = torch.empty((v, 3, max(levels, 1)), device=p.device, dtype=torch.int64)
+    totals = torch.empty((v, 2, 4), device=p.device, dtype=torch.int64)
+    ws = torch.empty(max(lib.rcu_calib_curve_workspace_bytes(n, v, levels), 8), device=p.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_calib_curve(_lib.ptr(p), _lib.ptr(target), _lib.ptr(mask), n, v, levels, _lib.ptr(out), _lib.ptr(totals), _lib.ptr(ws),
+                                   _lib.current_stream()))
+    return out, totals
+
+
 # ------------------------------------------------------------------------------------------- ECE
 def _foreground(probabilities, target_ndim):
     """numpyfunctions.py:27-33."""
@@ -260,7 +273,9 @@ class SubjectBatch:
         labelled under ``connectivity`` in the shapes the subjects were put with -- from the resident maps, all subjects in one call.  With
         ``'boundary'`` in ``want``, ``boundary`` = per subject the triple (``boundary_table`` of ``bands`` bands with the entropy of p as the
         uncertainty, ``surface_distance_histograms``, the level histogram ``ue_hist_off_border`` [4, levels] of the voxels outside the
-        target's border shell ``boarder_mask(target, 1, 1)``), all subjects of one shape in one call per kernel."""
+        target's border shell ``boarder_mask(target, 1, 1)``), all subjects of one shape in one call per kernel.  With ``'calib_levels'`` in
+        ``want``, ``calib_levels`` uint64 [used, 3, levels] and ``calib_totals`` uint64 [used, 2, 4]: the calibration level histogram of
+        ``calibration_levels`` inside the mask, exactly as ``hist`` uses it, in one launch."""
         v = self.used
         out, keep = {}, []
         p, prediction, target = self.p[:v], self.prediction[:v], self.target[:v]
@@ -273,6 +288,9 @@ class SubjectBatch:
             keep.append(('ue', _unc_counts_from_p_launch(p, prediction, target, None, thresholds)))
         if 'ue_hist' in want:
             keep.append(('ue_hist', _unc_hist_launch(p, None, prediction, target, None, levels)))
+        if 'calib_levels' in want:
+            calib = _calib_curve_launch(p, target, None if self.mask is None else self.mask[:v], levels)
+            keep.extend([('calib_levels', calib[0]), ('calib_totals', calib[1])])
         if 'components' in want:
             out['components'] = self._component_tables(v, connectivity)
         if 'boundary' in want:
@@ -287,6 +305,9 @@ class SubjectBatch:
             out['counts'] = host['ue'].numpy()
         if 'ue_hist' in host:
             out['ue_hist'] = host['ue_hist'].numpy().view(np.uint64)
+        for key in ('calib_levels', 'calib_totals'):
+            if key in host:
+                out[key] = host[key].numpy().view(np.uint64)
         return out
 
     def _by_shape(self, v):
@@ -475,6 +496,163 @@ def ue_curve_metrics(hist):
     best = max(range(1, levels), key=lambda k: (dice_at[k], -k))
     out['ue_dice_max'] = dice_at[best]
     out['ue_dice_max_threshold'] = best / levels
+    return out
+
+
+# ------------------------------------------------ calibration metrics from a level histogram (EXTENSION)
+CALIB_CURVE_KEYS = ('n', 'n_pos', 'brier', 'nll', 'bias', 'ece', 'mce', 'ace', 'ks', 'brier_reliability', 'brier_resolution', 'brier_uncertainty')
+CALIB_RECAL_KEYS = ('brier_recal', 'nll_recal', 'ece_recal')
+_Q_ONE = 1 << 32          # the integer of a confidence of 1: Q(p) = rint(clamp(p, 0, 1) * 2^32)
+_NLL_ONE = 1 << 20        # the integer of an NLL term of 1: N = rint(l * 2^20)
+_P_FLOOR = 2.0 ** -23     # the probability floor of the NLL (include/rcu.h, rcu_calib_curve; rcu_temperature_nll's convention)
+
+
+def calibration_thresholds(levels=UE_LEVELS):
+    """float32 [levels - 1]: the thresholds t_k of the calibration level histogram, ``rcu_ece_thresholds``' for any number of levels (host only)."""
+    return np.array(_lib.calib_curve_thresholds(levels)[:int(levels) - 1], dtype=np.float32)
+
+
+def calibration_levels(probabilities, target, levels=UE_LEVELS, mask=None, n_volumes=1):
+    """The calibration level histogram in one GPU pass (include/rcu.h, rcu_calib_curve) -> (``levels`` uint64 [n_volumes, 3, B], ``totals``
+    uint64 [n_volumes, 2, 4]).  level(p) = #{k : p >= t_k} on the thresholds of ``calibration_histogram`` extended to B levels (merging B / n
+    consecutive levels gives its n-bin histogram for every n that divides B); planes: voxels with target == 0, with target != 0, sum of
+    Q(p) = rint(p * 2^32); totals per target class: n, sum Q(p), sum rint(p^2 * 2^32), sum rint(l * 2^20) of the NLL terms.  Takes the
+    foreground map the way ``calibration_histogram`` does.  Integers: the results of disjoint voxel sets (subjects of a run) add."""
+    p = _foreground(probabilities, np.ndim(target) if not isinstance(target, torch.Tensor) else target.dim())
+    out, totals = _calib_curve_launch(_flat(p, torch.float32, n_volumes), _flat(target, torch.uint8, n_volumes), _flat(mask, torch.uint8, n_volumes),
+                                      levels)
+    return out.cpu().numpy().view(np.uint64), totals.cpu().numpy().view(np.uint64)
+
+
+def _level_rows(levels):
+    h = np.asarray(levels)
+    if h.ndim != 2 or h.shape[0] != 3 or h.shape[1] < 2:
+        raise ValueError('expected one calibration level histogram of shape [3, levels >= 2], got {}'.format(h.shape))
+    return ([int(v) for v in row] for row in h)
+
+
+def _pava(blocks):
+    """Pool adjacent violators on [positives, count] blocks in ascending order (exact: fractions compared by cross-multiplication)."""
+    out = []
+    for pos, cnt in blocks:
+        out.append([pos, cnt, 1])
+        while len(out) > 1 and out[-2][0] * out[-1][1] > out[-1][0] * out[-2][1]:
+            pos_, cnt_, k_ = out.pop()
+            out[-1][0] += pos_
+            out[-1][1] += cnt_
+            out[-1][2] += k_
+    return out
+
+
+def isotonic_levels(levels):
+    """float64 [B]: the isotonic (monotone non-decreasing) recalibration map of one level histogram ``[3, B]`` -- pool-adjacent-violators over
+    the non-empty levels with weight = voxels of the level and value = its positive fraction, what
+    ``sklearn.isotonic.IsotonicRegression(y_min=0, y_max=1)`` fits on (level, target) per voxel.  An empty level takes the value of the
+    nearest non-empty level below it, leading empty levels the first value (NaN everywhere for an empty histogram)."""
+    n0, n1, _ = _level_rows(levels)
+    filled = [l for l in range(len(n0)) if n0[l] + n1[l]]
+    out = np.full(len(n0), np.nan)
+    if not filled:
+        return out
+    values = []
+    for pos, cnt, k in _pava([n1[l], n0[l] + n1[l]] for l in filled):
+        values.extend([pos / cnt] * k)
+    cursor, current = 0, values[0]
+    for l in range(len(n0)):
+        if cursor < len(filled) and filled[cursor] == l:
+            current = values[cursor]
+            cursor += 1
+        out[l] = current
+    return out
+
+
+def calibration_curve_metrics(levels, totals, bins=10, mass_bins=10, recalibration=None):
+    """Calibration metrics of ONE level histogram ``levels`` [3, B] with its class totals ``totals`` [2, 4] (a subject's, or the sum of several
+    subjects': the integers add) -> dict with the keys ``CALIB_CURVE_KEYS``.  Host arithmetic on Python integers and float64.  With n0_l, n1_l
+    the voxels of level l per class, n_l their sum, S_l the level's sum of Q, and n_y, S1_y, S2_y, N_y the totals of class y:
+      brier    (S2_0 + n_1 2^32 - 2 S1_1 + S2_1) / (n 2^32): mean of (p - y)^2;   nll  (N_0 + N_1) / (n 2^20);   bias  S1 / (n 2^32) - n_1 / n
+      ece      the equal-width ECE of ``ece_from_histogram`` on the levels merged into ``bins`` bins (``bins`` must divide B);  mce  the largest
+               |mean confidence - positive fraction| of a non-empty merged bin
+      ace      equal-mass ECE at level resolution: level l goes to mass bin min(M - 1, floor(M C_l / n)), M = ``mass_bins``, C_l the voxels of the
+               lower levels;  sum_b |S_b - n1_b 2^32| / (n 2^32)
+      ks       max_l |sum_{l' <= l} (S_l' - n1_l' 2^32)| / (n 2^32): the Kolmogorov-Smirnov calibration error, evaluated at the level boundaries
+      brier_reliability, brier_resolution, brier_uncertainty   Murphy's decomposition over the levels with forecast f_l = S_l / (n_l 2^32) and
+               o_l = n1_l / n_l: sum n_l (f_l - o_l)^2 / n, sum n_l (o_l - o)^2 / n, o (1 - o);  reliability - resolution + uncertainty is the
+               Brier score of the level-mean forecast
+    An empty selection (n = 0) gives NaN for everything but the counts.  ``recalibration``: a map g [B] (``isotonic_levels`` of ANOTHER run's
+    pooled histogram, typically the validation run's) adds ``CALIB_RECAL_KEYS``, computed from the counts alone with every voxel of level l at
+    g_l: brier_recal; nll_recal with g clipped to [2^-23, 1 - 2^-23]; ece_recal over the distinct values of g."""
+    n0, n1, sq = _level_rows(levels)
+    t = np.asarray(totals)
+    if t.shape != (2, 4):
+        raise ValueError('expected class totals of shape [2, 4], got {}'.format(t.shape))
+    t = [[int(v) for v in row] for row in t]
+    B = len(n0)
+    bins, mass_bins = int(bins), int(mass_bins)
+    if bins < 1 or B % bins:
+        raise ValueError('bins = {} does not divide the {} levels'.format(bins, B))
+    if mass_bins < 1:
+        raise ValueError('mass_bins must be >= 1, got {}'.format(mass_bins))
+    g = None
+    if recalibration is not None:
+        g = np.asarray(recalibration, dtype=np.float64).reshape(-1)
+        if g.size != B:
+            raise ValueError('the recalibration map has {} levels, the histogram {}'.format(g.size, B))
+    n, n_pos = t[0][0] + t[1][0], t[1][0]
+    if n != sum(n0) + sum(n1) or n_pos != sum(n1):
+        raise ValueError('the class totals and the level histogram count different voxels')
+    nan = float('nan')
+    out = {'n': n, 'n_pos': n_pos}
+    if n == 0:
+        out.update({k: nan for k in CALIB_CURVE_KEYS[2:]})
+        if g is not None:
+            out.update({k: nan for k in CALIB_RECAL_KEYS})
+        return out
+    one = n * _Q_ONE
+    out['brier'] = (t[0][2] + n_pos * _Q_ONE - 2 * t[1][1] + t[1][2]) / one
+    out['nll'] = (t[0][3] + t[1][3]) / (n * _NLL_ONE)
+    out['bias'] = (t[0][1] + t[1][1] - n_pos * _Q_ONE) / one
+    # equal width: the reference's histogram of `bins` bins
+    width = B // bins
+    merged = [(sum(n0[b:b + width]) + sum(n1[b:b + width]), sum(sq[b:b + width]), sum(n1[b:b + width])) for b in range(0, B, width)]
+    count = np.array([m[0] for m in merged], dtype=np.int64)
+    out['ece'] = float(ece_from_histogram(count, np.array([m[1] / _Q_ONE for m in merged]), np.array([m[2] for m in merged], dtype=np.int64)))
+    out['mce'] = max(abs(s_ - pos * _Q_ONE) / (cnt * _Q_ONE) for cnt, s_, pos in merged if cnt)
+    # equal mass and Kolmogorov-Smirnov: levels ascending
+    gap = [0] * mass_bins
+    below, running, ks = 0, 0, 0
+    for l in range(B):
+        d = sq[l] - n1[l] * _Q_ONE
+        gap[min(mass_bins - 1, (mass_bins * below) // n)] += d
+        below += n0[l] + n1[l]
+        running += d
+        ks = max(ks, abs(running))
+    out['ace'] = sum(abs(d) for d in gap) / one
+    out['ks'] = ks / one
+    # Murphy's decomposition over the non-empty levels
+    base = n_pos / n
+    rel, res = [], []
+    for l in range(B):
+        n_l = n0[l] + n1[l]
+        if n_l:
+            f_l, o_l = sq[l] / (n_l * _Q_ONE), n1[l] / n_l
+            rel.append(n_l * (f_l - o_l) ** 2)
+            res.append(n_l * (o_l - base) ** 2)
+    out['brier_reliability'] = math.fsum(rel) / n
+    out['brier_resolution'] = math.fsum(res) / n
+    out['brier_uncertainty'] = base * (1.0 - base)
+    if g is not None:
+        used = [l for l in range(B) if n0[l] + n1[l]]
+        if any(not 0.0 <= g[l] <= 1.0 for l in used):       # (NaN fails both compares)
+            raise ValueError('the recalibration map leaves [0, 1] (or is NaN) at a level that holds voxels')
+        gc = np.clip(g, _P_FLOOR, 1.0 - _P_FLOOR)
+        out['brier_recal'] = math.fsum(n0[l] * g[l] ** 2 + n1[l] * (1.0 - g[l]) ** 2 for l in used) / n
+        out['nll_recal'] = -math.fsum(n1[l] * math.log(gc[l]) + n0[l] * math.log1p(-gc[l]) for l in used) / n
+        groups = {}
+        for l in used:
+            cnt, pos = groups.get(g[l], (0, 0))
+            groups[g[l]] = (cnt + n0[l] + n1[l], pos + n1[l])
+        out['ece_recal'] = math.fsum(abs(cnt * value - pos) for value, (cnt, pos) in sorted(groups.items())) / n
     return out
 
 
