@@ -17,7 +17,9 @@ if __name__ == '__main__':
                         'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) components '
                         '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice) and '
                         'boundary (errors and uncertainty by distance to the target\'s boundary, surface distances, metrics off the border shell), agreement '
-                        '(the run\'s agreement.csv -- written under others.agreement: true -- against each subject\'s Dice: correlations, failure detection)')
+                        '(the run\'s agreement.csv -- written under others.agreement: true -- against each subject\'s Dice: correlations, failure detection) and lesions '
+                        '(lesion-wise Dice, lesion F1, panoptic quality and the filtering of predicted lesions by uncertainty, from the joint table of '
+                        'predicted components and target lesions)')
     parser.add_argument('--pred_dir', type=str, default=None, help='root with one sub-directory per dataset and run id '
                         '(default: directories.PREDICT_DIR and the per-run *_PREDICT names)')
     parser.add_argument('--gt_dir', type=str, default=None, help='BraTS training tree / ISIC dataset prefix '
@@ -25,8 +27,13 @@ if __name__ == '__main__':
     parser.add_argument('--out_dir', type=str, default=None, help='default: directories.EVAL_DIR')
     parser.add_argument('--batch_subjects', type=int, default=8, help='rcu_amd: subjects of a probability-map run evaluated per GPU launch')
     parser.add_argument('--levels', type=int, default=1000, help='rcu_amd: uncertainty levels of the ue_curves action and threshold grid of the '
-                        'components action (2..4096)')
-    parser.add_argument('--connectivity', type=int, default=26, choices=(6, 26), help='rcu_amd: neighbourhood of the components action (2-D images: 4 / 8)')
+                        'components and lesions actions (2..4096)')
+    parser.add_argument('--connectivity', type=int, default=26, choices=(6, 26), help='rcu_amd: neighbourhood of the components and lesions actions (2-D images: 4 / 8)')
+    parser.add_argument('--merge_radius', type=int, default=0, help='rcu_amd: the lesions action counts target components closer than this Euclidean '
+                        'dilation (in voxels) as one lesion; 0: the target\'s components')
+    parser.add_argument('--min_lesion_voxels', type=int, default=0, help='rcu_amd: the lesions action treats target lesions with fewer voxels as background')
+    parser.add_argument('--match_iou', type=float, default=0.5, help='rcu_amd: the lesions action matches a predicted component and a lesion whose IoU '
+                        'is above this, in [0.5, 1)')
     parser.add_argument('--bands', type=int, default=10, help='rcu_amd: distance bands of the boundary action (1..64)')
     parser.add_argument('--dice_fail', type=float, default=0.8, help='rcu_amd: the agreement action counts a subject with Dice below this as a failed '
                         'segmentation')
@@ -58,4 +65,5 @@ if __name__ == '__main__':
     out_dir = os.path.join(args.out_dir, ds) if args.out_dir else dirs.eval_dir(ds)
     scripts.eval_uncertainty(ds, runs, gt_dir, out_dir, acts, fused=not args.plain, batch_subjects=args.batch_subjects,
                              levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail,
-                             calib_bins=args.calib_bins, mass_bins=args.mass_bins, recalibrate_from=args.recalibrate_from)
+                             calib_bins=args.calib_bins, mass_bins=args.mass_bins, recalibrate_from=args.recalibrate_from,
+                             merge_radius=args.merge_radius, min_lesion_voxels=args.min_lesion_voxels, match_iou=args.match_iou)

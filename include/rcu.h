@@ -569,6 +569,36 @@ int rcu_cc_table(const int32_t* labels_dev, const uint8_t* other_dev, const void
 int rcu_cc_set_tile(int tile_depth, int tile_height, int tile_width);
 
 /* ------------------------------------------------------------------------------------------
+ * Component pairs (EXTENSION: the joint table of two labellings; rcu_amd.evaluation.component_pairs, lesion_tables, lesion_metrics and the
+ * 'lesions' evaluation action: lesion-wise Dice, lesion F1, panoptic quality, one-to-one matching, filtering of lesions by uncertainty)
+ *   a_dev, b_dev   [n_volumes][n_per_volume] int32 label maps: 0 (and every negative value) is background, positive values are ids.  The
+ *                  outputs of rcu_cc_relabel and of rcu_cc_label are both valid; nothing is assumed about how dense the ids are.
+ *   inside_dev     [n_volumes][n_per_volume] uint8 or null
+ *   table_dev      rcu_cc_pairs_bytes(capacity, n_volumes) bytes (0 for arguments out of range): per volume `capacity` slots of one rcu_cc_pair
+ *                  -- volume v's slots start at slot v * capacity --, then, 256-byte aligned behind the slots of all volumes, two uint32
+ *                  counters per volume: used (slots claimed) and dropped (voxels whose pair found no slot after `capacity` probes)
+ *   A slot is empty iff its a and b are 0 (a real pair has both above 0).  For a pair (a, b), voxels = the voxels of the volume that carry label
+ *   a in A and b in B, inside_voxels = those of them where inside_dev is not 0 (0 without inside_dev).  The call clears table_dev itself,
+ *   stream-ordered.  Open addressing with linear probing (csrc/rcu_cc_pairs.hip): the hashed key is (uint64) a << 32 | b, the slot's first
+ *   eight bytes are claimed with one 64-bit compare-and-swap; per wave one insert per distinct pair; nobody waits for anybody.  The ORDER of
+ *   the slots is the race's; the sorted list of the non-empty slots is a function of the inputs alone whenever dropped == 0 (integer adds: the
+ *   same bits whatever the launch geometry, the batching or the hash).  With dropped != 0 the table is full and lacks pairs -- a voxel is
+ *   either counted in the table or counted as dropped --: run again with a larger capacity (one of at least 2 * n_per_volume always suffices).
+ *   Limits: capacity a power of two in 64..2^26; those of rcu_cc_table: n_per_volume in 1..2^31 - 2, n_volumes in 1..65535, n_per_volume *
+ *   n_volumes < 2^32.  Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rcu_cc_pair {
+    uint32_t a, b, voxels, inside_voxels;
+} rcu_cc_pair;      /* 16 bytes */
+
+size_t rcu_cc_pairs_bytes(size_t capacity, int n_volumes);
+int rcu_cc_pairs(const int32_t* a_dev, const int32_t* b_dev, const uint8_t* inside_dev, size_t n_per_volume, int n_volumes, size_t capacity,
+                 void* table_dev, void* stream);
+/* Test aid (as rcu_cc_set_tile): the hash of a pair is shifted right by `shift` bits (0..63; 0 = the whole hash) before it picks the start slot, so
+ * that small inputs crowd into a few start slots and probe long chains.  Every shift gives the same sorted table.  Process-wide. */
+int rcu_cc_pairs_set_hash_shift(int shift);
+
+/* ------------------------------------------------------------------------------------------
  * Distance transform (EXTENSION: where in the image the errors and the uncertainty sit; rcu_amd.evaluation.distance_transform_sq, boarder_mask,
  * boundary_table, surface_distance_histograms and the 'boundary' evaluation action.  The reference builds its border shell with two host
  * distance transforms: common/utils/labelhelper.py:12-20)

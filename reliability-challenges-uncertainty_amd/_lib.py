@@ -141,6 +141,9 @@ SIGNATURES = {
     'rcu_cc_relabel': (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_cc_table': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'rcu_cc_set_tile': (c_int, [c_int, c_int, c_int]),
+    'rcu_cc_pairs_bytes': (c_size_t, [c_size_t, c_int]),
+    'rcu_cc_pairs': (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_size_t, c_void_p, c_void_p]),
+    'rcu_cc_pairs_set_hash_shift': (c_int, [c_int]),
     'rcu_edt_sq': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_border_mask': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_boundary_table': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p]),

@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components, boundary, agreement and calib_curves are extensions
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components, boundary, agreement, calib_curves and lesions are extensions
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -48,6 +48,11 @@ COMPONENT_LIST_PLACEHOLDER = 'eval_component_list_{}.csv'
 BOUNDARY_PLACEHOLDER = 'eval_boundary_{}.csv'
 BOUNDARY_POOLED_PLACEHOLDER = 'eval_boundary_pooled_{}.csv'
 BOUNDARY_BANDS_PLACEHOLDER = 'eval_boundary_bands_{}.csv'
+# rcu_amd extension (the 'lesions' action), in UNCERTAINTY_NAME as well
+LESIONS_PLACEHOLDER = 'eval_lesions_{}.csv'
+LESIONS_POOLED_PLACEHOLDER = 'eval_lesions_pooled_{}.csv'
+LESION_LIST_PLACEHOLDER = 'eval_lesion_list_{}.csv'
+LESION_CURVE_PLACEHOLDER = 'eval_lesion_curve_{}.csv'
 
 # rcu_amd extension (the 'agreement' action), in UNCERTAINTY_NAME as well; AGREEMENT_FILE is what the test script wrote into the run directory
 AGREEMENT_PLACEHOLDER = 'eval_agreement_{}.csv'
@@ -586,6 +591,67 @@ class ComponentsAction(UncertaintyAction):
             writer.writerows(self.list_rows)
 
 
+class LesionsAction(UncertaintyAction):
+    """EXTENSION (the reference has no such action): lesion-wise metrics -- BraTS 2023's lesion-wise Dice, lesion F1, panoptic quality, a
+    one-to-one matching and the filtering of predicted lesions by their uncertainty -- from the joint table of the predicted components and
+    the target's lesions, made on the GPU (evaluation.lesion_tables / lesion_metrics).  The uncertainty is prepared exactly like
+    ``ComponentsAction``'s, and there is no brain mask.  Files in ``<base_dir>/uncertainty``:
+      eval_lesions_<id>.csv          one row per subject: the keys of evaluation.LESION_METRIC_KEYS
+      eval_lesions_pooled_<id>.csv   the same metrics of all subjects' tables together (whatever the batching or the subject order)
+      eval_lesion_list_<id>.csv      one row per kept lesion: subject and the keys of evaluation.LESION_LIST_KEYS
+      eval_lesion_curve_<id>.csv     the pooled filtering curve, one row per threshold k / levels: level, threshold and the keys of
+                                     evaluation.LESION_CURVE_KEYS with the components of mean uncertainty > threshold removed"""
+
+    LIST_HEADER = ('subject',) + ev.LESION_LIST_KEYS
+
+    def __init__(self, levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, rescale_confidence='', rescale_sigma='global',
+                 min_max_dir=None):
+        self.levels, self.connectivity = self.checked_levels(levels), int(connectivity)
+        if self.connectivity not in (6, 26):
+            raise ValueError('connectivity must be 6 or 26, got {}'.format(connectivity))
+        self.merge_radius = ev._check_merge_radius(merge_radius)
+        self.min_lesion_voxels, self.match_iou = int(min_lesion_voxels), float(match_iou)
+        if self.min_lesion_voxels < 0:
+            raise ValueError('min_lesion_voxels must be >= 0, got {}'.format(min_lesion_voxels))
+        if not 0.5 <= self.match_iou < 1.0:
+            raise ValueError('match_iou must be in [0.5, 1): only above an IoU of 0.5 is the matching one-to-one; got {}'.format(match_iou))
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
+        self.tables, self.list_rows = [], []
+
+    def setup_run(self):
+        self.subject_rows(LESIONS_PLACEHOLDER, ev.LESION_METRIC_KEYS)
+        self.tables, self.list_rows = [], []
+
+    def analysis(self, tables):
+        return ev.lesion_analysis(tables, self.levels, self.match_iou, self.min_lesion_voxels)
+
+    def record_tables(self, tables, subject_name):
+        """One subject's ``lesion_tables`` triple: its metrics row, its lesions' rows, and its share of the pooled tables."""
+        metrics, _, listed = self.analysis(tables)
+        self.eval_cases[0].record(metrics, subject_name, self.id_)
+        self.list_rows.extend([subject_name] + [row[k] for k in ev.LESION_LIST_KEYS] for row in listed[0])
+        self.tables.append((subject_name, tables))
+
+    def eval_subject(self, sf, loader):
+        to_eval = self.prepared(sf, loader)
+        self.record_tables(ev.lesion_tables(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], self.connectivity, self.merge_radius)[0],
+                           sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        pooled, curve, _ = self.analysis([t for _, t in sorted(self.tables, key=lambda entry: entry[0])])
+        self.write_pooled_row(os.path.join(self.out_dir, LESIONS_POOLED_PLACEHOLDER.format(self.id_)), ev.LESION_METRIC_KEYS, pooled)
+        with open(os.path.join(self.out_dir, LESION_LIST_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(self.LIST_HEADER)
+            writer.writerows(self.list_rows)
+        with open(os.path.join(self.out_dir, LESION_CURVE_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['level', 'threshold'] + list(ev.LESION_CURVE_KEYS))
+            for k, row in enumerate(curve):
+                writer.writerow([k, k / self.levels] + [row[key] for key in ev.LESION_CURVE_KEYS])
+
+
 class BoundaryAction(UncertaintyAction):
     """EXTENSION (the reference prepares the border shell -- labelhelper.boarder_mask, analysis.py:54-64 -- but has no such action): where the
     errors and the uncertainty sit relative to the target's boundary, from exact distance transforms on the GPU (evaluation.boundary_table,
@@ -816,12 +882,14 @@ ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
 def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8, calib_bins=10,
-                mass_bins=10, recalibrate_from=None):
+                mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5):
     """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
     (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice), 'boundary' (``bands``: its distance bands, 1..64;
     ``levels``: of its off-border level histogram) and 'calib_curves' (``levels``: of its calibration level histogram; ``calib_bins``: the
     equal-width bins of its ECE, a divisor of ``levels``; ``mass_bins``: of its equal-mass ECE; ``recalibrate_from``: the levels file of
-    another run whose isotonic map is to be judged)."""
+    another run whose isotonic map is to be judged) and 'lesions' (``connectivity``, ``levels`` as 'components'; ``merge_radius``: target
+    lesions closer than this Euclidean dilation are one lesion; ``min_lesion_voxels``: smaller lesions count as background; ``match_iou``:
+    the IoU above which a component and a lesion match, in [0.5, 1))."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -836,6 +904,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'components':
             actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'lesions':
+            actions.append(LesionsAction(levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'boundary':
             actions.append(BoundaryAction(levels, bands, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'agreement':      # (``dice_fail``: the Dice below which a segmentation counts as failed)
@@ -934,7 +1004,7 @@ def _fusable(entry, actions):
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES | {CalibCurvesAction}}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
             all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction,
-                            AgreementAction, CalibCurvesAction)
+                            AgreementAction, CalibCurvesAction, LesionsAction)
                 for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
@@ -943,14 +1013,15 @@ def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
     list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
     by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`, 'calib_levels' by a
-    CalibCurvesAction, which holds `levels` as well)."""
+    CalibCurvesAction, which holds `levels` as well, 'lesions' by a LesionsAction, which holds `connectivity` and `merge_radius`)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
            (['ue'] if (CorrectionAction in by_type or AgreementAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
            (['ue_hist'] if UeCurvesAction in by_type else []) + \
            (['components'] if ComponentsAction in by_type else []) + \
            (['boundary'] if BoundaryAction in by_type else []) + \
-           (['calib_levels'] if CalibCurvesAction in by_type else [])
+           (['calib_levels'] if CalibCurvesAction in by_type else []) + \
+           (['lesions'] if LesionsAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -990,6 +1061,8 @@ def record_subject(actions, subject, res, slot, n_dim):
             action.record_histogram(res['ue_hist'][slot], subject)
         elif isinstance(action, ComponentsAction):
             action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
+        elif isinstance(action, LesionsAction):
+            action.record_tables(res['lesions'][slot], subject)
         elif isinstance(action, BoundaryAction):
             action.record_boundary(*res['boundary'][slot], subject)
         elif isinstance(action, AgreementAction):      # (the counts are there whenever the action is: metrics_wanted)
@@ -1008,7 +1081,8 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     want, thresholds, want_mask = metrics_wanted(actions)
     levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction, CalibCurvesAction))), ev.UE_LEVELS)
     bands = next((a.bands for a in actions if isinstance(a, BoundaryAction)), 10)
-    connectivity = next((a.connectivity for a in actions if isinstance(a, ComponentsAction)), 26)
+    connectivity = next((a.connectivity for a in actions if isinstance(a, (ComponentsAction, LesionsAction))), 26)
+    merge_radius = next((a.merge_radius for a in actions if isinstance(a, LesionsAction)), 0)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
     files = entry.subject_files
     reader = _ReadAhead(files, params, depth=2 * batch_subjects)
@@ -1035,7 +1109,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands)
+            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands, merge_radius=merge_radius)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)
@@ -1065,16 +1139,18 @@ class _Done:
 
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
-                  connectivity=26, bands=10, dice_fail=0.8, calib_bins=10, mass_bins=10, recalibrate_from=None):
+                  connectivity=26, bands=10, dice_fail=0.8, calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0,
+                  match_iou=0.5):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
     rescaling recipes) and ``fused=False`` take the reference's subject-by-subject, action-by-action order.
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
     'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action; ``calib_bins``, ``mass_bins``,
-    ``recalibrate_from``: of the 'calib_curves' action (``get_actions``)."""
+    ``recalibrate_from``: of the 'calib_curves' action; ``merge_radius``, ``min_lesion_voxels``, ``match_iou``: of the 'lesions' action, which
+    shares ``levels`` and ``connectivity`` with 'components' (``get_actions``)."""
     actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail, calib_bins,
-                          mass_bins, recalibrate_from)
+                          mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

@@ -262,7 +262,7 @@ class SubjectBatch:
                     dev[s_].copy_(host[s_], non_blocking=True)
         self._staged = set()
 
-    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26, bands=10):
+    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26, bands=10, merge_radius=0):
         """-> dict of host arrays over the ``used`` subjects: ``min`` / ``max`` (float32), ``hist`` = (count, sum_conf, sum_pos) of the
         reliability histogram inside the mask, ``counts`` [used, len(thresholds), 8] of the uncertainty-error action on the WHOLE volume
         (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice) and, with
@@ -275,7 +275,9 @@ class SubjectBatch:
         uncertainty, ``surface_distance_histograms``, the level histogram ``ue_hist_off_border`` [4, levels] of the voxels outside the
         target's border shell ``boarder_mask(target, 1, 1)``), all subjects of one shape in one call per kernel.  With ``'calib_levels'`` in
         ``want``, ``calib_levels`` uint64 [used, 3, levels] and ``calib_totals`` uint64 [used, 2, 4]: the calibration level histogram of
-        ``calibration_levels`` inside the mask, exactly as ``hist`` uses it, in one launch."""
+        ``calibration_levels`` inside the mask, exactly as ``hist`` uses it, in one launch.  With ``'lesions'`` in ``want``, ``lesions`` = per
+        subject the triple of ``lesion_tables`` (entropy of p as the uncertainty, ``connectivity``, ``merge_radius``), all subjects of one shape
+        through each kernel in one call; with ``'components'`` as well the prediction is labelled once for both."""
         v = self.used
         out, keep = {}, []
         p, prediction, target = self.p[:v], self.prediction[:v], self.target[:v]
@@ -291,8 +293,9 @@ class SubjectBatch:
         if 'calib_levels' in want:
             calib = _calib_curve_launch(p, target, None if self.mask is None else self.mask[:v], levels)
             keep.extend([('calib_levels', calib[0]), ('calib_totals', calib[1])])
-        if 'components' in want:
-            out['components'] = self._component_tables(v, connectivity)
+        if 'components' in want or 'lesions' in want:
+            regions = self._regions(v, connectivity, 'components' in want, _check_merge_radius(merge_radius) if 'lesions' in want else None)
+            out.update({key: value for key, value in zip(('components', 'lesions'), regions) if value is not None})
         if 'boundary' in want:
             out['boundary'] = self._boundary(v, _check_bands(bands), levels)
         host = {k: t.cpu() for k, t in keep}          # (the first .cpu() waits for the stream: the others are ready by then)
@@ -319,14 +322,22 @@ class SubjectBatch:
             index = slice(v) if len(slots) == v else torch.as_tensor(slots, device=self.device)
             yield slots, _volume_dims(shape), self.p[index], self.prediction[index], self.target[index]
 
-    def _component_tables(self, v, connectivity):
-        pairs = [None] * v
+    def _regions(self, v, connectivity, want_components, merge_radius):
+        """-> (the 'components' pairs or None, the 'lesions' triples or None; ``merge_radius`` None: no lesions).  The prediction's labelling
+        and its table serve both."""
+        pairs, triples = ([None] * v if want_components else None), ([None] * v if merge_radius is not None else None)
         for slots, dims, p, pr, tg in self._by_shape(v):
-            of_prediction = _component_tables_on_device(pr, dims, tg, _lib.RCU_CC_UNC_P, p, connectivity)
-            of_target = _component_tables_on_device(tg, dims, pr, _lib.RCU_CC_UNC_NONE, None, connectivity)
-            for k, slot in enumerate(slots):
-                pairs[slot] = (of_prediction[k], of_target[k])
-        return pairs
+            labelling = _labelling_on_device(pr, dims, connectivity)
+            of_prediction = _tables_of_labels(*labelling, tg, _lib.RCU_CC_UNC_P, p)
+            if want_components:
+                of_target = _component_tables_on_device(tg, dims, pr, _lib.RCU_CC_UNC_NONE, None, connectivity)
+                for k, slot in enumerate(slots):
+                    pairs[slot] = (of_prediction[k], of_target[k])
+            if merge_radius is not None:
+                found = _lesion_tables_on_device(pr, tg, dims, _lib.RCU_CC_UNC_P, p, connectivity, merge_radius, labelling, of_prediction)
+                for k, slot in enumerate(slots):
+                    triples[slot] = found[k]
+        return pairs, triples
 
     def _boundary(self, v, bands, levels):
         triples = [None] * v
@@ -701,18 +712,25 @@ def _compact_on_device(labels):
     return counts.cpu().numpy().view(np.uint32).astype(np.int64), ws
 
 
-def _component_tables_on_device(mask, dims, other, unc_kind, unc, connectivity):
-    """Device arrays [V, n] (mask, other: uint8 or None; unc as ``unc_kind`` says) -> list of V host tables of COMPONENT_DTYPE."""
-    v, n = mask.shape
-    labels = _labels_on_device(mask, dims, connectivity)
-    counts, ws = _compact_on_device(labels)
+def _tables_of_labels(labels, counts, ws, other, unc_kind, unc):
+    """Canonical labels [V, n] with their compaction (``_compact_on_device``) -> list of V host tables of COMPONENT_DTYPE."""
+    v, n = labels.shape
     total = int(counts.sum())
-    table = torch.empty(max(total, 1) * COMPONENT_DTYPE.itemsize, device=mask.device, dtype=torch.uint8)
+    table = torch.empty(max(total, 1) * COMPONENT_DTYPE.itemsize, device=labels.device, dtype=torch.uint8)
     _lib.check(_lib.load().rcu_cc_table(_lib.ptr(labels), _lib.ptr(other), _lib.ptr(unc), int(unc_kind), n, v, _lib.ptr(ws), _lib.ptr(table), total,
                                         _lib.current_stream()))
     rows = table.cpu().numpy()[:total * COMPONENT_DTYPE.itemsize].view(COMPONENT_DTYPE)
     ends = np.cumsum(counts)
     return [rows[int(e - c):int(e)].copy() for c, e in zip(counts, ends)]
+
+
+def _component_tables_on_device(mask, dims, other, unc_kind, unc, connectivity, labelling=None):
+    """Device arrays [V, n] (mask, other: uint8 or None; unc as ``unc_kind`` says) -> list of V host tables of COMPONENT_DTYPE.
+    ``labelling``: the mask's (labels, counts, workspace) where somebody made them already."""
+    if labelling is None:
+        labels = _labels_on_device(mask, dims, connectivity)
+        labelling = (labels,) + _compact_on_device(labels)
+    return _tables_of_labels(*labelling, other, unc_kind, unc)
 
 
 def connected_components(mask, connectivity=26, n_volumes=1):
@@ -1038,6 +1056,296 @@ def _boundary_on_device(p, prediction, target, dims, bands, levels):
     tables = table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(v, 2, bands + 1)
     hists = ue_hist.cpu().numpy().view(np.uint64)
     return [(tables[k].copy(), surfaces[k], hists[k].copy()) for k in range(v)]
+
+
+# ------------------------------------------------ lesion-wise matching from the joint table of two labellings on the GPU (EXTENSION)
+# one row per pair of labels that share a voxel (include/rcu.h, rcu_cc_pair)
+PAIR_DTYPE = np.dtype([('a', '<u4'), ('b', '<u4'), ('voxels', '<u4'), ('inside_voxels', '<u4')])
+PAIR_MIN_CAPACITY, PAIR_MAX_CAPACITY = 64, 1 << 26
+LESION_COUNT_KEYS = ('n_lesions', 'n_predicted', 'n_matched', 'n_fp_components', 'n_missed_lesions')
+LESION_METRIC_KEYS = LESION_COUNT_KEYS + ('lesion_dice', 'lesion_recall', 'lesion_precision', 'lesion_f1', 'sq', 'pq', 'auroc_unmatched',
+                                          'auprc_unmatched', 'lesion_dice_filtered_max', 'lesion_dice_filtered_max_threshold',
+                                          'lesion_f1_filtered_max', 'lesion_f1_filtered_max_threshold')
+LESION_CURVE_KEYS = ('n_predicted', 'n_matched', 'lesion_recall', 'fdr', 'lesion_dice')
+LESION_LIST_KEYS = ('lesion', 'root_index', 'voxels', 'dilated_voxels', 'n_touching', 'touching_voxels', 'overlap', 'dice', 'matched_component', 'iou')
+MERGE_RADIUS_MAX = 46340        # its square stays below 2^31: the squared distances are compared as int32 bit patterns
+
+
+def _next_power_of_two(x):
+    return 1 << max(0, int(x) - 1).bit_length()
+
+
+def pair_capacity(n_a, n_b):
+    """The default slots per volume for labellings with ids up to ``n_a`` and ``n_b``: the next power of two >= 4 (n_a + n_b + 2), at least 1024."""
+    return max(1024, _next_power_of_two(4 * (int(n_a) + int(n_b) + 2)))
+
+
+def _pairs_launch(a, b, inside, capacity):
+    """Device label maps [V, n] -> the device buffer of rcu_cc_pairs (slots, then counters); asynchronous on the current stream."""
+    v, n = a.shape
+    lib = _lib.load()
+    nbytes = lib.rcu_cc_pairs_bytes(int(capacity), v)
+    table = torch.empty(max(nbytes, 8), device=a.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_cc_pairs(_lib.ptr(a), _lib.ptr(b), _lib.ptr(inside), n, v, int(capacity), _lib.ptr(table), _lib.current_stream()))
+    return table
+
+
+def _pairs_unpack(table, capacity, v):
+    """-> (counters uint32 [V, 2] = used, dropped; list of V host tables of PAIR_DTYPE sorted by (a, b)).  Only the claimed slots travel."""
+    slot_bytes = (v * capacity * PAIR_DTYPE.itemsize + 255) & ~255
+    counters = table[slot_bytes:slot_bytes + 8 * v].cpu().numpy().view(np.uint32).reshape(v, 2).copy()
+    slots = table[:v * capacity * PAIR_DTYPE.itemsize].view(torch.int32).reshape(v, capacity, 4)
+    where = (slots[:, :, 0] != 0).nonzero()        # (a claimed slot holds a > 0)
+    volume = where[:, 0].cpu().numpy()
+    rows = slots[where[:, 0], where[:, 1]].cpu().numpy().reshape(-1, 4)
+    out = []
+    for k in range(v):
+        mine = np.ascontiguousarray(rows[volume == k]).view(PAIR_DTYPE).reshape(-1)
+        out.append(mine[np.lexsort((mine['b'], mine['a']))].copy())
+    return counters, out
+
+
+def _pairs_on_device(a, b, inside, capacity):
+    """``component_pairs`` for device arrays [V, n]: a table that reports dropped voxels is made again with twice the slots -- a reaction to
+    a full table, at most log2 steps: the next power of two >= 2 n holds any volume's pairs."""
+    v, n = a.shape
+    enough = min(PAIR_MAX_CAPACITY, max(PAIR_MIN_CAPACITY, _next_power_of_two(2 * n)))
+    while True:
+        counters, tables = _pairs_unpack(_pairs_launch(a, b, inside, capacity), capacity, v)
+        if not counters[:, 1].any():
+            return tables
+        if capacity >= enough:
+            raise RuntimeError('rcu_cc_pairs dropped voxels at capacity {}: more pairs than the largest table holds'.format(capacity))
+        capacity = min(enough, 2 * capacity)
+
+
+def component_pairs(a_labels, b_labels, inside=None, n_volumes=1, capacity=None):
+    """The sparse joint table of two labellings on the GPU -> one structured array (PAIR_DTYPE) per volume, sorted by (a, b): for every pair of
+    a positive label a of ``a_labels`` and a positive label b of ``b_labels`` that share a voxel, ``voxels`` = how many and ``inside_voxels`` =
+    how many of those where ``inside`` is not 0 (0 without it) -- ``np.unique`` over the stacked label pairs, in one pass over resident maps.
+    int32 label maps (0 and negative values: background; dense labels or canonical ones), numpy arrays or device tensors.  ``capacity``:
+    hash slots per volume, a power of two in 64..2^26; by default ``pair_capacity`` of the largest labels, and whenever the table reports
+    dropped voxels it is made again with twice the slots, up to the next power of two >= 2 n, which always suffices.  Integer adds: the
+    same table whatever the launch geometry, the batching or the capacity."""
+    a = _flat(a_labels, torch.int32, n_volumes)
+    b = _flat(b_labels, torch.int32, n_volumes, a, 'a_labels and b_labels')
+    i = _flat(inside, torch.uint8, n_volumes, a, 'a_labels and inside')
+    if capacity is None:
+        n = a.shape[1]
+        capacity = min(pair_capacity(min(max(int(a.max()), 0), n), min(max(int(b.max()), 0), n)),
+                       max(PAIR_MIN_CAPACITY, _next_power_of_two(2 * n)), PAIR_MAX_CAPACITY)
+    capacity = int(capacity)
+    if not PAIR_MIN_CAPACITY <= capacity <= PAIR_MAX_CAPACITY or capacity & (capacity - 1):
+        raise ValueError('capacity must be a power of two in 64..2^26, got {}'.format(capacity))
+    return _pairs_on_device(a, b, i, capacity)
+
+
+def _check_merge_radius(merge_radius):
+    if int(merge_radius) != merge_radius or not 0 <= int(merge_radius) <= MERGE_RADIUS_MAX:
+        raise ValueError('merge_radius must be an integer in 0..{}, got {}'.format(MERGE_RADIUS_MAX, merge_radius))
+    return int(merge_radius)
+
+
+def _labelling_on_device(mask, dims, connectivity):
+    """-> (canonical labels, components per volume, the workspace with the roots' ranks) of device masks [V, n]."""
+    labels = _labels_on_device(mask, dims, connectivity)
+    return (labels,) + _compact_on_device(labels)
+
+
+def _dense_of_labelling(labels, ws):
+    dense = torch.empty_like(labels)
+    _lib.check(_lib.load().rcu_cc_relabel(_lib.ptr(labels), labels.shape[1], labels.shape[0], _lib.ptr(ws), _lib.ptr(dense), _lib.current_stream()))
+    return dense
+
+
+def _lesion_tables_on_device(prediction, target, dims, unc_kind, unc, connectivity, merge_radius, labelling=None, pred_tables=None):
+    """``lesion_tables`` for device arrays [V, n]; ``labelling`` / ``pred_tables``: the prediction's, where somebody made them already."""
+    v, n = prediction.shape
+    if labelling is None:
+        labelling = _labelling_on_device(prediction, dims, connectivity)
+    if pred_tables is None:
+        pred_tables = _tables_of_labels(*labelling, target, unc_kind, unc)
+    if merge_radius == 0:
+        dilated = target
+    else:       # the Euclidean ball: squared distance to the nearest target voxel <= r^2, compared as unsigned (EDT_NONE's int32 view is -1)
+        sq = _edt_on_device(target, dims, 0)
+        dilated = ((sq >= 0) & (sq <= merge_radius * merge_radius)).to(torch.uint8)
+    lesions = _labelling_on_device(dilated, dims, connectivity)
+    lesion_tables = _tables_of_labels(*lesions, target, _lib.RCU_CC_UNC_NONE, None)
+    capacity = min(pair_capacity(labelling[1].max() if v else 0, lesions[1].max() if v else 0), PAIR_MAX_CAPACITY)
+    pairs = _pairs_on_device(_dense_of_labelling(labelling[0], labelling[2]), _dense_of_labelling(lesions[0], lesions[2]), target, capacity)
+    return [(pred_tables[k], lesion_tables[k], pairs[k]) for k in range(v)]
+
+
+def lesion_tables(prediction, target, uncertainty=None, connectivity=26, merge_radius=0, n_volumes=1):
+    """Everything the lesion-wise metrics need of a prediction and a target, on the GPU, all volumes through each kernel once -> per volume the
+    triple
+      components   ``component_table(prediction, target, uncertainty, connectivity)``: the predicted components
+      lesions      the table (COMPONENT_DTYPE) of the target's LESIONS: with ``merge_radius`` r = 0 the target's components; with r > 0 the
+                   components of the Euclidean dilation {squared distance to the nearest target voxel <= r^2} (``distance_transform_sq``), each
+                   owning the target voxels inside it -- lesions closer than the dilation are one lesion (BraTS 2023, with a Euclidean ball
+                   where BraTS iterates a 3 x 3 x 3 box).  ``voxels`` = the dilated size, ``other_voxels`` = the lesion's true size; a volume
+                   without target voxels has no lesions
+      pairs        ``component_pairs(predicted labels, lesion labels, inside=target)``, both labellings dense (1..K in table order): ``voxels`` =
+                   the overlap of component a with the dilation of lesion b, ``inside_voxels`` = its overlap with the lesion itself
+    Accepts what ``component_table`` accepts."""
+    merge_radius = _check_merge_radius(merge_radius)
+    dims = _volume_dims(_split_volumes(prediction.shape, n_volumes))
+    pr = _flat(prediction, torch.uint8, n_volumes)
+    tg = _flat(target, torch.uint8, n_volumes, pr, 'prediction and target')
+    kind, u = _uncertainty_source(uncertainty, None, n_volumes, pr, 'prediction and uncertainty')
+    return _lesion_tables_on_device(pr, tg, dims, kind, u, connectivity, merge_radius)
+
+
+class _ExactSum:
+    """A running sum of float64 terms that can take a term back: Shewchuk's non-overlapping partials (what ``math.fsum`` keeps) hold the
+    exact sum, ``value`` rounds it once -- whatever the order of the additions and removals."""
+
+    def __init__(self):
+        self.partials = []
+
+    def add(self, x):
+        i = 0
+        for y in self.partials:
+            if abs(x) < abs(y):
+                x, y = y, x
+            hi = x + y
+            lo = y - (hi - x)
+            if lo:
+                self.partials[i] = lo
+                i += 1
+            x = hi
+        self.partials[i:] = [x]
+
+    def value(self):
+        return math.fsum(self.partials)
+
+
+def _is_one_subject(tables):
+    return len(tables) == 3 and all(isinstance(t, np.ndarray) and t.dtype.names is not None for t in tables)
+
+
+def _ratio(num, den):
+    return num / den if den else float('nan')
+
+
+def lesion_analysis(tables, levels=UE_LEVELS, match_iou=0.5, min_lesion_voxels=0):
+    """-> (metrics: dict with the keys ``LESION_METRIC_KEYS``, curve: one dict with the keys ``LESION_CURVE_KEYS`` per threshold k / levels,
+    k = 0..levels, lesions: per subject one dict with the keys ``LESION_LIST_KEYS`` per kept lesion).  ``lesion_metrics`` says what they are."""
+    levels, min_lesion_voxels, match_iou = int(levels), int(min_lesion_voxels), float(match_iou)
+    if levels < 1:
+        raise ValueError('levels must be >= 1, got {}'.format(levels))
+    if not 0.5 <= match_iou < 1.0:
+        raise ValueError('match_iou must be in [0.5, 1): only above an IoU of 0.5 is the matching one-to-one; got {}'.format(match_iou))
+    if min_lesion_voxels < 0:
+        raise ValueError('min_lesion_voxels must be >= 0, got {}'.format(min_lesion_voxels))
+    subjects = [tables] if _is_one_subject(tables) else list(tables)
+    grid = [k / levels for k in range(levels + 1)]
+    size, mean, cut, touched_by, matched_iou = {}, {}, {}, {}, {}       # per predicted component (subject, a)
+    true_size, touching = {}, {}                               # per kept lesion (subject, g): t_g, [(component id, i(a, g))]
+    listed = []
+    for s_, (components, lesions, pairs) in enumerate(subjects):
+        for k, row in enumerate(components):
+            voxels = int(row['voxels'])
+            a = (s_, k + 1)
+            size[a], mean[a], touched_by[a] = voxels, int(row['unc_sum']) / (voxels * COMPONENT_UNC_ONE), 0
+            cut[a] = bisect.bisect_left(grid, mean[a])
+        kept = {}
+        for k, row in enumerate(lesions):
+            if int(row['other_voxels']) >= max(min_lesion_voxels, 1):
+                kept[k + 1] = row
+                true_size[(s_, k + 1)] = int(row['other_voxels'])
+                touching[(s_, k + 1)] = []
+        for row in pairs:
+            a, g = (s_, int(row['a'])), (s_, int(row['b']))
+            if g in touching and int(row['voxels']) > 0:
+                touching[g].append((a, int(row['inside_voxels'])))
+                touched_by[a] += 1
+        rows = []
+        for k, row in kept.items():
+            g = (s_, k)
+            t_g, mine = true_size[g], sorted(touching[g])
+            overlap, union = sum(i for _, i in mine), sum(size[a] for a, _ in mine)
+            best, best_a = 0.0, 0
+            for a, i in mine:
+                iou = i / (size[a] + t_g - i)
+                if iou > best:
+                    best, best_a = iou, a[1]
+                if iou > match_iou:
+                    matched_iou[a] = iou
+            rows.append({'lesion': k, 'root_index': int(row['root']), 'voxels': t_g, 'dilated_voxels': int(row['voxels']), 'n_touching': len(mine),
+                         'touching_voxels': union, 'overlap': overlap, 'dice': 2 * overlap / (t_g + union),
+                         'matched_component': best_a if best > match_iou else 0, 'iou': best})
+        listed.append(rows)
+    n_lesions, n_predicted, n_matched = len(true_size), len(size), len(matched_iou)
+    total_iou = math.fsum(matched_iou.values())
+    out = {'n_lesions': n_lesions, 'n_predicted': n_predicted, 'n_matched': n_matched,
+           'n_fp_components': sum(1 for t in touched_by.values() if t == 0), 'n_missed_lesions': sum(1 for t in touching.values() if not t)}
+    # detection of the unmatched components by their mean uncertainty: the distinct scores ascending, (unmatched, matched) counts
+    groups = {}
+    for a, m_ in mean.items():
+        groups.setdefault(m_, [0, 0])[1 if a in matched_iou else 0] += 1
+    # the filtering curve: component a is there from threshold cut_a / levels on; per-lesion sums and the exact sum of the lesions' Dice follow
+    arriving = {}
+    for a, c in cut.items():
+        arriving.setdefault(c, []).append(a)
+    of_component = {}
+    for g, mine in touching.items():
+        for a, i in mine:
+            of_component.setdefault(a, []).append((g, i))
+    overlap, union, dice = dict.fromkeys(touching, 0), dict.fromkeys(touching, 0), dict.fromkeys(touching, 0.0)
+    dice_sum = _ExactSum()
+    present = present_matched = present_fp = 0
+    curve, best_dice, best_f1 = [], None, None
+    for k in range(levels + 1):
+        for a in arriving.get(k, ()):
+            present += 1
+            present_matched += a in matched_iou
+            present_fp += touched_by[a] == 0
+            for g, i in of_component.get(a, ()):
+                overlap[g] += i
+                union[g] += size[a]
+                d = 2 * overlap[g] / (true_size[g] + union[g])
+                dice_sum.add(-dice[g])
+                dice_sum.add(d)
+                dice[g] = d
+        row = {'n_predicted': present, 'n_matched': present_matched, 'lesion_recall': _ratio(present_matched, n_lesions),
+               'fdr': _ratio(present - present_matched, present), 'lesion_dice': _ratio(dice_sum.value(), n_lesions + present_fp)}
+        curve.append(row)
+        f1 = _ratio(2 * present_matched, n_lesions + present)
+        if best_dice is None or row['lesion_dice'] > best_dice[0] or (best_dice[0] != best_dice[0] and row['lesion_dice'] == row['lesion_dice']):
+            best_dice = (row['lesion_dice'], k)       # (a NaN -- nothing to judge at that threshold -- loses to any number)
+        if best_f1 is None or f1 > best_f1[0] or (best_f1[0] != best_f1[0] and f1 == f1):
+            best_f1 = (f1, k)
+    last = curve[-1]       # m_a <= 1: the last threshold removes nothing
+    out.update(lesion_dice=last['lesion_dice'], lesion_recall=_ratio(n_matched, n_lesions), lesion_precision=_ratio(n_matched, n_predicted),
+               lesion_f1=_ratio(2 * n_matched, n_lesions + n_predicted), sq=_ratio(total_iou, n_matched), pq=_ratio(2 * total_iou, n_lesions + n_predicted))
+    out['auroc_unmatched'], out['auprc_unmatched'] = _rank_metrics(groups[score] for score in sorted(groups))
+    out.update(lesion_dice_filtered_max=best_dice[0], lesion_dice_filtered_max_threshold=best_dice[1] / levels,
+               lesion_f1_filtered_max=best_f1[0], lesion_f1_filtered_max_threshold=best_f1[1] / levels)
+    return out, curve, listed
+
+
+def lesion_metrics(tables, levels=UE_LEVELS, match_iou=0.5, min_lesion_voxels=0):
+    """Lesion-wise metrics of one subject's ``lesion_tables`` triple, or of a list of subjects' triples -- the subject is then part of every
+    id, and nothing depends on the order of the subjects or of the rows -> dict with the keys ``LESION_METRIC_KEYS``.  Host arithmetic on
+    Python integers, every ratio rounded once, sums of ratios exactly rounded (``math.fsum``).  With s_a and m_a = unc_sum_a / (s_a 2^24) the
+    size and mean uncertainty of predicted component a, t_g the true size of lesion g (``other_voxels`` of its row), v(a, g) and i(a, g) the
+    pair's ``voxels`` and ``inside_voxels``:
+      lesions with t_g < ``min_lesion_voxels`` are dropped as if they were background, their pairs with them
+      touch(g) = {a : v(a, g) > 0};   d_g = 2 sum_{a in touch(g)} i(a, g) / (t_g + sum_{a in touch(g)} s_a): the Dice of lesion g against the
+                 union of the predicted components that touch its dilation;   a component that touches no kept lesion is a false positive
+      lesion_dice   sum_g d_g / (n_lesions + n_fp_components) (BraTS 2023's lesion-wise Dice);   n_missed_lesions: touch(g) empty
+      IoU(a, g) = i(a, g) / (s_a + t_g - i(a, g));   a and g MATCH iff IoU > ``match_iou``, in [0.5, 1): one-to-one, because the regions of
+                 either side are disjoint;   n_matched = TP
+      lesion_recall TP / n_lesions, lesion_precision TP / n_predicted, lesion_f1 2 TP / (n_lesions + n_predicted), sq = the mean IoU of the
+                 matches, pq = sum IoU / (TP + (n_predicted - TP) / 2 + (n_lesions - TP) / 2) (panoptic quality, Kirillov et al. 2019)
+      auroc_unmatched, auprc_unmatched   detection of the unmatched predicted components by m_a (``component_metrics``' auroc_fp formulas)
+      lesion_dice_filtered_max, lesion_f1_filtered_max, each with _threshold   over the thresholds k / levels, k = 0..levels, the components
+                 with m_a > k / levels (float64) removed: the maximum and the smallest threshold that attains it (Nair et al. 2020's
+                 filtering of lesions by their uncertainty)
+    Every ratio with a zero denominator is NaN."""
+    return lesion_analysis(tables, levels, match_iou, min_lesion_voxels)[0]
 
 
 def _counts(prediction, target, uncertainty, thresholds, mask=None):
