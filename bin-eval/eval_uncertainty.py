@@ -9,7 +9,18 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-if __name__ == '__main__':
+
+def _int_in(lo, hi):
+    """argparse type: an integer in lo..hi (anything else is a usage error)."""
+    def parse(text):
+        value = int(text)
+        if not lo <= value <= hi:
+            raise argparse.ArgumentTypeError('must be in {}..{}, got {}'.format(lo, hi, value))
+        return value
+    return parse
+
+
+def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--ds', type=str, nargs='?', help='the dataset to evaluate the runs on')
     parser.add_argument('--ids', type=str, nargs='*', help='the ids of the runs to be evaluated')
@@ -19,7 +30,8 @@ if __name__ == '__main__':
                         'boundary (errors and uncertainty by distance to the target\'s boundary, surface distances, metrics off the border shell), agreement '
                         '(the run\'s agreement.csv -- written under others.agreement: true -- against each subject\'s Dice: correlations, failure detection) and lesions '
                         '(lesion-wise Dice, lesion F1, panoptic quality and the filtering of predicted lesions by uncertainty, from the joint table of '
-                        'predicted components and target lesions)')
+                        'predicted components and target lesions) and patches (patch accuracy vs. patch uncertainty of Mukhoti & Gal 2018 -- p(accurate | certain), '
+                        'p(uncertain | inaccurate), PAvPU -- over a grid of non-overlapping windows, from a patch table made on the GPU)')
     parser.add_argument('--pred_dir', type=str, default=None, help='root with one sub-directory per dataset and run id '
                         '(default: directories.PREDICT_DIR and the per-run *_PREDICT names)')
     parser.add_argument('--gt_dir', type=str, default=None, help='BraTS training tree / ISIC dataset prefix '
@@ -27,7 +39,7 @@ if __name__ == '__main__':
     parser.add_argument('--out_dir', type=str, default=None, help='default: directories.EVAL_DIR')
     parser.add_argument('--batch_subjects', type=int, default=8, help='rcu_amd: subjects of a probability-map run evaluated per GPU launch')
     parser.add_argument('--levels', type=int, default=1000, help='rcu_amd: uncertainty levels of the ue_curves action and threshold grid of the '
-                        'components and lesions actions (2..4096)')
+                        'components and lesions actions and levels of the patch histogram of the patches action (2..4096)')
     parser.add_argument('--connectivity', type=int, default=26, choices=(6, 26), help='rcu_amd: neighbourhood of the components and lesions actions (2-D images: 4 / 8)')
     parser.add_argument('--merge_radius', type=int, default=0, help='rcu_amd: the lesions action counts target components closer than this Euclidean '
                         'dilation (in voxels) as one lesion; 0: the target\'s components')
@@ -43,8 +55,17 @@ if __name__ == '__main__':
     parser.add_argument('--mass_bins', type=int, default=10, help='rcu_amd: equal-mass bins of the calib_curves action')
     parser.add_argument('--recalibrate_from', type=str, default=None, help='rcu_amd: an eval_calib_levels_<id>.csv of another run (the validation run, '
                         'evaluated with the same --levels): the calib_curves action also reports Brier, NLL and ECE under that run\'s isotonic map')
+    parser.add_argument('--patch', type=_int_in(1, 16), default=4, help='rcu_amd: in-plane edge of the windows of the patches action, in voxels (1..16)')
+    parser.add_argument('--patch_depth', type=_int_in(1, 16), default=1, help='rcu_amd: depth of the windows of the patches action in slices (1..16); the '
+                        'default 1 gives windows on the slices a 2-D network saw, --patch_depth 4 with --patch 4 gives cubes')
+    parser.add_argument('--patch_accuracy', type=_int_in(0, 999), default=500, help='rcu_amd: the patches action counts a window as accurate when more '
+                        'than this many per mille of its voxels are predicted correctly (0..999)')
     parser.add_argument('--plain', action='store_true', help='rcu_amd: the reference\'s subject-by-subject, action-by-action loop for every run')
-    args = parser.parse_args()
+    return parser
+
+
+if __name__ == '__main__':
+    args = make_parser().parse_args()
     from rcu_amd import directories as dirs
     from rcu_amd import scripts
     ds = args.ds or 'brats'
@@ -66,4 +87,5 @@ if __name__ == '__main__':
     scripts.eval_uncertainty(ds, runs, gt_dir, out_dir, acts, fused=not args.plain, batch_subjects=args.batch_subjects,
                              levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail,
                              calib_bins=args.calib_bins, mass_bins=args.mass_bins, recalibrate_from=args.recalibrate_from,
-                             merge_radius=args.merge_radius, min_lesion_voxels=args.min_lesion_voxels, match_iou=args.match_iou)
+                             merge_radius=args.merge_radius, min_lesion_voxels=args.min_lesion_voxels, match_iou=args.match_iou,
+                             patch=(args.patch_depth, args.patch, args.patch), patch_accuracy=args.patch_accuracy)

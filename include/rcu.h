@@ -692,6 +692,38 @@ int rcu_mc_votes(const float* in_dev, size_t n, size_t hw, int nb_classes, int f
 int rcu_agreement_tables(const uint32_t* votes_dev, int n_words, size_t n_per_volume, int n_volumes, int passes, uint64_t* hist_dev,
                          uint64_t* pairs_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Patch-level uncertainty (EXTENSION: the patch accuracy vs. patch uncertainty family of Mukhoti & Gal, Evaluating Bayesian Deep Learning Methods
+ * for Semantic Segmentation, 2018 -- p(accurate | certain), p(uncertain | inaccurate), PAvPU; rcu_amd.evaluation.patch_table, patch_histogram,
+ * pavpu_metrics and the 'patches' evaluation action)
+ *   Grid.  n_volumes independent volumes of depth x height x width voxels, laid out as for rcu_cc_label.  A volume is cut into non-overlapping
+ *   patches of pd x ph x pw voxels (each extent in 1..RCU_PATCH_MAX_EXTENT) anchored at the origin: patch (gz, gy, gx) holds the voxels with
+ *   z / pd == gz, y / ph == gy, x / pw == gx; the patches at the far edges are partial.  rcu_patch_count = ceil(depth / pd) * ceil(height / ph) *
+ *   ceil(width / pw) patches per volume, numbered in raster order (gx fastest); 0 for arguments out of range.  Depth 1 gives the 2-D grid.
+ *   Table.  table_dev is uint64 [n_volumes][patches][4], the row of a patch {n, errors, foreground, sum_q} over its voxels whose mask byte is
+ *   not 0 (every voxel with a null mask_dev):
+ *       n            the number of such voxels                     errors   those with (prediction != 0) != (target != 0)
+ *       foreground   those with prediction != 0 or target != 0     sum_q    the sum of q(u), q and the uncertainty sources being rcu_cc_table's
+ *   (RCU_CC_UNC_NONE / _F32 / _F64 / _P, the same arithmetic and the same argument check; RCU_CC_UNC_NONE leaves sum_q 0).  A patch has at most
+ *   4096 voxels, so sum_q <= 2^36.  Integers, one lane per patch (csrc/rcu_patch.hip): the table is a function of the inputs alone, whatever the
+ *   launch geometry, the batching (volumes in one call or in several) or the alignment of a volume's first element.
+ *   Histogram.  hist_dev is uint64 [n_volumes][3][levels], zeroed here: every table row with n != 0 adds 1 to hist[cell][level] with
+ *       cell 0   accurate patch that holds foreground: 1000 (n - errors) > accuracy_per_mille n, and foreground > 0
+ *       cell 1   inaccurate patch (it necessarily holds foreground)            cell 2   accurate patch of pure background
+ *       level    the level of the patch's mean uncertainty sum_q / (n 2^24) under the rule of rcu_unc_hist, level(u) = #{k in 1..levels-1 : u > k /
+ *                levels}, taken IN INTEGERS: #{k : sum_q levels > k n 2^24} = min(levels - 1, (sum_q levels - 1) div (n 2^24)) for sum_q > 0, else 0
+ *   (rows of rcu_patch_table keep every product below 2^49).  Histograms of volumes add.
+ *   Limits: depth * height * width and n_patches in 1..2^31 - 2, n_volumes in 1..65535, levels in 2..RCU_UNC_HIST_MAX_LEVELS, accuracy_per_mille in
+ *   0..999.  Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it).
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_PATCH_MAX_EXTENT 16
+size_t rcu_patch_count(int depth, int height, int width, int pd, int ph, int pw);
+int rcu_patch_table(const uint8_t* prediction_dev, const uint8_t* target_dev, const uint8_t* mask_dev /* may be null */, const void* unc_dev,
+                    int unc_kind /* RCU_CC_UNC_* */, int depth, int height, int width, int n_volumes, int pd, int ph, int pw,
+                    uint64_t* table_dev /* [n_volumes][patches][4] */, void* stream);
+int rcu_patch_hist(const uint64_t* table_dev, size_t n_patches, int n_volumes, int levels, int accuracy_per_mille,
+                   uint64_t* hist_dev /* [n_volumes][3][levels] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,8 @@ RCU_TEMPERATURE_MAX_CANDIDATES = 128
 RCU_LOGIT_MAX_SAMPLES = 1024
 # sample agreement (include/rcu.h): passes a vote plane holds (32 per uint32 word)
 RCU_VOTES_MAX_PASSES = 64
+# patch-level uncertainty (include/rcu.h): the largest extent of a patch along an axis
+RCU_PATCH_MAX_EXTENT = 16
 TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
@@ -167,6 +169,9 @@ SIGNATURES = {
                                                   c_void_p]),
     'rcu_mc_votes': (c_int, [c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     'rcu_agreement_tables': (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'rcu_patch_count': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    'rcu_patch_table': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_patch_hist': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -4,7 +4,7 @@ Mirrors
   CSV hooks            rechun/eval/hook.py:10-116 (WriteCsvHook, WriteBinsCsvHook, WriteSummaryCsvHook)
   file / run registry  rechun/eval/evaldata.py:8-103, common/data/collector.py:120-174, rechun/directories.py:56-71
   loader               rechun/eval/analysis.py:15-125 (probabilities / target>0 / prediction / T2 brain mask, cached)
-  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components, boundary, agreement, calib_curves and lesions are extensions
+  actions + driver     bin-eval/eval_uncertainty.py:13-244 (minmax, ece_dice, calib, bnf_ue); ue_curves, components, boundary, agreement, calib_curves, lesions and patches are extensions
 so that the CSV files ``bin-analysis/*`` consumes keep their names, columns and row order.  The volumes
 are read with rcu_amd.nifti, the per-voxel work (histograms, counts, entropy) runs through
 rcu_amd.evaluation on the GPU; the ``bnf_ue`` action evaluates its 11 thresholds in ONE pass per subject
@@ -48,6 +48,11 @@ COMPONENT_LIST_PLACEHOLDER = 'eval_component_list_{}.csv'
 BOUNDARY_PLACEHOLDER = 'eval_boundary_{}.csv'
 BOUNDARY_POOLED_PLACEHOLDER = 'eval_boundary_pooled_{}.csv'
 BOUNDARY_BANDS_PLACEHOLDER = 'eval_boundary_bands_{}.csv'
+# rcu_amd extension (the 'patches' action), in UNCERTAINTY_NAME as well
+PATCHES_PLACEHOLDER = 'eval_patches_{}.csv'
+PATCHES_POOLED_PLACEHOLDER = 'eval_patches_pooled_{}.csv'
+PATCH_LEVELS_PLACEHOLDER = 'eval_patch_levels_{}.csv'
+PATCH_LEVELS_COLUMNS = ('level', 'threshold', 'accurate_fg', 'inaccurate', 'accurate_bg', 'pavpu', 'p_ac', 'p_ui')
 # rcu_amd extension (the 'lesions' action), in UNCERTAINTY_NAME as well
 LESIONS_PLACEHOLDER = 'eval_lesions_{}.csv'
 LESIONS_POOLED_PLACEHOLDER = 'eval_lesions_pooled_{}.csv'
@@ -541,6 +546,49 @@ class UeCurvesAction(UncertaintyAction):
                 writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]])
 
 
+class PatchesAction(UncertaintyAction):
+    """EXTENSION (the reference has no such action): patch accuracy vs. patch uncertainty (Mukhoti & Gal, 2018) from one patch histogram per
+    subject (evaluation.patch_histogram / pavpu_metrics) over a grid of non-overlapping windows of ``patch`` = (depth, height, width) voxels,
+    a patch being accurate when more than ``accuracy_per_mille`` / 1000 of its voxels are.  Prepared exactly like ``UeCurvesAction`` -- any
+    confidence entry, no brain mask.  Files in ``<base_dir>/uncertainty``:
+      eval_patches_<id>.csv          one row per subject: the keys of evaluation.PAVPU_KEYS
+      eval_patches_pooled_<id>.csv   the same metrics of the SUM of the subjects' histograms (integers: whatever the batching or order)
+      eval_patch_levels_<id>.csv     that pooled histogram, one row per level: level, threshold = level / levels, the patches of the level
+                                     that are accurate with foreground / inaccurate / accurate pure background, and PAvPU, p(accurate |
+                                     certain) and p(uncertain | inaccurate) over all patches with "uncertain" := level >= this one (empty
+                                     at level 0, where there is no threshold)"""
+
+    def __init__(self, levels, patch, accuracy_per_mille, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        self.levels = self.checked_levels(levels)
+        self.patch, self.accuracy_per_mille = ev._check_patch(patch), ev._check_per_mille(accuracy_per_mille)
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
+        self.pooled = None
+
+    def setup_run(self):
+        self.subject_rows(PATCHES_PLACEHOLDER, ev.PAVPU_KEYS)
+        self.pooled = np.zeros((3, self.levels), dtype=np.uint64)
+
+    def record_histogram(self, hist, subject_name):
+        """One subject's patch histogram ``[3, levels]``: its metrics row, and its share of the pooled histogram."""
+        self.eval_cases[0].record(ev.pavpu_metrics(hist), subject_name, self.id_)
+        self.pooled += np.asarray(hist, dtype=np.uint64)
+
+    def eval_subject(self, sf, loader):
+        to_eval = self.prepared(sf, loader)
+        self.record_histogram(ev.patch_histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], patch=self.patch,
+                                                 levels=self.levels, accuracy_per_mille=self.accuracy_per_mille)[0], sf.subject)
+
+    def finish_eval(self):
+        super().finish_eval()
+        self.write_pooled_row(os.path.join(self.out_dir, PATCHES_POOLED_PLACEHOLDER.format(self.id_)), ev.PAVPU_KEYS, ev.pavpu_metrics(self.pooled))
+        curve = ev.pavpu_curve(self.pooled)
+        with open(os.path.join(self.out_dir, PATCH_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(PATCH_LEVELS_COLUMNS)
+            for level in range(self.levels):
+                writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]] + list(curve[level] or ('', '', '')))
+
+
 class ComponentsAction(UncertaintyAction):
     """EXTENSION (the reference has no such action): component-level uncertainty metrics from connected components labelled on the GPU
     (evaluation.component_table / component_metrics).  The uncertainty is prepared exactly like ``UeCurvesAction``'s -- the entropy of a
@@ -882,14 +930,16 @@ ECE_TYPES = {EceAction, EceCalibrationAction}
 
 
 def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8, calib_bins=10,
-                mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5):
+                mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500):
     """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
     (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice), 'boundary' (``bands``: its distance bands, 1..64;
     ``levels``: of its off-border level histogram) and 'calib_curves' (``levels``: of its calibration level histogram; ``calib_bins``: the
     equal-width bins of its ECE, a divisor of ``levels``; ``mass_bins``: of its equal-mass ECE; ``recalibrate_from``: the levels file of
     another run whose isotonic map is to be judged) and 'lesions' (``connectivity``, ``levels`` as 'components'; ``merge_radius``: target
     lesions closer than this Euclidean dilation are one lesion; ``min_lesion_voxels``: smaller lesions count as background; ``match_iou``:
-    the IoU above which a component and a lesion match, in [0.5, 1))."""
+    the IoU above which a component and a lesion match, in [0.5, 1)) and 'patches' (``patch``: the (depth, height, width) extents of its
+    windows, each in 1..16; ``patch_accuracy``: a patch is accurate when more than this many per mille of its voxels are; ``levels``: of its
+    patch histogram)."""
     actions = []
     for name in action_names:
         if name == 'minmax':
@@ -902,6 +952,8 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
             actions.append(CorrectionAction(ev.UE_THRESHOLDS, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'ue_curves':
             actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
+        elif name == 'patches':
+            actions.append(PatchesAction(levels, patch, patch_accuracy, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'components':
             actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
         elif name == 'lesions':
@@ -1004,7 +1056,7 @@ def _fusable(entry, actions):
     masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES | {CalibCurvesAction}}
     return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
             all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction,
-                            AgreementAction, CalibCurvesAction, LesionsAction)
+                            AgreementAction, CalibCurvesAction, LesionsAction, PatchesAction)
                 for a in actions) and
             all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
 
@@ -1013,7 +1065,8 @@ def metrics_wanted(actions):
     """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
     list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
     by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`, 'calib_levels' by a
-    CalibCurvesAction, which holds `levels` as well, 'lesions' by a LesionsAction, which holds `connectivity` and `merge_radius`)."""
+    CalibCurvesAction, which holds `levels` as well, 'lesions' by a LesionsAction, which holds `connectivity` and `merge_radius`, 'patches' by
+    a PatchesAction, which holds `levels`, `patch` and `accuracy_per_mille`)."""
     by_type = {type(a): a for a in actions}
     want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
            (['ue'] if (CorrectionAction in by_type or AgreementAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
@@ -1021,7 +1074,8 @@ def metrics_wanted(actions):
            (['components'] if ComponentsAction in by_type else []) + \
            (['boundary'] if BoundaryAction in by_type else []) + \
            (['calib_levels'] if CalibCurvesAction in by_type else []) + \
-           (['lesions'] if LesionsAction in by_type else [])
+           (['lesions'] if LesionsAction in by_type else []) + \
+           (['patches'] if PatchesAction in by_type else [])
     ue = by_type.get(CorrectionAction)
     want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
     return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
@@ -1059,6 +1113,8 @@ def record_subject(actions, subject, res, slot, n_dim):
                 case.record(ev.correction_results(counts[t]), subject, action.id_)
         elif isinstance(action, UeCurvesAction):
             action.record_histogram(res['ue_hist'][slot], subject)
+        elif isinstance(action, PatchesAction):
+            action.record_histogram(res['patch_hist'][slot], subject)
         elif isinstance(action, ComponentsAction):
             action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
         elif isinstance(action, LesionsAction):
@@ -1079,7 +1135,8 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     fn are ece_dice's confusion matrix), min / max -- and the results fanned out to the actions' CSV hooks in subject order.  The rows are
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
     want, thresholds, want_mask = metrics_wanted(actions)
-    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction, CalibCurvesAction))), ev.UE_LEVELS)
+    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction, CalibCurvesAction, PatchesAction))), ev.UE_LEVELS)
+    patch, patch_accuracy = next(((a.patch, a.accuracy_per_mille) for a in actions if isinstance(a, PatchesAction)), (ev.PATCH_DEFAULT, 500))
     bands = next((a.bands for a in actions if isinstance(a, BoundaryAction)), 10)
     connectivity = next((a.connectivity for a in actions if isinstance(a, (ComponentsAction, LesionsAction))), 26)
     merge_radius = next((a.merge_radius for a in actions if isinstance(a, LesionsAction)), 0)
@@ -1109,7 +1166,8 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands, merge_radius=merge_radius)
+            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands, merge_radius=merge_radius,
+                                patch=patch, accuracy_per_mille=patch_accuracy)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)
@@ -1140,7 +1198,7 @@ class _Done:
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
                   connectivity=26, bands=10, dice_fail=0.8, calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0,
-                  match_iou=0.5):
+                  match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
@@ -1148,9 +1206,9 @@ def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
     'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action; ``calib_bins``, ``mass_bins``,
     ``recalibrate_from``: of the 'calib_curves' action; ``merge_radius``, ``min_lesion_voxels``, ``match_iou``: of the 'lesions' action, which
-    shares ``levels`` and ``connectivity`` with 'components' (``get_actions``)."""
+    shares ``levels`` and ``connectivity`` with 'components'; ``patch``, ``patch_accuracy``: of the 'patches' action (``get_actions``)."""
     actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail, calib_bins,
-                          mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou)
+                          mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou, patch, patch_accuracy)
     for entry in eval_data_list:
         for action in actions:
             action.setup_eval(entry)

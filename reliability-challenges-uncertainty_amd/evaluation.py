@@ -262,7 +262,8 @@ class SubjectBatch:
                     dev[s_].copy_(host[s_], non_blocking=True)
         self._staged = set()
 
-    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26, bands=10, merge_radius=0):
+    def metrics(self, n_bins=10, thresholds=UE_THRESHOLDS, want=('minmax', 'ece', 'ue'), levels=1000, connectivity=26, bands=10, merge_radius=0,
+                patch=(1, 4, 4), accuracy_per_mille=500):
         """-> dict of host arrays over the ``used`` subjects: ``min`` / ``max`` (float32), ``hist`` = (count, sum_conf, sum_pos) of the
         reliability histogram inside the mask, ``counts`` [used, len(thresholds), 8] of the uncertainty-error action on the WHOLE volume
         (bin-eval/eval_uncertainty.py:176-202 uses no mask; tp, tn, fp, fn of it are the confusion matrix of ece_dice) and, with
@@ -277,7 +278,10 @@ class SubjectBatch:
         ``want``, ``calib_levels`` uint64 [used, 3, levels] and ``calib_totals`` uint64 [used, 2, 4]: the calibration level histogram of
         ``calibration_levels`` inside the mask, exactly as ``hist`` uses it, in one launch.  With ``'lesions'`` in ``want``, ``lesions`` = per
         subject the triple of ``lesion_tables`` (entropy of p as the uncertainty, ``connectivity``, ``merge_radius``), all subjects of one shape
-        through each kernel in one call; with ``'components'`` as well the prediction is labelled once for both."""
+        through each kernel in one call; with ``'components'`` as well the prediction is labelled once for both.  With ``'patches'`` in
+        ``want``, ``patch_hist`` uint64 [used, 3, levels]: ``patch_histogram`` of the grid of ``patch`` windows at the accuracy cut
+        ``accuracy_per_mille``, with the entropy of p as the uncertainty, on the whole volume like ``ue_hist``; all subjects of one shape in one
+        call per kernel, the patch tables never leave the device."""
         v = self.used
         out, keep = {}, []
         p, prediction, target = self.p[:v], self.prediction[:v], self.target[:v]
@@ -293,6 +297,8 @@ class SubjectBatch:
         if 'calib_levels' in want:
             calib = _calib_curve_launch(p, target, None if self.mask is None else self.mask[:v], levels)
             keep.extend([('calib_levels', calib[0]), ('calib_totals', calib[1])])
+        if 'patches' in want:
+            keep.append(('patch_hist', self._patches(v, _check_patch(patch), _check_levels(levels), _check_per_mille(accuracy_per_mille))))
         if 'components' in want or 'lesions' in want:
             regions = self._regions(v, connectivity, 'components' in want, _check_merge_radius(merge_radius) if 'lesions' in want else None)
             out.update({key: value for key, value in zip(('components', 'lesions'), regions) if value is not None})
@@ -308,7 +314,7 @@ class SubjectBatch:
             out['counts'] = host['ue'].numpy()
         if 'ue_hist' in host:
             out['ue_hist'] = host['ue_hist'].numpy().view(np.uint64)
-        for key in ('calib_levels', 'calib_totals'):
+        for key in ('calib_levels', 'calib_totals', 'patch_hist'):
             if key in host:
                 out[key] = host[key].numpy().view(np.uint64)
         return out
@@ -338,6 +344,18 @@ class SubjectBatch:
                 for k, slot in enumerate(slots):
                     triples[slot] = found[k]
         return pairs, triples
+
+    def _patches(self, v, patch, levels, accuracy_per_mille):
+        """-> device int64 [v, 3, levels]: the patch histograms of the first ``v`` subjects, one table and one histogram launch per shape."""
+        out = None
+        for slots, dims, p, pr, tg in self._by_shape(v):
+            hist = _patch_hist_on_device(_patch_table_on_device(pr, tg, None, _lib.RCU_CC_UNC_P, p, dims, patch), levels, accuracy_per_mille)
+            if len(slots) == v:
+                return hist
+            if out is None:
+                out = torch.empty((v, 3, levels), device=self.device, dtype=torch.int64)
+            out[torch.as_tensor(slots, device=self.device)] = hist
+        return out
 
     def _boundary(self, v, bands, levels):
         triples = [None] * v
@@ -1056,6 +1074,162 @@ def _boundary_on_device(p, prediction, target, dims, bands, levels):
     tables = table.cpu().numpy().view(BOUNDARY_DTYPE).reshape(v, 2, bands + 1)
     hists = ue_hist.cpu().numpy().view(np.uint64)
     return [(tables[k].copy(), surfaces[k], hists[k].copy()) for k in range(v)]
+
+
+# ------------------------------------------------ patch accuracy vs. patch uncertainty from a patch table on the GPU (EXTENSION)
+# one row per patch of the grid (include/rcu.h, rcu_patch_table)
+PATCH_DTYPE = np.dtype([('n', '<u8'), ('errors', '<u8'), ('foreground', '<u8'), ('sum_q', '<u8')])
+PATCH_DEFAULT = (1, 4, 4)
+_PAVPU_BASE_KEYS = ('n_patches', 'n_inaccurate', 'pavpu_max', 'pavpu_max_threshold', 'p_ac_at_max', 'p_ui_at_max', 'pavpu_mean', 'auroc', 'auprc')
+PAVPU_KEYS = _PAVPU_BASE_KEYS + tuple(k + '_fg' for k in _PAVPU_BASE_KEYS)
+
+
+def _check_patch(patch):
+    patch = tuple(int(v) for v in patch)
+    if len(patch) != 3 or not all(1 <= v <= _lib.RCU_PATCH_MAX_EXTENT for v in patch):
+        raise ValueError('patch must be three extents (depth, height, width) in 1..{}, got {}'.format(_lib.RCU_PATCH_MAX_EXTENT, patch))
+    return patch
+
+
+def _check_per_mille(accuracy_per_mille):
+    if not 0 <= int(accuracy_per_mille) <= 999:
+        raise ValueError('accuracy_per_mille must be in 0..999, got {}'.format(accuracy_per_mille))
+    return int(accuracy_per_mille)
+
+
+def _check_levels(levels):
+    if not 2 <= int(levels) <= _lib.RCU_UNC_HIST_MAX_LEVELS:
+        raise ValueError('levels must be in 2..{}, got {}'.format(_lib.RCU_UNC_HIST_MAX_LEVELS, levels))
+    return int(levels)
+
+
+def _patch_table_on_device(prediction, target, mask, unc_kind, unc, dims, patch):
+    """Device arrays [V, n] -> device int64 [V, patches, 4] holding the uint64 rows; asynchronous on the current stream."""
+    v = target.shape[0]
+    lib = _lib.load()
+    patches = lib.rcu_patch_count(*dims, *patch)
+    table = torch.empty((v, patches, 4), device=target.device, dtype=torch.int64)
+    _lib.check(lib.rcu_patch_table(_lib.ptr(prediction), _lib.ptr(target), _lib.ptr(mask), _lib.ptr(unc), int(unc_kind), *dims, v, *patch,
+                                   _lib.ptr(table), _lib.current_stream()))
+    return table
+
+
+def _patch_hist_on_device(table, levels, accuracy_per_mille):
+    """Device int64 [V, patches, 4] -> device int64 [V, 3, levels] holding the uint64 counts; asynchronous on the current stream."""
+    v, patches = table.shape[0], table.shape[1]
+    hist = torch.empty((v, 3, levels), device=table.device, dtype=torch.int64)
+    _lib.check(_lib.load().rcu_patch_hist(_lib.ptr(table), patches, v, levels, accuracy_per_mille, _lib.ptr(hist), _lib.current_stream()))
+    return hist
+
+
+def _patch_table_of(prediction, target, uncertainty, foreground_probability, patch, mask, n_volumes):
+    dims = _volume_dims(_split_volumes(target.shape, n_volumes))
+    tg = _flat(target, torch.uint8, n_volumes)
+    pr = _flat(prediction, torch.uint8, n_volumes, tg, 'prediction and target')
+    mk = _flat(mask, torch.uint8, n_volumes, tg, 'mask and target')
+    kind, u = _uncertainty_source(uncertainty, foreground_probability, n_volumes, tg, 'target and uncertainty')
+    return _patch_table_on_device(pr, tg, mk, kind, u, dims, patch)
+
+
+def patch_table(prediction, target, uncertainty=None, foreground_probability=None, patch=PATCH_DEFAULT, mask=None, n_volumes=1):
+    """List of ``n_volumes`` structured arrays (PATCH_DTYPE), one row per patch of the volume's grid of non-overlapping windows of ``patch`` =
+    (depth, height, width) voxels, each extent in 1..16, anchored at the origin and numbered in raster order; the windows at the far edges are
+    partial, a 2-D image is a volume of depth 1.  Per patch, over its voxels inside ``mask`` (all of them without one): ``n``, ``errors``
+    (prediction and target disagree), ``foreground`` (prediction or target set) and ``sum_q`` = the sum of q(u) = rint(clamp(u, 0, 1) * 2^24)
+    as in ``component_table`` -- the patch's mean uncertainty is sum_q / (n * 2^24).  Integer sums, one GPU lane per patch: the same rows
+    whatever the batching.  The uncertainty is given as for ``boundary_table``."""
+    table = _patch_table_of(prediction, target, uncertainty, foreground_probability, _check_patch(patch), mask, n_volumes)
+    host = table.cpu().numpy().view(np.uint64)
+    return [host[k].copy().view(PATCH_DTYPE).reshape(-1) for k in range(n_volumes)]
+
+
+def patch_histogram(prediction, target, uncertainty=None, foreground_probability=None, patch=PATCH_DEFAULT, mask=None, n_volumes=1,
+                    levels=UE_LEVELS, accuracy_per_mille=500):
+    """uint64 ``[n_volumes, 3, levels]``: the patches of ``patch_table`` that hold a voxel, counted by cell -- 0: accurate patch that holds
+    foreground, 1: inaccurate patch, 2: accurate patch of pure background; accurate := 1000 (n - errors) > accuracy_per_mille n -- and by the
+    level of their mean uncertainty, level(u) = #{k in 1..levels-1 : u > k / levels} taken in integers on sum_q and n (include/rcu.h,
+    rcu_patch_hist).  Table and histogram are made on the GPU; the table never leaves it."""
+    levels, accuracy_per_mille = _check_levels(levels), _check_per_mille(accuracy_per_mille)
+    table = _patch_table_of(prediction, target, uncertainty, foreground_probability, _check_patch(patch), mask, n_volumes)
+    return _patch_hist_on_device(table, levels, accuracy_per_mille).cpu().numpy().view(np.uint64)
+
+
+def patch_histogram_of_table(table, levels=UE_LEVELS, accuracy_per_mille=500):
+    """``patch_histogram`` from tables that ``patch_table`` returned, in host integer arithmetic: another ``levels`` or accuracy cut needs no
+    second GPU pass.  One structured array -> uint64 ``[3, levels]``; a list of them -> ``[len, 3, levels]``."""
+    levels, accuracy_per_mille = _check_levels(levels), _check_per_mille(accuracy_per_mille)
+    if not isinstance(table, np.ndarray):
+        return np.stack([patch_histogram_of_table(t, levels, accuracy_per_mille) for t in table]) if len(table) else np.zeros((0, 3, levels), np.uint64)
+    u64 = np.uint64
+    n, errors, foreground, sum_q = (np.ascontiguousarray(table[k]).reshape(-1).astype(u64) for k in PATCH_DTYPE.names)
+    used = n != 0
+    n, errors, foreground, sum_q = n[used], errors[used], foreground[used], sum_q[used]
+    accurate = u64(1000) * (n - errors) > u64(accuracy_per_mille) * n
+    cell = np.where(accurate, np.where(foreground != 0, 0, 2), 1)
+    # level = #{k in 1..B-1 : sum_q B > k n 2^24}: the products stay below 2^49
+    level = np.where(sum_q != 0, np.minimum(u64(levels - 1), (np.maximum(sum_q, u64(1)) * u64(levels) - u64(1)) // (n << u64(24))), u64(0))
+    return np.bincount(cell * levels + level.astype(np.int64), minlength=3 * levels).astype(np.uint64).reshape(3, levels)
+
+
+def _pavpu_curve(accurate, inaccurate):
+    """Per level k of the accurate and the inaccurate patches per level (Python integers): (pavpu, p_ac, p_ui) at the threshold k / B, where a
+    patch is uncertain iff its level is >= k -- suffix sums from the top; entry 0 (no threshold) is None."""
+    levels, n_acc, n_inacc = len(accurate), sum(accurate), sum(inaccurate)
+    n, nan = n_acc + n_inacc, float('nan')
+    curve, n_au, n_iu = [None] * levels, 0, 0
+    for k in range(levels - 1, 0, -1):
+        n_au, n_iu = n_au + accurate[k], n_iu + inaccurate[k]
+        n_ac, n_ic = n_acc - n_au, n_inacc - n_iu
+        curve[k] = ((n_ac + n_iu) / n if n else nan, n_ac / (n_ac + n_ic) if n_ac + n_ic else nan, n_iu / n_inacc if n_inacc else nan)
+    return curve
+
+
+def _pavpu_of(accurate, inaccurate):
+    """The keys ``_PAVPU_BASE_KEYS`` from the accurate and the inaccurate patches per level (Python integers)."""
+    levels = len(accurate)
+    out = {'n_patches': sum(accurate) + sum(inaccurate), 'n_inaccurate': sum(inaccurate)}
+    if out['n_patches'] == 0:
+        out.update({k: float('nan') for k in _PAVPU_BASE_KEYS[2:]})
+        return out
+    curve = _pavpu_curve(accurate, inaccurate)
+    best = max(range(1, levels), key=lambda k: (curve[k][0], -k))
+    out['pavpu_max'], out['p_ac_at_max'], out['p_ui_at_max'] = curve[best]
+    out['pavpu_max_threshold'] = best / levels
+    out['pavpu_mean'] = math.fsum(c[0] for c in curve[1:]) / (levels - 1)
+    out['auroc'], out['auprc'] = _rank_metrics(zip(inaccurate, accurate))
+    return {k: out[k] for k in _PAVPU_BASE_KEYS}
+
+
+def pavpu_curve(hist):
+    """ONE patch histogram ``[3, B]`` -> the list of (pavpu, p_ac, p_ui) over all patches per level k = 0..B-1 at the threshold k / B (see
+    ``pavpu_metrics``); entry 0, where there is no threshold, is None."""
+    h = _one_patch_histogram(hist)
+    return _pavpu_curve([a + b for a, b in zip(h[0], h[2])], h[1])
+
+
+def _one_patch_histogram(hist):
+    h = np.asarray(hist)
+    if h.ndim != 2 or h.shape[0] != 3 or h.shape[1] < 2:
+        raise ValueError('expected one patch histogram of shape [3, levels >= 2], got {}'.format(h.shape))
+    return [[int(v) for v in row] for row in h]
+
+
+def pavpu_metrics(hist):
+    """Patch accuracy vs. patch uncertainty (Mukhoti & Gal, 2018) of ONE patch histogram ``[3, B]`` (cells accurate with foreground, inaccurate,
+    accurate pure background; a subject's, or the sum of several subjects': histograms add) -> dict with the keys ``PAVPU_KEYS``.  Host
+    arithmetic on Python integers, every ratio rounded once.  A patch is uncertain at the threshold k / B (k = 1..B-1) iff its level is >= k;
+    with n_ac, n_au, n_ic, n_iu the accurate / inaccurate patches that are certain / uncertain there and N their sum:
+      p_ac = n_ac / (n_ac + n_ic)   p(accurate | certain)        p_ui = n_iu / (n_ic + n_iu)   p(uncertain | inaccurate)
+      pavpu = (n_ac + n_iu) / N
+      pavpu_max, pavpu_max_threshold   the maximum of pavpu over the thresholds and the smallest threshold that attains it; p_ac_at_max,
+                                       p_ui_at_max there;  pavpu_mean: the mean over the B - 1 thresholds (math.fsum)
+      auroc, auprc                     of detecting the inaccurate patches by their level (``_rank_metrics``: ties counted half)
+    and every key again with the suffix ``_fg`` over the patches that hold foreground only (cells 0 and 1): a volume that is mostly
+    background is mostly patches that are trivially accurate and certain.  Undefined values are ``float('nan')``."""
+    h = _one_patch_histogram(hist)
+    out = _pavpu_of([a + b for a, b in zip(h[0], h[2])], h[1])
+    out.update({k + '_fg': v for k, v in _pavpu_of(h[0], h[1]).items()})
+    return out
 
 
 # ------------------------------------------------ lesion-wise matching from the joint table of two labellings on the GPU (EXTENSION)

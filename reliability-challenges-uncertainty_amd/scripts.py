@@ -947,7 +947,8 @@ for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, te
 
 def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, actions=('minmax', 'ece_dice', 'calib', 'bnf_ue'),
                      expected_subjects=None, fused=True, batch_subjects=8, timing=None, levels=1000, connectivity=26, bands=10, dice_fail=0.8,
-                     calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5):
+                     calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5, patch=(1, 4, 4),
+                     patch_accuracy=500):
     """``run_dirs``: run id (baseline, baseline_mc, ..., aleatoric) -> prediction directory.  BraTS evaluates
     inside the T2 brain mask (``ece_details='foreground'``), ISIC on all pixels (eval_uncertainty.py:19-26).
     ``ground_truth_dir``: the BraTS tree of ``<subject>/<subject>_{t2,seg,...}.nii.gz`` or, for ISIC, the dataset
@@ -961,8 +962,9 @@ def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, action
         gts = evalrun.collect_isic_ground_truth(ground_truth_dir)
         details = ''
     entries = [evalrun.get_eval_data(run_id, path, gts, expected_subjects) for run_id, path in run_dirs.items()]
-    # (levels: of the extension actions 'ue_curves' and 'components', connectivity: of 'components'; bands: of 'boundary'; dice_fail: of 'agreement'; calib_bins / mass_bins / recalibrate_from: of 'calib_curves', whose level histogram has `levels` levels too; merge_radius / min_lesion_voxels / match_iou: of 'lesions', which shares levels and connectivity with 'components'; fused / batch_subjects / timing: rcu_amd.evalrun.evaluate_runs -- one upload per subject shared by all actions, subjects batched per launch)
+    # (levels: of the extension actions 'ue_curves' and 'components', connectivity: of 'components'; bands: of 'boundary'; dice_fail: of 'agreement'; calib_bins / mass_bins / recalibrate_from: of 'calib_curves', whose level histogram has `levels` levels too; merge_radius / min_lesion_voxels / match_iou: of 'lesions', which shares levels and connectivity with 'components'; patch / patch_accuracy: of 'patches', whose histogram has `levels` levels; fused / batch_subjects / timing: rcu_amd.evalrun.evaluate_runs -- one upload per subject shared by all actions, subjects batched per launch)
     evalrun.evaluate_runs(entries, list(actions), base_dir, details, fused=fused, batch_subjects=batch_subjects, timing=timing, levels=levels,
                           connectivity=connectivity, bands=bands, dice_fail=dice_fail, calib_bins=calib_bins, mass_bins=mass_bins,
-                          recalibrate_from=recalibrate_from, merge_radius=merge_radius, min_lesion_voxels=min_lesion_voxels, match_iou=match_iou)
+                          recalibrate_from=recalibrate_from, merge_radius=merge_radius, min_lesion_voxels=min_lesion_voxels, match_iou=match_iou,
+                          patch=patch, patch_accuracy=patch_accuracy)
     return entries
