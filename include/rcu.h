@@ -93,7 +93,10 @@ typedef struct rcu_unet_options {
                                  a padded extent -- the padding holds zeros no kernel writes, which is the conv's own zero padding -- and runs on the Winograd
                                  kernels (the reference's BraTS slices are 240 x 240: levels 240, 120, 60, 30, 15; ISIC's 192 x 256 ends in a 12 x 16 level);
                                  0: real extents only, such levels take the direct kernels (the plans of rounds 1-5; A/B measurements) */
-    int32_t reserved[1];      /* must be 0 */
+    int32_t upconv_winograd4; /* the 25-product F(4x4,3x3) up-convolutions (csrc/rcu_wino4_up.hip; the slot was reserved[0] -- a caller that zeroes it keeps
+                                 the sub-pixel F(2x2,2x2) kernels).  0: never; 1 (default): per layer where the plan's work items fill the chip and the
+                                 kernel measured faster at that plan size (pick_config); 2: wherever its tiles fit, whatever the fill (parity tests on
+                                 small batches).  Padded levels (pad_levels) keep the sub-pixel kernels under every value */
 } rcu_unet_options;
 /* fills *opts with the defaults above */
 void rcu_unet_default_options(rcu_unet_options* opts);

@@ -54,7 +54,7 @@ class UnetDesc(Structure):
 
 class UnetOptions(Structure):
     """rcu_unet_options (include/rcu.h): the planner's kernel-family / layout choices; defaults = the shipped path."""
-    _fields_ = [(n, c_int32) for n in ('conv_winograd', 'conv_winograd4', 'conv_first', 'act_layout', 'fuse_head', 'head_winograd4', 'pad_levels')] + [('reserved', c_int32 * 1)]
+    _fields_ = [(n, c_int32) for n in ('conv_winograd', 'conv_winograd4', 'conv_first', 'act_layout', 'fuse_head', 'head_winograd4', 'pad_levels', 'upconv_winograd4')]
 
 
 class LayerInfo(Structure):

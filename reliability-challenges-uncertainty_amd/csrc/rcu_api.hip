@@ -143,6 +143,26 @@ static size_t conv_tile_floats(const ConvConfigInfo& ci)
 
 static bool is_head_unit(const ConvLayer& L) { return L.name.rfind("conv_cls.0", 0) == 0; }
 
+// The default rule of rcu_unet_options.upconv_winograd4 = 1, per layer: the 25-product up-convolution (rcu_wino4_up.hip) where its work items -- one
+// per (slice group, low-resolution tile, 32-cout tile), one workgroup per CU -- fill the chip as far as the kernel has been measured against the
+// sub-pixel one.  Measured per layer in one process, old - new - old (tools/upconv4_gate.py, profiles/upconv4_layer_gate.txt), on the four
+// up-convolutions of the BraTS shape at 640 / 480 / 320 / 160 samples per launch: 22-28 % faster in all sixteen cases, the spread between the
+// two legs of the old kernel below 1.5 %.  The smallest fill among them is 480 items (1.9 rounds of 256 workgroups: 512 -> 256 channels into
+// 24x16 at 160 samples, 0.309-0.313 against 0.232 ms); below it nothing is measured, and a plan of a few slices keeps the sub-pixel kernels.
+// The second condition is the plan size: only plans sized for the pass-group launches of the predict steps -- 480 samples of 192x128 and up, the
+// sizes at which the 12x8 rule of pick_config changes kernels too -- take the kernel.  A 160-sample plan keeps the bits of an 8-sample one
+// (tests/test_gpu_fullsize.py compares them), although the kernel is faster there as well: upconv_winograd4 = 2 takes it.
+constexpr long kUpconv4MinItems = 480;
+constexpr long long kUpconv4MinPlanPixels = 480LL * 192 * 128;   // samples x pixels of the network's input level
+static bool upconv4_wins(int cfg, const ConvLayer& L, int n_slices)
+{
+    const ConvConfigInfo& ci = conv_config_info(cfg);
+    const long items = (long)((n_slices + ci.TS - 1) / ci.TS) * (L.gh / ci.TH) * (L.gw / ci.TW) * (L.coutp / ci.BN);
+    const int l = L.level - 1;   // the level of the output (L.level: the low-resolution level the tiles walk)
+    const long long plan_pixels = (long long)n_slices * ((long long)L.H << l) * ((long long)L.W << l);
+    return items >= kUpconv4MinItems && plan_pixels >= kUpconv4MinPlanPixels;
+}
+
 // Which kernel runs a layer.  (gh, gw) = L.gh x L.gw is the grid the tiles walk: the ALLOCATED extent of the layer's level (an up-convolution's
 // low-resolution level), which is the real extent unless the level is padded (choose_level_extents); oh x ow the allocated extent of its output tensor.
 static int pick_config(const ConvLayer& L, int n_slices, const rcu_unet_options& opt, int oh, int ow)
@@ -162,6 +182,22 @@ static int pick_config(const ConvLayer& L, int n_slices, const rcu_unet_options&
     const bool center_pad = L.upsample && (2 * (L.H / 2) != L.H || 2 * (L.W / 2) != L.W);   // unet.py:110-116: direct kernel only
     if (L.upsample && !center_pad && wino_on && L.c1p % 32 == 0 && L.c2p == 0 && max_bytes < ((size_t)1 << 31)) {
         const int lh = gh, lw = gw;
+        // F(4x4,3x3) on the up-sampled grid without its vanishing point (rcu_wino4_up.hip): 25 instead of 36 multiplications per 16 output pixels.
+        // Whole tiles of unpadded levels only -- the kernel has no ConvArgs::part form, so a padded level on either side keeps the sub-pixel
+        // kernels below under every option value -- and every byte offset its lanes form, a tile's slices beyond the batch included, below 2^32.
+        // rcu_unet_options.upconv_winograd4: 0 never, 2 wherever the geometry fits (parity tests on small batches), 1 (default) where the
+        // plan's work items fill the chip and tools/upconv4_gate.py measured the kernel faster than the sub-pixel one at that plan size:
+        // see upconv4_wins.
+        const int u4_mode = opt.upconv_winograd4;
+        const bool u4_fits = u4_mode != 0 && 2 * lh == L.H && 2 * lw == L.W && oh == L.H && ow == L.W &&
+                             (size_t)(n_slices + 8) * std::max(in_px * (size_t)L.c1p, (size_t)oh * ow * (size_t)L.coutp) * 4 < ((size_t)1 << 32);
+        if (u4_fits) {
+            const int cfg4 = (lh % 16 == 0 && lw % 16 == 0) ? CONV_CFG_UPW4_T32x32_N32
+                             : (lh % 8 == 0 && lw % 16 == 0) ? CONV_CFG_UPW4_S2T16x32_N32
+                             : (lh % 4 == 0 && lw == 8)      ? CONV_CFG_UPW4_S8T8x16_N32
+                                                             : -1;
+            if (cfg4 >= 0 && (u4_mode == 2 || upconv4_wins(cfg4, L, n_slices))) return cfg4;
+        }
         if (L.coutp == 32 && lh % 16 == 0 && lw % 32 == 0) return CONV_CFG_UPW_T16x32_N32;
         if (L.coutp > 32 && lh % 16 == 0 && lw % 16 == 0) return CONV_CFG_UPW_T16x16_N64;
         if (L.coutp > 32 && lh % 8 == 0 && lw % 16 == 0) return CONV_CFG_UPW_S2T8x16_N64;
@@ -280,7 +316,7 @@ static void assign_layouts(rcu_unet* h);
 static bool cfg_handles_padding(int cfg)
 {
     return cfg == CONV_CFG_FIRST_T8x32 || (cfg >= CONV_CFG_WINO_T16x16_N64 && cfg <= CONV_CFG_UPW_S8T4x8_N64) ||
-           (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_END);
+           (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_UPW4_T32x32_N32);   // (rcu_wino4_up.hip: never chosen on a padded level, pick_config)
 }
 
 // Builds layers and tensors for the level extents in h->level_ext (build_plan: the real extents; choose_level_extents tries padded ones).
@@ -415,6 +451,7 @@ static double plan_cost(const rcu_unet* h)
         if (L.cfg == CONV_CFG_FIRST_T8x32) { mults = 9.0; eff = 0.25; }                 // a write stream, not a matrix kernel
         else if (ci.WINO == 3) { mults = L.cfg == CONV_CFG_WINO4_S8T12x8_N32 ? 3.0 : 2.25; eff = (L.c1p + L.c2p) <= 32 ? 0.45 : 0.58; }
         else if (ci.WINO == 2) { mults = 9.0; eff = 0.72; }                              // four classes x 9 / 4 per low-resolution pixel
+        else if (ci.WINO == 4) { mults = 6.25; eff = 0.70; }                             // 25 per 4x4 output tile = 2x2 low-resolution pixels; measured 0.63-0.76
         else if (ci.WINO == 1) { mults = 4.0; eff = 0.62; }
         else if (L.upsample) { mults = 16.0; eff = 0.72; }                               // four classes x 2x2 taps per low-resolution pixel
         else { mults = 9.0; eff = 0.75; }
@@ -489,7 +526,7 @@ static int build_plan(rcu_unet* h) { return choose_level_extents(h); }
 // cat-free decoder unit share one layout.  rcu_unet_options.act_layout = 1 keeps everything channels-last (A/B tests).
 static bool cfg_reads_blocked(int cfg)
 {
-    return (cfg >= CONV_CFG_WINO_T16x16_N64 && cfg <= CONV_CFG_UPW_S8T4x8_N64) || (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_END);
+    return (cfg >= CONV_CFG_WINO_T16x16_N64 && cfg <= CONV_CFG_UPW_S8T4x8_N64) || (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_END);   // rcu_wino4_up.hip too
 }
 static bool cfg_writes_blocked(int cfg) { return cfg_reads_blocked(cfg) || cfg == CONV_CFG_FIRST_T8x32; }
 
@@ -539,6 +576,7 @@ extern "C" void rcu_unet_default_options(rcu_unet_options* opts)
     opts->fuse_head = 1;
     opts->head_winograd4 = 1;
     opts->pad_levels = 1;
+    opts->upconv_winograd4 = 1;
 }
 
 // desc / options checks + the plan (layers, tensors, level extents); no device memory
@@ -559,7 +597,8 @@ static int make_plan(const rcu_unet_desc* desc, const rcu_unet_options* opts, co
     if (opts) {
         o = *opts;
         if ((o.conv_winograd | 1) != 1 || (o.conv_winograd4 < 0 || o.conv_winograd4 > 3) ||
-            (o.conv_first | 1) != 1 || (o.act_layout | 1) != 1 || (o.fuse_head | 1) != 1 || (o.head_winograd4 | 1) != 1 || (o.pad_levels | 1) != 1 || o.reserved[0])
+            (o.conv_first | 1) != 1 || (o.act_layout | 1) != 1 || (o.fuse_head | 1) != 1 || (o.head_winograd4 | 1) != 1 || (o.pad_levels | 1) != 1 ||
+            (o.upconv_winograd4 < 0 || o.upconv_winograd4 > 2))
             return fail(RCU_ERR_INVALID, "rcu_unet_create_with: bad rcu_unet_options value");
     }
     rcu_unet* h = new rcu_unet();
@@ -806,6 +845,34 @@ static int fold_conv(rcu_unet* h, const ConvLayer& L, const std::string& conv, c
         }
         return RCU_OK;
     }
+    if (ci.WINO == 4) {
+        // F(4x4,3x3) of the up-sampled image (rcu_wino4_up.hip): U = G g G^T as below, without row and column 2 (the point -1, where the up-sampled
+        // input vanishes); rows and columns 3 (the point +2) carry the factor -3 by which the kernel's shared transformed value b - c differs from
+        // B^T's row 3 -- both directions for the corner entry: 9.  Computed in double, rounded once; packed per Cin chunk and cout tile as
+        // [position p = 5 ki + kj][channel pair q][cout][2], k = 0..4 the rows 0, 1, 3, 4, 5.
+        static const double G4[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
+        static const int keep[5] = {0, 1, 3, 4, 5};
+        for (int co = 0; co < L.cout; ++co) {
+            const int cop = co0 + co;
+            const int ntile = cop / BN, nn = cop % BN;
+            for (int ci_ = 0; ci_ < cin; ++ci_) {
+                const int chunk = ci_ / KC, kq = ci_ % KC;
+                const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
+                const size_t tile0 = ((size_t)chunk * L.NT + ntile) * tile_floats;
+                for (int ki = 0; ki < 5; ++ki)
+                    for (int kj = 0; kj < 5; ++kj) {
+                        double u = 0.0;
+                        for (int r = 0; r < 3; ++r)
+                            for (int c = 0; c < 3; ++c) u += G4[keep[ki]][r] * (double)w9[r * 3 + c] * G4[keep[kj]][c];
+                        u *= (keep[ki] == 3 ? -3.0 : 1.0) * (keep[kj] == 3 ? -3.0 : 1.0);
+                        const int p = 5 * ki + kj;
+                        wpack[tile0 + (((size_t)p * 4 + (kq >> 1)) * BN + nn) * 2 + (kq & 1)] = (float)u;
+                    }
+            }
+        }
+        return RCU_OK;
+    }
     if (ci.WINO == 3) {
         // F(4x4,3x3): U = G g G^T (6x6) per (cout, cin) with the Lavin-Gray G for the points 0, +-1, +-2, inf; packed per Cin chunk and
         // cout tile as [position p = 6 i + j][channel pair q][cout][2] (rcu_wino4.hip).  Computed in double, rounded once.
@@ -894,7 +961,7 @@ extern "C" int rcu_unet_finalize_weights(rcu_unet* h)
     for (ConvLayer& L : h->layers) {
         const ConvConfigInfo& ci = conv_config_info(L.cfg);
         const int nchunks = (L.c1p + L.c2p) / ci.KC;
-        L.wpack_floats = (size_t)nchunks * L.NT * (ci.WINO == 2 ? 2 : L.upsample ? 4 : 1) * conv_tile_floats(ci);
+        L.wpack_floats = (size_t)nchunks * L.NT * (ci.WINO == 2 ? 2 : ci.WINO == 4 ? 1 : L.upsample ? 4 : 1) * conv_tile_floats(ci);
         std::vector<float> wpack(L.wpack_floats, 0.f);
         const int cpad = L.NT * ci.BN;
         std::vector<float> alpha(cpad, 0.f), betab(cpad, 0.f), beta(cpad, 0.f);
@@ -998,7 +1065,7 @@ static int run_layer(rcu_unet* h, const ConvLayer& L, int n, const float* masks,
     a.tiles_x = (gw + ci.TW - 1) / ci.TW;
     a.slice_groups = (n + ci.TS - 1) / ci.TS;
     a.NT = L.NT;
-    a.NTW_total = L.NT * (ci.WINO == 2 ? 2 : L.upsample ? 4 : 1);
+    a.NTW_total = L.NT * (ci.WINO == 2 ? 2 : ci.WINO == 4 ? 1 : L.upsample ? 4 : 1);
     {
         const unsigned long long items = (unsigned long long)a.NTW_total * a.tiles_x * a.tiles_y * a.slice_groups;
         auto magic = [&](int d) -> uint32_t {
@@ -1426,9 +1493,10 @@ extern "C" int rcu_unet_layer_info(const rcu_unet* h, int layer, rcu_layer_info*
         const double ncols = (double)L.NT * ci.BN;
         // Winograd: 16 multiplications per 2x2 output tile instead of 9 per pixel
         // and 9 per 2x2 low-resolution tile and parity class (= 9 per low-resolution pixel) for the up-convolutions
-        // F(4x4,3x3): 36 per 4x4 output tile
+        // F(4x4,3x3): 36 per 4x4 output tile; 25 for the up-convolutions on the up-sampled grid
         out->mfma_flops_per_slice = ci.WINO == 2 ? 2.0 * L.c1p * ncols * 9.0 * (px / 4.0)
                                     : ci.WINO == 3 ? 2.0 * (L.c1p + L.c2p) * ncols * 36.0 * (px / 16.0)
+                                    : ci.WINO == 4 ? 2.0 * L.c1p * ncols * 25.0 * (px / 16.0)   // px: output pixels; canonical x 25 / 144
                                                    : 2.0 * (L.c1p + L.c2p) * ncols * (ci.WINO ? 4.0 : (double)ci.TAPS) * px;
         if (L.cfg == CONV_CFG_WINO4_S8T12x8_N32) out->mfma_flops_per_slice *= 4.0 / 3.0;   // 8 tile slots per slice execute, 6 hold tiles
         if (L.cfg == CONV_CFG_FIRST_T8x32)   // K = 4 channels per tap unless more than four are real

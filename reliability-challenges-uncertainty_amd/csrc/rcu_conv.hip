@@ -592,6 +592,7 @@ hipError_t set_max_dynamic_lds(const void* kernel, int bytes)
 
 const ConvConfigInfo& conv_config_info(int cfg)
 {
+    if (cfg >= CONV_CFG_UPW4_T32x32_N32) return wino4_up_config_info(cfg);
     if (cfg >= CONV_CFG_WINO4_T32x32_N32) return wino4_config_info(cfg);
     if (cfg == CONV_CFG_FIRST_T8x32) return first_config_info();
     if (cfg >= CONV_CFG_UPW_T16x16_N64) return wino_up_config_info(cfg);
@@ -628,6 +629,7 @@ static hipError_t launch_cfg(const ConvArgs& a, hipStream_t stream)
 
 hipError_t launch_conv3x3(int cfg, const ConvArgs& a, hipStream_t stream)
 {
+    if (cfg >= CONV_CFG_UPW4_T32x32_N32) return launch_upconv_wino4(cfg, a, stream);
     if (cfg >= CONV_CFG_WINO4_T32x32_N32) return launch_conv_wino4(cfg, a, stream);
     if (cfg == CONV_CFG_FIRST_T8x32) return launch_conv_first(a, stream);
     if (cfg >= CONV_CFG_UPW_T16x16_N64) return launch_upconv_wino(cfg, a, stream);

@@ -132,6 +132,11 @@ enum ConvConfig {
     CONV_CFG_WINO4_S8T12x8_N32,                  // 12x8 pixels of eight consecutive slices (6 tiles per slice in the 8 tile slots of the S8 block), images 8 wide
     CONV_CFG_WINO4_T32x32_N32_HEAD,              // T32x32_N32 with the 1x1 head + softmax + statistics in the epilogue (run-time choice of forward_impl, never a plan entry)
     CONV_CFG_WINO4_S4T8x32_N32,                  // 8x32 pixels of four consecutive slices, images 32 pixels wide (round 6: ISIC's 24x32 level without padding)
+    // Winograd F(4x4,3x3) up-convolutions on the up-sampled grid without the vanishing point (rcu_wino4_up.hip): 25 positions, one wave per SIMD
+    // (200 accumulator registers), 32 couts; the names give the OUTPUT tile.  Unpadded levels only (no ConvArgs::part)
+    CONV_CFG_UPW4_T32x32_N32,                    // 32x32 output pixels of one slice
+    CONV_CFG_UPW4_S2T16x32_N32,                  // 16x32 output pixels of two consecutive slices
+    CONV_CFG_UPW4_S8T8x16_N32,                   // 8x16 output pixels of eight consecutive slices, output images 16 pixels wide
     CONV_CFG_END
 };
 
@@ -141,18 +146,20 @@ struct ConvConfigInfo {
     int KCP;   // floats per [tap][channel] row of a packed weight tile (KC, or KC + 4 in the padded layout)
     int SWZ;   // 1: the two 16-byte units of a row are swapped for output channels 16..31 (mod 32), see ConvTile
     int WINO;  // 1: Winograd F(2x2,3x3) kernel, TAPS = 16 positions; 2: F(2x2,2x2) up-conv, TAPS = 18 (two classes);
-               // 3: F(4x4,3x3), TAPS = 36 positions; packed tile = [p][channel pair][cout][2] (rcu_wino.hip, rcu_wino_up.hip,
-               // rcu_wino4.hip)
+               // 3: F(4x4,3x3), TAPS = 36 positions; 4: F(4x4,3x3) up-conv, TAPS = 25 positions, TH x TW = the low-resolution tile;
+               // packed tile = [p][channel pair][cout][2] (rcu_wino.hip, rcu_wino_up.hip, rcu_wino4.hip, rcu_wino4_up.hip)
 };
 const ConvConfigInfo& conv_config_info(int cfg);
 const ConvConfigInfo& wino_config_info(int cfg);
 const ConvConfigInfo& wino_up_config_info(int cfg);
 const ConvConfigInfo& wino4_config_info(int cfg);
+const ConvConfigInfo& wino4_up_config_info(int cfg);
 const ConvConfigInfo& first_config_info();
 hipError_t launch_conv3x3(int cfg, const ConvArgs& a, hipStream_t stream);
 hipError_t launch_conv_wino(int cfg, const ConvArgs& a, hipStream_t stream);
 hipError_t launch_upconv_wino(int cfg, const ConvArgs& a, hipStream_t stream);
 hipError_t launch_conv_wino4(int cfg, const ConvArgs& a, hipStream_t stream);
+hipError_t launch_upconv_wino4(int cfg, const ConvArgs& a, hipStream_t stream);
 hipError_t launch_conv_first(const ConvArgs& a, hipStream_t stream);
 
 // Loads of data a kernel reads exactly once (activation / logits / probability / label streams of the per-voxel kernels): non-temporal, so that the

@@ -61,7 +61,7 @@ class UNet(nn.Module):
     MAX_HANDLES = 6          # cached (height, width[, lane]) plans incl. their workspaces
     # rcu_unet_options (include/rcu.h): what the planner may choose.  The defaults are the shipped path; ``plan_options`` of an instance
     # overrides them for A/B measurements and for the parity tests that compare kernel families on the same input.
-    PLAN_DEFAULTS = dict(conv_winograd=1, conv_winograd4=1, conv_first=1, act_layout=0, head_winograd4=1, pad_levels=1)
+    PLAN_DEFAULTS = dict(conv_winograd=1, conv_winograd4=1, conv_first=1, act_layout=0, head_winograd4=1, pad_levels=1, upconv_winograd4=1)
     _generations = itertools.count(1)      # every plan ever created gets the next number: a borrower's plan is valid for ONE generation of its donor's
 
     def __init__(self, nb_classes, in_channels, depth=DEFAULT_DEPTH, start_filters=DEFAULT_START_FILTERS,

@@ -5,6 +5,8 @@ csrc/rcu_wino.hip computes)?  Decides whether an F(4x4,3x3) kernel can hold the 
 probabilities / entropy <= 1e-4 against the oracle).
 
     python tools/wino43_numerics.py [min_cin for F(4x4,3x3), default 128] [slices, default 2]
+    python tools/wino43_numerics.py upconv4      the up-convolutions in the 25-product F(4x4,3x3) form (csrc/rcu_wino4_up.hip) inside the
+                                                 network of today's plan, on the weights and inputs of the fixtures G1, G11 and G18
 
 Each Winograd stage is evaluated in float32 with the operation order a kernel would use (transform in registers, channel
 contraction as a float32 sum, output transform, then bias/BN); the contraction's summation order differs from an MFMA chain but
@@ -54,9 +56,37 @@ def wino_conv(x, w, bias, m, BT, G, AT):
     return y + bias[None, :, None, None]
 
 
-def forward(state, x, mode, min_cin, dtype=torch.float32):
-    """mode: 'direct' | 'f23' | 'f43' (F(4,3) for units with cin >= min_cin, F(2,3) elsewhere where cin >= 32)."""
-    plan, _ = uo.unet_plan(**PARAMS)
+# the 25-product up-convolution: the positions 0, 1, 3, 4, 5 of a direction survive on an up-sampled image (the point -1 vanishes), they read 4
+# transformed values of the raw low-resolution quadruple (a, b, c, d) -- rows 0, 1, 4, 5 of B4T applied to (a, b, b, c, c, d) -- and row 3's
+# factor -3 sits in the weights
+KEEP = [0, 1, 3, 4, 5]
+VALUE_OF = [0, 1, 2, 2, 3]
+T4 = np.array([[4, -5, 1, 0], [0, -8, 2, 0], [0, 1, -1, 0], [0, 4, -5, 1]], dtype=np.float64)
+SCALE3 = np.array([1, 1, -3, 1, 1], dtype=np.float64)
+
+
+def upconv25(x, w, bias):
+    """float32 nearest x2 -> conv3x3 in the 25-product form.  x [N,C,h,w] float32 (low resolution), h, w even; low-resolution zero padding only."""
+    n, c, h, wd = x.shape
+    U = np.einsum('ir,ocrs,js->ijoc', G4, w.double().numpy(), G4)[KEEP][:, KEEP] * SCALE3[:, None, None, None] * SCALE3[None, :, None, None]
+    U = torch.as_tensor(U).float()                      # rounded once, as on the host
+    t = F.pad(x, (1, 1, 1, 1)).unfold(2, 4, 2).unfold(3, 4, 2)       # raw 4x4 patches, one per 4x4 output tile: [N, C, th, tw, 4, 4]
+    tt = torch.as_tensor(T4).float()
+    v = torch.einsum('ir,nctwrs->nctwis', tt, t)
+    v = torch.einsum('js,nctwis->nctwij', tt, v)        # 16 values
+    v = v[..., VALUE_OF, :][..., VALUE_OF]               # 25 positions
+    mm = torch.einsum('ijoc,nctwij->notwij', U, v)
+    at = torch.as_tensor(A4T[:, KEEP]).float()
+    y = torch.einsum('pi,notwij->notwpj', at, mm)
+    y = torch.einsum('qj,notwpj->notwpq', at, y)
+    y = y.permute(0, 1, 2, 4, 3, 5).reshape(n, w.shape[0], 2 * h, 2 * wd)
+    return y + bias[None, :, None, None]
+
+
+def forward(state, x, mode, min_cin, dtype=torch.float32, params=None, up25=False):
+    """mode: 'direct' | 'f23' | 'f43' (F(4,3) for units with cin >= min_cin, F(2,3) elsewhere where cin >= 32); up25: the up-convolutions in
+    the 25-product form where the low-resolution image has even extents."""
+    plan, _ = uo.unet_plan(**(params or PARAMS))
     st = {k: torch.as_tensor(v).to(dtype) if torch.as_tensor(v).is_floating_point() else torch.as_tensor(v) for k, v in state.items()}
     x = x.to(dtype)
     skips = []
@@ -70,8 +100,10 @@ def forward(state, x, mode, min_cin, dtype=torch.float32):
                 x = F.conv2d(x, w, b, padding=1)
             elif mode == 'f43' and cin >= min_cin and x.shape[-1] % 4 == 0 and x.shape[-2] % 4 == 0:
                 x = wino_conv(x, w, b, 4, B4T, G4, A4T)
-            else:
+            elif x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0:
                 x = wino_conv(x, w, b, 2, B2T, G2, A2T)
+            else:
+                x = F.conv2d(x, w, b, padding=1)
             x = F.batch_norm(x, st[k + '.bn.running_mean'], st[k + '.bn.running_var'], st[k + '.bn.weight'], st[k + '.bn.bias'],
                              False, 0.0, uo.BN_EPS)
             x = F.relu(x)
@@ -80,14 +112,50 @@ def forward(state, x, mode, min_cin, dtype=torch.float32):
             x = F.max_pool2d(x, 2)
         elif kind == 'up':
             skip = skips.pop()
-            up = F.interpolate(x, scale_factor=2, mode='nearest')
-            up = F.conv2d(up, st[op['key'] + '.weight'], st[op['key'] + '.bias'], padding=1)
+            if up25 and dtype != torch.float64 and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0:
+                up = upconv25(x, st[op['key'] + '.weight'], st[op['key'] + '.bias'])
+            else:
+                up = F.interpolate(x, scale_factor=2, mode='nearest')
+                up = F.conv2d(up, st[op['key'] + '.weight'], st[op['key'] + '.bias'], padding=1)
             x = torch.cat((up, skip), 1)
         elif kind == 'head':
             return F.conv2d(x, st[op['key'] + '.weight'], st[op['key'] + '.bias'])
 
 
+def upconv4_gate():
+    """Gate A of the 25-product up-convolutions: logit error against the float64 network no worse than 1.5 x today's plan (F(4x4,3x3) conv units,
+    up-convolutions as they are), and the G18 probability error below 3e-5."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from conftest import golden_params, golden_state, load_golden
+    ok = True
+    for name in ('g1_unet_eval', 'g11_fullsize_digest', 'g18_unet_stress'):
+        g = load_golden(name)
+        p = golden_params(g)
+        if name == 'g1_unet_eval':
+            st, x = golden_state(g), torch.as_tensor(g['x_a'])
+        else:
+            st = uo.reference_init_state(int(g['seed']), bn_seed=int(g['seed']) + 1000, **p)
+            if name == 'g18_unet_stress':
+                st = uo.stress_state(st, float(g['bn_gain']), float(g['head_gain']))
+            x = torch.as_tensor(g['x'])
+        st = {k: torch.as_tensor(v) for k, v in st.items()}
+        ref = forward(st, x, 'direct', 0, torch.float64, params=p)
+        pref = torch.softmax(ref, 1)
+        row = {}
+        for tag, up25 in (('today', False), ('upconv4', True)):
+            y = forward(st, x, 'f43', 32, params=p, up25=up25).double()
+            row[tag] = (float((y - ref).abs().max()), float((torch.softmax(y.float(), 1).double() - pref).abs().max()))
+        ratio = row['upconv4'][0] / row['today'][0]
+        print('{:<20} x {}  |logit| max {:.3f}   today: max|dlogit| {:.3e} max|dp| {:.3e}   25-product up-convolutions: {:.3e} {:.3e}   ratio {:.2f}'.format(
+            name, tuple(x.shape), float(ref.abs().max()), row['today'][0], row['today'][1], row['upconv4'][0], row['upconv4'][1], ratio))
+        ok = ok and ratio <= 1.5 and (name != 'g18_unet_stress' or row['upconv4'][1] < 3e-5)
+    print('gate A: {}'.format('pass' if ok else 'FAIL'))
+    return 0 if ok else 1
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'upconv4':
+        sys.exit(upconv4_gate())
     min_cin = int(sys.argv[1]) if len(sys.argv) > 1 else 128
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 2
     import bench
