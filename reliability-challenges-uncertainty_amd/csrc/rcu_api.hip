@@ -240,16 +240,24 @@ static int pick_config(const ConvLayer& L, int n_slices, const rcu_unet_options&
         // full-width tile of four slices takes them as they are (round 6; padded to 32x32 the level would compute a third more)
         if (w4_ok && gw == 32 && gh % 8 == 0) return CONV_CFG_WINO4_S4T8x32_N32;
         if (w4_ok && gw == 16 && gh % 8 == 0) return CONV_CFG_WINO4_S8T8x16_N32;
-        // the 12x8 level (bottom_convs): F(4x4,3x3) with a slice's 6 tiles in the 8 tile slots of the S8 block -- 3 multiplications per output
-        // pixel executed (2.25 x 4/3) against F(2x2,3x3)'s 4 (round 5; no pooled output in this geometry)
+        // the 12x8 level (bottom_convs): F(4x4,3x3) with the 60 tiles of ten slices in the 64 tile slots of a workgroup -- 2.4 multiplications per
+        // output pixel executed (2.25 x 64/60) against F(2x2,3x3)'s 4 (round 5; ten slices instead of eight -- 48 of 64 slots -- since
+        // profiles/fold10_gate.txt; no pooled output in this geometry)
         if (w4_ok && gw == 8 && gh % 12 == 0 && L.t_pool < 0) {
-            // ... where its few, long work items fill the chip's rounds: one item = 8 slices x 32 couts against F(2x2,3x3)'s 8 slices x a 4x8 strip x
-            // 64 couts.  Measured per round of 256 workgroups (bottom_convs, tools/layer_report.py): 0.282 against 0.210 ms, so the folded form wins
-            // when rounds_4 * 1.35 < rounds_2 -- 640 samples: 5 against 8 rounds (1.41 against 1.68 ms), 480: 4 against 6; but 160 samples
-            // (an ensemble member's launch): 2 against 2 (0.57 against 0.44 ms), 320: 3 against 4 (a tie) -- there F(2x2,3x3) stays
-            const long groups = (n_slices + 7) / 8;
-            const long rounds4 = (groups * (gh / 12) * (L.coutp / 32) + 255) / 256;
-            const long rounds2 = (groups * (gh / 4) * ((L.coutp + 63) / 64) + 255) / 256;
+            // ... where its few, long work items fill the chip's rounds: one item = 10 slices x 32 couts against F(2x2,3x3)'s 8 slices x a 4x8 strip x
+            // 64 couts.  Measured per round of 256 workgroups (bottom_convs, tools/layer_report.py) while an item was 8 slices: 0.282 against
+            // 0.210 ms, so the folded form wins when rounds_4 * 1.35 < rounds_2 -- 640 samples: 4 against 8 rounds, 480: 3 against 6.  A round
+            // of ten slices measured 0.295 ms against the eight-slice tile's 0.284 on the same box (profiles/fold10_gate.txt): 1.18 against
+            // 1.42 ms at 640 samples, 0.89 against 1.14 at 480.
+            // Plans below the pass-group sizes of the predict steps (480 samples of 192x128, as upconv4_wins) keep the decisions of the 8-slice
+            // tile, i.e. the same rule with rounds_4 counted in groups of eight: 160 samples (an ensemble member's launch) 2 against 2, 320: 3
+            // against 4 -- F(2x2,3x3) stays.  Ten slices would take both (1 against 2, 2 against 4 rounds) and the kernel would win there too, but
+            // a 160-sample plan keeps the bits of an 8-sample one (tests/test_gpu_fullsize.py compares them); conv_winograd4 = 2 takes it.
+            const long long plan_pixels = (long long)n_slices * ((long long)L.H << L.level) * ((long long)L.W << L.level);
+            const long groups2 = (n_slices + 7) / 8;
+            const long groups4 = plan_pixels >= kUpconv4MinPlanPixels ? (n_slices + 9) / 10 : groups2;
+            const long rounds4 = (groups4 * (gh / 12) * (L.coutp / 32) + 255) / 256;
+            const long rounds2 = (groups2 * (gh / 4) * ((L.coutp + 63) / 64) + 255) / 256;
             if (w4_mode == 2 || L.coutp <= 32 || (double)rounds4 * 1.35 < (double)rounds2) return CONV_CFG_WINO4_S8T12x8_N32;   // (2: whatever the fill -- parity tests on small batches)
         }
         if (L.coutp == 32 && gh % 16 == 0 && gw % 32 == 0) return CONV_CFG_WINO_T16x32_N32;
@@ -449,7 +457,7 @@ static double plan_cost(const rcu_unet* h)
         const double kn = (double)(L.c1p + L.c2p) * (double)(L.NT * ci.BN);
         double mults, eff;
         if (L.cfg == CONV_CFG_FIRST_T8x32) { mults = 9.0; eff = 0.25; }                 // a write stream, not a matrix kernel
-        else if (ci.WINO == 3) { mults = L.cfg == CONV_CFG_WINO4_S8T12x8_N32 ? 3.0 : 2.25; eff = (L.c1p + L.c2p) <= 32 ? 0.45 : 0.58; }
+        else if (ci.WINO == 3) { mults = L.cfg == CONV_CFG_WINO4_S8T12x8_N32 ? 2.4 : 2.25; eff = (L.c1p + L.c2p) <= 32 ? 0.45 : 0.58; }
         else if (ci.WINO == 2) { mults = 9.0; eff = 0.72; }                              // four classes x 9 / 4 per low-resolution pixel
         else if (ci.WINO == 4) { mults = 6.25; eff = 0.70; }                             // 25 per 4x4 output tile = 2x2 low-resolution pixels; measured 0.63-0.76
         else if (ci.WINO == 1) { mults = 4.0; eff = 0.62; }
@@ -1498,7 +1506,7 @@ extern "C" int rcu_unet_layer_info(const rcu_unet* h, int layer, rcu_layer_info*
                                     : ci.WINO == 3 ? 2.0 * (L.c1p + L.c2p) * ncols * 36.0 * (px / 16.0)
                                     : ci.WINO == 4 ? 2.0 * L.c1p * ncols * 25.0 * (px / 16.0)   // px: output pixels; canonical x 25 / 144
                                                    : 2.0 * (L.c1p + L.c2p) * ncols * (ci.WINO ? 4.0 : (double)ci.TAPS) * px;
-        if (L.cfg == CONV_CFG_WINO4_S8T12x8_N32) out->mfma_flops_per_slice *= 4.0 / 3.0;   // 8 tile slots per slice execute, 6 hold tiles
+        if (L.cfg == CONV_CFG_WINO4_S8T12x8_N32) out->mfma_flops_per_slice *= 64.0 / 60.0;   // 64 tile slots per ten slices execute, 60 hold tiles
         if (L.cfg == CONV_CFG_FIRST_T8x32)   // K = 4 channels per tap unless more than four are real
             out->mfma_flops_per_slice = 2.0 * (L.cin1 > 4 ? 8 : 4) * ncols * 9.0 * px;
     }

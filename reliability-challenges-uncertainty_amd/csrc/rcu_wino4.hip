@@ -43,15 +43,20 @@ namespace rcu {
 // FULLW: the tile spans the image's width (checked by the launcher), so the halo columns are zero padding and are not staged at all:
 // the LDS image holds TW positions per row and the lanes of the first / last tile column zero their outer patch column themselves.
 // What it buys is LDS: eight slices of 8x16 pixels (the 24x16 level) fit the 160 KB only without the two halo columns.
-// FOLD: 12x8-pixel images (the BraTS bottom level).  A slice is 3 x 2 = 6 tiles of 4x4 pixels; they go into the 8 tile slots (2 block rows x 4
-// columns) a slice has in the S8 block geometry: slot k = 4 tr' + tc' holds tile (k / 2, k % 2) for k < 6, slots 6 and 7 are idle -- their MFMA rows
-// read tile 5's patch again and are never stored: 48 of a workgroup's 64 tile slots work (a lane's four tiles, slots 4g .. 4g+3 of one slice, are a
-// 2 x 2 block of tiles, the lower half of it idle for odd g), which still beats F(2x2,3x3)'s 4 multiplications per pixel with 2.25 x 4/3 = 3.
+// FOLD: 12x8-pixel images (the BraTS bottom level).  A slice is 3 x 2 = 6 tiles of 4x4 pixels, and the workgroup's 64 tile slots -- slot k = wave
+// k / 16, MFMA row k % 16 -- take the tiles of FOLD_TS = 10 consecutive slices one behind the other: slot k < 60 holds tile ((k % 6) / 2, k % 2) of
+// slice k / 6, slots 60..63 are idle -- their MFMA rows read slice 9's last patch again and are never stored.  60 of 64 slots work: 2.25 x 64/60 =
+// 2.4 multiplications per pixel against F(2x2,3x3)'s 4.  (Until the tile held ten slices a slice had the 8 slots of the S8 block geometry the tile
+// descends from, two of them idle: 48 of 64.)  A slice's tiles do not line up with the waves or with a lane's four accumulator rows any more: wave 0
+// holds slices 0, 1 and four tiles of slice 2, and the four slots 4j .. 4j+3 (j = 4 wave + g) of D-side lane (n, g) are tiles 0-3 of a slice
+// (j % 3 = 0), tiles 2-5 (j % 3 = 2), or tiles 4, 5 of one slice and 0, 1 of the next (j % 3 = 1); j = 15 is idle.  So slice, Dropout2d factor and
+// store offset are per tile in this geometry, derived in the epilogue (wino4_epilogue), not per lane.
 template <int SB_, int BR_, int BC_, int WS_, int WR_, bool FULLW_ = false, bool FOLD_ = false>
 struct Wino4Tile {
     static constexpr int SB = SB_, BR = BR_, BC = BC_, WS = WS_, WR = WR_;
     static constexpr bool FULLW = FULLW_, FOLD = FOLD_;
-    static constexpr int TS = SB * WS, TH = FOLD ? 12 : 4 * BR * WR, TW = FOLD ? 8 : 4 * BC;
+    static constexpr int FOLD_TS = 10;                                       // slices of a folded tile: 60 of the 64 slots
+    static constexpr int TS = FOLD ? FOLD_TS : SB * WS, TH = FOLD ? 12 : 4 * BR * WR, TW = FOLD ? 8 : 4 * BC;
     static constexpr int TCOLS = FOLD ? 2 : BC;                              // tile columns of the workgroup tile
     static constexpr int BN = 32, KC = 8, THREADS = 256, WAVES = 4, NPOS = 36;
     static constexpr int XCOLS = FULLW ? TW : TW + 2;                        // staged pixel columns per row: x = -1 .. TW, or 0 .. TW - 1
@@ -67,7 +72,8 @@ struct Wino4Tile {
     static constexpr int BUF_DW = A_DW + W_DW;
     static constexpr int LDS_BYTES = 2 * BUF_DW * 4;
     static_assert(SB * BR * BC == 16 && WS * WR == WAVES && BC % 4 == 0, "block geometry");
-    static_assert(!FOLD || (SB == 2 && BR == 2 && BC == 4 && WS == 4 && WR == 1 && FULLW), "the folded 12x8 geometry rides on the S8 block");
+    static_assert(!FOLD || (SB == 2 && BR == 2 && BC == 4 && WS == 4 && WR == 1 && FULLW), "the folded 12x8 geometry descends from the S8 block");
+    static_assert(!FOLD || 6 * TS <= 16 * WAVES, "a folded slice is 6 tiles");
     static_assert(W_DW % 256 == 0 && LDS_BYTES <= 160 * 1024, "LDS");
     // wave -> (first slice of its block inside the tile, top pixel row of its block inside the slice tile)
     static __device__ __forceinline__ void block_origin(int wave, int& s, int& y)
@@ -79,15 +85,28 @@ struct Wino4Tile {
     static __device__ __forceinline__ void tile_of(int m, int& sb, int& tr, int& tc)
     {
         sb = m / (BR * BC);
+        tr = (m / BC) % BR;
+        tc = m % BC;
+    }
+    // MFMA row m of wave `wave` -> (slice inside the workgroup tile, top pixel row of the 4x4 tile inside the slice tile, tile column)
+    static __device__ __forceinline__ void row_tile(int wave, int m, int& s, int& y, int& tc)
+    {
         if constexpr (FOLD) {
-            const int k = min(m % 8, 5);      // idle slots 6, 7 read tile 5's patch
-            tr = k >> 1;
-            tc = k & 1;
+            const int k = min(16 * wave + m, 6 * TS - 1);   // the idle slots read the last tile's patch
+            s = k / 6;
+            const int t = k - 6 * s;
+            y = 4 * (t >> 1);
+            tc = t & 1;
         } else {
-            tr = (m / BC) % BR;
-            tc = m % BC;
+            int bs, by, sb, tr;
+            block_origin(wave, bs, by);
+            tile_of(m, sb, tr, tc);
+            s = bs + sb;
+            y = by + 4 * tr;
         }
     }
+    // FOLD: does MFMA row m of wave `wave` hold a tile?
+    static __device__ __forceinline__ bool row_works(int wave, int m) { return !FOLD || 16 * wave + m < 6 * TS; }
     static __device__ __forceinline__ int swizzle(int x, int s, int R) { return (((x >> 3) ^ s) & 1) | (((R >> 2) & 1) << 1); }
 };
 
@@ -105,19 +124,19 @@ __device__ __forceinline__ uint32_t wino4_slot_geometry(int j, int wave, int lan
 }
 
 template <class T>
-__device__ __forceinline__ WinoEpiRaw wino4_epilogue_load(const ConvArgs& a, int ntile, int n0, int wave, int lane)
+__device__ __forceinline__ WinoEpiRaw wino4_epilogue_load(const ConvArgs& a, int ntile, int n0, int wave, int lane, int r = 0)
 {
+    // r: which of the lane's four tiles the Dropout2d factor belongs to -- they are tiles of one slice except in the folded geometry
     WinoEpiRaw e;
     const int co = ntile * T::BN + 2 * (lane & 15);   // < NT * BN, the length of alpha / betab / beta
-    int bs, by, sb, tr, tc;
-    T::block_origin(wave, bs, by);
-    T::tile_of(4 * (lane >> 4), sb, tr, tc);
+    int s, ty, tc;
+    T::row_tile(wave, 4 * (lane >> 4) + r, s, ty, tc);
     // the arguments in ONE batch of scalar loads (a wave alone on its SIMD sits out every scalar round trip: the mask branch used to fetch its
     // own arguments behind the branch)
     const float *alpha = a.alpha, *betab = a.betab, *beta = a.beta, *mask = a.mask, *mask2 = a.mask2;
     int N = a.N, Cmask = a.Cmask, Cmask2 = a.Cmask2, Csplit = a.Csplit;
     asm volatile("" : "+s"(alpha), "+s"(betab), "+s"(beta), "+s"(mask), "+s"(mask2), "+s"(N), "+s"(Cmask), "+s"(Cmask2), "+s"(Csplit));
-    const int n = min(n0 + bs + sb, N - 1);
+    const int n = min(n0 + s, N - 1);
     e.al = *reinterpret_cast<const f32x2*>(alpha + co);
     e.bb = *reinterpret_cast<const f32x2*>(betab + co);
     e.be = *reinterpret_cast<const f32x2*>(beta + co);
@@ -208,23 +227,24 @@ __device__ __forceinline__ float wino4_acc(const f32x4 (&accv)[8])
 }
 
 // Per-lane parts of the epilogue's store offsets (output and pooled output): slice, pixel and cout pair of the lane's first tile relative to
-// the workgroup tile's origin and cout tile -- made once per kernel; a tile adds scalars (wino4_epilogue).
+// the workgroup tile's origin and cout tile -- made once per kernel; a tile adds scalars (wino4_epilogue).  Folded geometry: the lane's four tiles
+// lie in up to two slices, so the plan holds the cout pair and pixel column only and the epilogue adds each tile's slice and pixel.
 struct Wino4StorePlan {
     uint32_t out, pool;
 };
 template <class T, bool PART>
 __device__ __forceinline__ Wino4StorePlan wino4_store_plan(const ConvArgs& a, int wave, int lane)
 {
-    int bs, by, sb, tr, tc;
-    T::block_origin(wave, bs, by);
-    T::tile_of(4 * (lane >> 4), sb, tr, tc);
+    int s, ty, tc;
+    T::row_tile(wave, 4 * (lane >> 4), s, ty, tc);
+    if constexpr (T::FOLD) s = ty = tc = 0;
     const int n16 = lane & 15, odd = n16 & 1, c = 2 * n16 - 2 * odd;   // the even lane stores four couts of one pixel column, the odd lane of the next
     // PART (padded levels, ConvArgs::part): `out` and `pooled` have extents of their own
     const int oH = PART ? a.out_H : a.H, oW = PART ? a.out_W : a.W;
     const int Hp = PART ? a.pool_H : a.H >> 1, Wp = PART ? a.pool_W : a.W >> 1;
     Wino4StorePlan p;
-    p.out = wino_out_offset(bs + sb, oH * oW, a.CoutP, (uint32_t)((by + 4 * tr) * oW + 4 * tc + odd), c, a.out_pix_bytes, a.out_chunk_bytes);
-    p.pool = wino_out_offset(bs + sb, Hp * Wp, a.CoutP, (uint32_t)(((by + 4 * tr) >> 1) * Wp + 2 * tc + odd), c, a.pool_pix_bytes, a.pool_chunk_bytes);
+    p.out = wino_out_offset(s, oH * oW, a.CoutP, (uint32_t)(ty * oW + 4 * tc + odd), c, a.out_pix_bytes, a.out_chunk_bytes);
+    p.pool = wino_out_offset(s, Hp * Wp, a.CoutP, (uint32_t)((ty >> 1) * Wp + 2 * tc + odd), c, a.pool_pix_bytes, a.pool_chunk_bytes);
     return p;
 }
 
@@ -309,24 +329,48 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
     // PART: rows / columns of the real image left from the lane's first pixel (row by + 4 tr, column 4 tc + odd of the workgroup tile), and the same
     // for its first pooled pixel: a pixel `dy` rows down and `dx` columns right of the first is real iff dy < ylim && dx < xlim
     [[maybe_unused]] int ylim = 0, xlim = 0, pylim = 0, pxlim = 0;
+    [[maybe_unused]] int Hr = 0, Wr = 0;
     if constexpr (PART) {
-        int bs, by, sb, tr, tc;
-        T::block_origin(wave, bs, by);
-        T::tile_of(4 * (lane >> 4), sb, tr, tc);
-        const int Hr = a.Hr, Wr = a.Wr;
-        ylim = Hr - (y0 + by + 4 * tr);
-        xlim = Wr - (x0 + 4 * tc + odd);
-        pylim = (Hr >> 1) - ((y0 + by + 4 * tr) >> 1);
-        pxlim = (Wr >> 1) - (((x0 + 4 * tc) >> 1) + odd);
+        Hr = a.Hr;
+        Wr = a.Wr;
+        if constexpr (!T::FOLD) {
+            int s, ty, tc;
+            T::row_tile(wave, 4 * (lane >> 4), s, ty, tc);
+            ylim = Hr - (y0 + ty);
+            xlim = Wr - (x0 + 4 * tc + odd);
+            pylim = (Hr >> 1) - ((y0 + ty) >> 1);
+            pxlim = (Wr >> 1) - (((x0 + 4 * tc) >> 1) + odd);
+        }
+    }
+    // Folded geometry: the lane's four tiles are consecutive tiles of the 6-tile slices, so the last of them may belong to the next slice: a second
+    // set of epilogue constants with that slice's Dropout2d factors, loaded here and not beside the first (wino4_epilogue_load in the chunk loop):
+    // nothing new lives through the last chunks, and the round trip is nothing against the 32 or 64 chunks of a tile of this level
+    [[maybe_unused]] int s_first = 0;
+    [[maybe_unused]] WinoEpi ep_last = ep;
+    if constexpr (T::FOLD) {
+        int ty, tc;
+        T::row_tile(wave, 4 * (lane >> 4), s_first, ty, tc);
+        ep_last = wino_epilogue_fold(wino4_epilogue_load<T>(a, ntile, n0, wave, lane, 3));
     }
     wino_static_for<0, 4>([&](auto r_c) {
         constexpr int r = decltype(r_c)::value;
-        // where tile r of the lane's four sits relative to its first: the next tile column -- or, folded, a 2 x 2 block of tiles whose lower
-        // half (r = 2, 3) does not exist for the lanes that hold slots 4..7 of a slice (odd g): their stores go out of range
-        constexpr int tdx = T::FOLD ? 4 * (r & 1) : 4 * r, tdy = T::FOLD ? 4 * (r >> 1) : 0;
-        const uint32_t vo_r = (T::FOLD && r >= 2 && ((lane >> 4) & 1) != 0) ? WINO_OOB : vo;
+        // where tile r of the lane's four sits relative to its first: the next tile column -- or, folded, anywhere in the first tile's slice or
+        // the next one (row_tile), or nowhere (the idle slots 60..63: their stores go out of range)
+        constexpr int tdx = T::FOLD ? 0 : 4 * r, tdy = 0;
+        uint32_t vo_r = vo;
+        WinoEpi ep_r = ep;
+        if constexpr (T::FOLD) {
+            int s, ty, tc;
+            T::row_tile(wave, 4 * (lane >> 4) + r, s, ty, tc);
+            vo_r = T::row_works(wave, 4 * (lane >> 4) + r) ? vo + wino_out_offset(s, oH * oW, CoutP, (uint32_t)(ty * oW + 4 * tc), 0, px_bytes, chunk_bytes) : WINO_OOB;
+            if (s != s_first) ep_r = ep_last;
+            if constexpr (PART) {
+                ylim = Hr - (y0 + ty);
+                xlim = Wr - (x0 + 4 * tc + odd);
+            }
+        }
         f32x2 y[4][4];   // [row][col], components = the two couts
-        wino4_output_tile<r, EV>(accv, ep, relu_floor, y);
+        wino4_output_tile<r, EV>(accv, ep_r, relu_floor, y);
         // Neighbouring lanes (couts 2n, 2n+1 | 2n+2, 2n+3 of the same pixels) trade pixel columns: the even lane ends up with four
         // couts of columns 0 and 2 of the tile, the odd lane with four couts of columns 1 and 3 -> 16-byte stores.
 #pragma unroll
@@ -544,10 +588,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
     int aCol[2][6];
     bool zero_left = false, zero_right = false;   // FULLW: this lane's patch column 0 / 5 lies outside the image
     {
-        int bs, by, sb, tr, tc;
-        T::block_origin(wave, bs, by);
-        T::tile_of(m16, sb, tr, tc);
-        const int s = bs + sb, R0 = by + 4 * tr;
+        int s, R0, tc;
+        T::row_tile(wave, m16, s, R0, tc);
         const int base = (s * T::SLICE_POS + R0 * T::PITCH) * 8 + 2 * kq;
 #pragma unroll
         for (int ip = 0; ip < 2; ++ip)
@@ -893,9 +935,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
 using W4Cfg0 = Wino4Tile<1, 2, 8, 1, 4>;   // 32x32 pixels of one slice
 using W4Cfg1 = Wino4Tile<1, 2, 8, 2, 2>;   // 16x32 pixels of two consecutive slices (heights not divisible by 32)
 using W4Cfg2 = Wino4Tile<2, 2, 4, 4, 1, true>;   // 8x16 pixels of eight consecutive slices, full image width (the 24x16 level)
-using W4Cfg3 = Wino4Tile<2, 2, 4, 4, 1, true, true>;   // 12x8 pixels of eight consecutive slices, folded into the same block geometry (the 12x8 level)
+using W4Cfg3 = Wino4Tile<2, 2, 4, 4, 1, true, true>;   // 12x8 pixels of TEN consecutive slices, their 60 tiles folded into the 64 tile slots (the 12x8 level)
 using W4Cfg4 = Wino4Tile<1, 2, 8, 4, 1, true>;   // 8x32 pixels of four consecutive slices, full image width (round 6: 24x32 levels -- the reference's ISIC size 192x256 -- without padding to 32x32)
 
+// "S8T12x8" names the S8 block geometry the folded tile descends from (and the enum, the layer tables and the profiles know it by): the tile holds TEN
+// slices (W4Cfg3::TS).
 static const ConvConfigInfo kWino4Info[6] = {
     {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>", 8, 0, 3},
     {W4Cfg1::TS, W4Cfg1::TH, W4Cfg1::TW, W4Cfg1::BN, 8, 36, "conv3x3_winograd4<S2T16x32,N32,K8>", 8, 0, 3},
