@@ -727,6 +727,61 @@ int rcu_patch_table(const uint8_t* prediction_dev, const uint8_t* target_dev, co
 int rcu_patch_hist(const uint64_t* table_dev, size_t n_patches, int n_volumes, int levels, int accuracy_per_mille,
                    uint64_t* hist_dev /* [n_volumes][3][levels] */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Input corruptions (EXTENSION: the reference tests on clean, in-distribution volumes only; rcu_amd.corruption, rcu_amd.steps.CorruptInputStep and
+ * the `others.corruption` key of the test scripts -- calibration and uncertainty under dataset shift, Ovadia et al. 2019, Mehrtash et al. 2020)
+ *   Appearance corruptions of the network input: the labels stay valid, every writer and every evaluation action runs unchanged on the corrupted
+ *   run.  x and out are float32 [n][channels][H][W]; image i is the slice with GLOBAL index g = first_sample + i.  The output of a slice is a
+ *   function of (x of that slice, kind, amount, key, g) alone, bit for bit the same whatever n, the position in the batch, the launch geometry or
+ *   the stream.  Arithmetic is float32 with fmaf in the stated order unless said otherwise; a = (float)amount, p = i * W + j, c the channel.
+ *     0 gaussian_noise   y = fmaf(a, z, x), z the normal z(K = key, g, p, s = 0, class = c) of "Test-time logit sampling" above with C = channels
+ *                        (element c & 3 of the block c >> 2).  a >= 0, channels <= 8.
+ *     1 gaussian_blur    per plane scipy.ndimage.gaussian_filter(x, sigma = amount, mode='reflect', truncate=4.0): radius r = int(4 amount + 0.5),
+ *                        taps w_k = exp(-k^2 / (2 amount^2)) / sum, k = -r..r, made on the HOST in float64, rounded to float32 and passed as
+ *                        aux_host[k + r] (n_aux = 2 r + 1).  The H axis first, then the W axis on its float32 result; each pass is one chain
+ *                        acc = fmaf(w_k, x[i + k], acc) over k = -r..r from acc = 0; an index i out of range is -i - 1, or 2 n - 1 - i at the far
+ *                        end.  0 < amount <= 8, r < min(H, W).
+ *     2 downsample       k = (int)amount; y[i][j] = the mean of the pixels that exist in block (i / k, j / k): their float32 sum in raster order
+ *                        of the block, divided by their count.  2 <= k <= 16.
+ *     3 contrast         m = the mean of the (slice, channel) plane in float64 (a fixed partition summed in a fixed order: a function of the
+ *                        plane alone), m32 = (float)m, y = fmaf(a, x - m32, m32).  0 <= amount <= 4.
+ *     4 intensity_shift  y = x + a.  amount finite.
+ *     5 bias_field       y = x * expf(a * f_c(i, j)), f_c = sum over (u, v) in {0, 1, 2}^2 without (0, 0), in raster order, of
+ *                        coef[c][3 u + v - 1] * (A_u[i] * B_v[j]): f = fmaf(coef, A_u[i] * B_v[j], f) from f = 0, with A_u[i] = cos(pi u (i + 0.5) / H),
+ *                        B_v[j] = cos(pi v (j + 0.5) / W) made on the host in float64 and rounded to float32, and sum_e |coef[c][e]| = 1 (so |f| <= 1).
+ *                        aux_host = coef [channels][8], A [3][H], B [3][W] back to back (n_aux = 8 channels + 3 H + 3 W).  One field per channel,
+ *                        the same for every slice of a run (a coil profile); rcu_amd.corruption.bias_coefficients derives coef from the key.
+ *                        0 <= amount <= 2.
+ *     6 ghosting         y[i][j] = fmaf(a, x[(i + H / 2) mod H][j], x[i][j]) with the integer H / 2: the N/2 ghost along the phase-encode axis.
+ *                        0 <= amount <= 1.
+ *     7 channel_drop     y = 0 on the channels c whose bit (1 << c) is set in the mask passed as amount, y = x on the others (a missing MR sequence:
+ *                        z-scored inputs have mean 0).  amount an integer in 1 .. 2^channels - 2, 2 <= channels <= 30.
+ *   key and first_sample enter kind 0 only; kinds without aux_host take n_aux = 0.
+ *   Severities 1..5 of rcu_amd.corruption (part of the definition; in input units, BraTS inputs being per-channel z-scores):
+ *     gaussian_noise    0.1   0.2   0.3   0.5   0.8
+ *     gaussian_blur     0.5   1     1.5   2     3
+ *     downsample        2     3     4     6     8
+ *     contrast          0.8   0.6   0.45  0.3   0.2
+ *     intensity_shift   0.1   0.2   0.3   0.5   0.8
+ *     bias_field        0.1   0.2   0.3   0.45  0.6
+ *     ghosting          0.05  0.1   0.15  0.25  0.4
+ *   (channel_drop has no severity: it names its channels.)
+ *   Limits: n, channels, H, W >= 1, H * W <= 2^30, channels <= 4096.  Every argument is checked before the device is touched (RCU_ERR_INVALID,
+ *   rcu_last_error() names it); a kind is never skipped silently.  x and out must not overlap.  workspace_dev: rcu_corrupt_workspace_bytes bytes
+ *   (0 for the kinds that need none: NULL is accepted there); aux_host is read before the call returns.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_CORRUPT_GAUSSIAN_NOISE 0
+#define RCU_CORRUPT_GAUSSIAN_BLUR 1
+#define RCU_CORRUPT_DOWNSAMPLE 2
+#define RCU_CORRUPT_CONTRAST 3
+#define RCU_CORRUPT_INTENSITY_SHIFT 4
+#define RCU_CORRUPT_BIAS_FIELD 5
+#define RCU_CORRUPT_GHOSTING 6
+#define RCU_CORRUPT_CHANNEL_DROP 7
+size_t rcu_corrupt_workspace_bytes(size_t n, int channels, int height, int width, int kind);
+int rcu_corrupt(const float* x_dev, size_t n, int channels, int height, int width, int kind, double amount, uint64_t key, uint64_t first_sample,
+                const float* aux_host, int n_aux, float* out_dev, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@ RCU_LOGIT_MAX_SAMPLES = 1024
 RCU_VOTES_MAX_PASSES = 64
 # patch-level uncertainty (include/rcu.h): the largest extent of a patch along an axis
 RCU_PATCH_MAX_EXTENT = 16
+# input corruptions (include/rcu.h): code -> name of the kinds of rcu_corrupt
+CORRUPTION_KINDS = ('gaussian_noise', 'gaussian_blur', 'downsample', 'contrast', 'intensity_shift', 'bias_field', 'ghosting', 'channel_drop')
 TTA_ELEMENTS = ('identity', 'flip_h', 'flip_v', 'rot180', 'transpose', 'rot90', 'rot270', 'anti_transpose')
 
 
@@ -172,6 +174,9 @@ SIGNATURES = {
     'rcu_patch_count': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'rcu_patch_table': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'rcu_patch_hist': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_corrupt_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int, c_int, c_int]),
+    'rcu_corrupt': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint64, POINTER(c_float), c_int, c_void_p, c_void_p,
+                            c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from . import calibration
+from . import corruption as corruption_mod
 from . import data as data_mod
 from . import distributed as rdist
 from . import evalrun
@@ -338,7 +339,7 @@ class PrepareSubjectStep(steps.BatchStep):
 
 def _other(context, key, default=None):
     """A key of the YAML file's free-form ``others`` (rcu_amd extensions, absent from the reference's configs: coalesce_pixels, pipelined,
-    max_inflight, stream_lanes, device_metrics, tta)."""
+    max_inflight, stream_lanes, device_metrics, tta, corruption)."""
     return getattr(context.config.others, key, default)
 
 
@@ -500,6 +501,41 @@ def _temperature_hooks(context):
     return [ApplyTemperatureHook(calibration.load_temperature(context.config.others.temperature))]
 
 
+class CorruptionRecordHook(loops.TestLoopHook):
+    """``others.corruption``: ``<test_dir>/corruption.json`` -- the parsed stages with their amounts, and the seed -- so that runs can be told
+    apart at evaluation time (the written files keep their names).  Written by the rank that writes the run's output."""
+
+    def __init__(self, record, file_name='corruption.json'):
+        self.record, self.file_name = record, file_name
+
+    def end_startup(self, context):
+        if not getattr(context, 'writes_output', True):
+            return
+        with open(os.path.join(context.test_dir, self.file_name), 'w') as f:
+            json.dump(self.record, f, indent=1, sort_keys=True)
+            f.write('\n')
+
+
+def _corruption(context):
+    """``others.corruption`` (an rcu_amd extension, include/rcu.h "Input corruptions"; rcu_amd.corruption.parse): one stage or a list of at most
+    8, applied in order to every batch in front of the script's predict steps -- on every rank: the corrupted slice is a function of the slice,
+    the stages, the YAML file's ``seed`` (0 without one) and the slice's global index.  -> (steps, startup hooks), both empty without the key."""
+    if not hasattr(context.config.others, 'corruption'):
+        return [], []
+    try:
+        stages = corruption_mod.parse(context.config.others.corruption)
+    except ValueError as e:
+        raise ValueError('others.corruption: {}'.format(e)) from None
+    seed = 0 if context.config.seed is None else int(context.config.seed)
+    return [steps.CorruptInputStep(stages, seed)], [CorruptionRecordHook(corruption_mod.describe(stages, seed))]
+
+
+def _refuse_corruption(context, script):
+    if hasattr(context.config.others, 'corruption'):
+        raise ValueError('others.corruption (input corruptions) applies to the test scripts only; the {} script does not take it: calibration is '
+                         'fitted on clean validation data'.format(script))
+
+
 def _default_steps(context, world):
     if hasattr(context.config.others, 'tta'):
         _agreement(context, world)      # (refuses others.agreement: true)
@@ -652,13 +688,14 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     _refuse_logit_samples(context, 'default')
     entries = ('probabilities',) if dataset == 'brats' else None
-    test_steps = _default_steps(context, world)
+    corrupt_steps, corrupt_hooks = _corruption(context)
+    test_steps = corrupt_steps + _default_steps(context, world)
     extra = []
     if any(isinstance(s_, steps.SampleAgreementStep) for s_ in test_steps):
         entries = None if entries is None else entries + ('agreement',)
         extra.append(AgreementCsvHook(context.config.others.mc))
     return _run(context, dataset, test_steps, WriteHook(link_inputs=dataset == 'isic'), entries, world,
-                startup_hooks=_temperature_hooks(context), subject_hooks=extra)
+                startup_hooks=_temperature_hooks(context) + corrupt_hooks, subject_hooks=extra)
 
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
@@ -667,13 +704,14 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
     _refuse_temperature(context, 'ensemble')
     _refuse_agreement(context, 'ensemble')
     _refuse_logit_samples(context, 'ensemble')
+    corrupt_steps, corrupt_hooks = _corruption(context)
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
     if world.world > 1:     # the K members of every batch sharded over the ranks (bin-dl/brats_test_ensemble.py:44-59 on N GPUs)
         test_steps = [rdist.ShardedEnsemblePredictionStep(members, world, lanes=lanes), steps.MultiPredictionSummary()]
     else:
         test_steps = [steps.EnsemblePredictionStep(members, lanes=lanes), steps.MultiPredictionSummary()]
-    return _run(context, dataset, test_steps, WriteHook(link_inputs=dataset == 'isic'), None, world)
+    return _run(context, dataset, corrupt_steps + test_steps, WriteHook(link_inputs=dataset == 'isic'), None, world, startup_hooks=corrupt_hooks)
 
 
 def test_aleatoric(dataset, config_file=None, device='cuda'):
@@ -681,8 +719,9 @@ def test_aleatoric(dataset, config_file=None, device='cuda'):
     _refuse_tta(context, 'aleatoric')
     _refuse_temperature(context, 'aleatoric')
     _refuse_agreement(context, 'aleatoric')
-    return _run(context, dataset, _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
-                None, world)
+    corrupt_steps, corrupt_hooks = _corruption(context)
+    return _run(context, dataset, corrupt_steps + _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
+                None, world, startup_hooks=corrupt_hooks)
 
 
 # ------------------------------------------------------------------------------- auxiliary networks
@@ -825,21 +864,22 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     _refuse_temperature(context, 'auxiliary_feat')
     _refuse_agreement(context, 'auxiliary_feat')
     _refuse_logit_samples(context, 'auxiliary_feat')
+    corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
         return context
     test_model = _load_segmentation_model(context)
     if dataset == 'brats':
         build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset())
-        test = loops.Test([AuxiliaryFeatPredictStep(test_model)], [loops.ExtractSubjectInfoStep(), EvalAuxiliaryFeatStep()],
+        test = loops.Test(corrupt_steps + [AuxiliaryFeatPredictStep(test_model)], [loops.ExtractSubjectInfoStep(), EvalAuxiliaryFeatStep()],
                           loops.SubjectAssembler(), entries=('probabilities', 'segm_probabilities'))
         hook = WriteConfidenceHook('segm_probabilities')
     else:
         build = data_mod.BuildData(build_dataset=data_mod.BuildIsicDataset())
-        test = loops.Test([AuxiliaryFeatPredictStep(test_model), PrepareSubjectStep()],
+        test = loops.Test(corrupt_steps + [AuxiliaryFeatPredictStep(test_model), PrepareSubjectStep()],
                           [EvalAuxiliaryFeatStep(squeeze_labels=True)], loops.Subject2dAssembler(),
                           entries=('probabilities', 'segm_probabilities', 'labels'))
         hook = WriteConfidenceHook('segm_probabilities', link=('label_paths',))
-    test(context, build, hook=_hooks(hook))
+    test(context, build, hook=_hooks(hook, corrupt_hooks))
     return context
 
 
@@ -849,11 +889,12 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     _refuse_temperature(context, 'auxiliary_segm')
     _refuse_agreement(context, 'auxiliary_segm')
     _refuse_logit_samples(context, 'auxiliary_segm')
+    corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
         return context
     if dataset == 'brats':
         build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset())
-        test = loops.Test([AuxiliarySegmPredictStep()], [loops.ExtractSubjectInfoStep(), EvalAuxiliarySegmStep()],
+        test = loops.Test(corrupt_steps + [AuxiliarySegmPredictStep()], [loops.ExtractSubjectInfoStep(), EvalAuxiliarySegmStep()],
                           loops.SubjectAssembler(), entries=('probabilities', 'orig_prediction'))
         hook = WriteConfidenceHook('orig_prediction')
     else:
@@ -861,10 +902,10 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
             raise ValueError('"others.prediction_dir" is required in the config')
         build = data_mod.BuildData(build_dataset=data_mod.BuildIsicDataset(),
                                    prediction_dir=context.config.others.prediction_dir)
-        test = loops.Test([AuxiliarySegmPredictStep(keep_labels=True)], [EvalAuxiliarySegmStep(set_score=True)],
+        test = loops.Test(corrupt_steps + [AuxiliarySegmPredictStep(keep_labels=True)], [EvalAuxiliarySegmStep(set_score=True)],
                           loops.Subject2dAssembler(), entries=('probabilities', 'labels', 'orig_prediction'))
         hook = WriteConfidenceHook('orig_prediction', link=('label_paths', 'image_paths'))
-    test(context, build, hook=_hooks(hook))
+    test(context, build, hook=_hooks(hook, corrupt_hooks))
     return context
 
 
@@ -912,6 +953,7 @@ def fit_temperature(dataset, config_file, device='cuda'):
     _refuse_temperature(context, 'fit_temperature')
     _refuse_logit_samples(context, 'fit_temperature')
     _refuse_agreement(context, 'fit_temperature')
+    _refuse_corruption(context, 'fit_temperature')
     mc = int(getattr(others, 'mc', 0) or 0)
     seed = 0 if context.config.seed is None else int(context.config.seed)
     context.load_from_checkpoint(context.get_test_at())

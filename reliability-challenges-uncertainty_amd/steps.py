@@ -715,6 +715,32 @@ def _images_to_device(batch_context, context):
     return images
 
 
+class CorruptInputStep(BatchStep):
+    """EXTENSION -- seeded input corruption for dataset-shift runs (rcu_amd.corruption, include/rcu.h "Input corruptions").  Put in front of the
+    predict steps: uploads the batch's images as they do and replaces ``batch_context.input['images']`` with the corrupted device tensor, image i
+    being the slice with global index ``first_sample_of(batch_context, n) + i``.  Every predict step that follows picks it up --
+    ``.float().to(device)`` on that tensor is a no-op -- and none of them needs to know.  ``stages``: ``corruption.parse``'s result (or what it
+    takes); ``seed``: the run's seed, stage s runs under ``corruption.corruption_seed(seed, s)``."""
+
+    def __init__(self, stages, seed) -> None:
+        super().__init__()
+        from . import corruption
+        if isinstance(stages, (list, tuple)) and stages and all(isinstance(s, corruption.Stage) for s in stages):
+            self.stages = tuple(stages)
+        else:
+            self.stages = corruption.parse(stages)
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError('CorruptInputStep needs an integer seed, got {!r}'.format(seed))
+        self.seed = seed
+        corruption.corruption_seed(seed, len(self.stages) - 1)
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        from . import corruption
+        _check_context(context)
+        images = _images_to_device(batch_context, context)
+        batch_context.input['images'] = corruption.corrupt(images, self.stages, self.seed, first_sample_of(batch_context, images.shape[0]))
+
+
 class SegmentationPredictStep(BatchStep):
 
     def __init__(self, has_labels=False, do_probs=False) -> None:
