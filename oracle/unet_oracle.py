@@ -79,7 +79,28 @@ def unet_plan(nb_classes, in_channels, depth=4, start_filters=16, dropout=0.2, d
         plan.append(dict(kind='rewind'))
         unit('conv_sigma.0', cout, cout, dropout is not None)
         plan.append(dict(kind='head', key='conv_sigma.1', cin=cout, cout=nb_classes, out='sigma'))
+    _number_layers(plan)
     return plan, sites
+
+
+def _number_layers(plan):
+    """op['index'] of every conv unit, up-convolution and residual 1x1 conv: the layer's position in the GPU plan (rcu_unet_layer_info order,
+    csrc/rcu_api.hip build_plan_for).  That order is the execution order, except that a residual block's 1x1 conv runs between the block's two
+    units (the second unit adds into its output), and conv_sigma.0 shares the row of conv_cls.0 (one kernel computes the twin)."""
+    index = 0
+    first_of_residual_block = False
+    for i, op in enumerate(plan):
+        if op['kind'] == 'res_begin':
+            first_of_residual_block = True
+        elif op['kind'] == 'unit' and op['key'].startswith('conv_sigma.0'):
+            op['index'] = next(o['index'] for o in plan if o['kind'] == 'unit' and o['key'].startswith('conv_cls.0'))
+        elif op['kind'] in ('unit', 'up'):
+            op['index'] = index
+            index += 1
+            if first_of_residual_block:
+                next(o for o in plan[i:] if o['kind'] == 'res_add')['index'] = index
+                index += 1
+                first_of_residual_block = False
 
 
 def strip_module_prefix(state):
@@ -87,32 +108,52 @@ def strip_module_prefix(state):
     return {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in state.items()}
 
 
-def unet_forward(state, x, masks=None, return_features=False, **params):
+def unet_forward(state, x, masks=None, return_features=False, dtype=torch.float32, tap=None, **params):
     """x: float32 [N, Cin, H, W] -> logits [N, C, H, W] or (logits, sigma) when sigma_out; with
     ``return_features`` also the input of conv_cls (UNet.features, unet.py:178-179) as the last element.
     ``state``: mapping name -> tensor/ndarray with the reference's state_dict keys.
-    ``masks``: None or a list (one per dropout site, execution order) of [N, C_site] factors."""
+    ``masks``: None or a list (one per dropout site, execution order) of [N, C_site] factors.
+    ``dtype``: torch.float64 promotes state, input and masks -- the high-precision reference the float32 oracle itself is measured against.
+    ``tap``: None or a callable ``tap(index, op, tensor) -> tensor``, called on the output of every conv unit (after mask, BatchNorm and ReLU)
+    and of every up-convolution (before the centre pad and the concat); what it returns stands for that output in the rest of the forward.
+    ``index`` is the layer's row in the GPU plan (rcu_unet_layer_info order, ``op['index']``), ``op`` the entry of unet_plan.  A tap records
+    activations (return ``tensor``) or plants a fault (tests/parity_power.py).  If it has a method ``resume(index, op)``, that is asked BEFORE a
+    layer is computed: a tensor it returns (the recorded output of an earlier, identical forward) is taken as the layer's output, the conv is
+    not computed and ``tap`` is not called for that layer -- a forward that differs from a recorded one from layer k on costs only the layers
+    behind k."""
     state = {k: torch.as_tensor(v) for k, v in strip_module_prefix(state).items()}
+    if dtype != torch.float32:
+        state = {k: (v.to(dtype) if torch.is_floating_point(v) else v) for k, v in state.items()}
     plan, sites = unet_plan(**params)
     if masks is not None and len(masks) != len(sites):
         raise ValueError('expected {} dropout masks, got {}'.format(len(sites), len(masks)))
-    x = torch.as_tensor(x, dtype=torch.float32)
+    x = torch.as_tensor(x, dtype=torch.float32).to(dtype)
+    resume = getattr(tap, 'resume', None)
     skips = []
     outs = {}
     trunk = None
     for op in plan:
         kind = op['kind']
-        if kind == 'unit':
+        recorded = resume(op['index'], op) if resume is not None and kind in ('unit', 'up') else None
+        if recorded is not None:
+            if kind == 'up':
+                skip = skips.pop()
+                x = torch.cat((_centre_pad(recorded, skip), skip), 1)
+            else:
+                x = recorded
+        elif kind == 'unit':
             k = op['key']
             x = F.conv2d(x, state[k + '.conv.weight'], state[k + '.conv.bias'], padding=1)
             if op['site'] is not None and masks is not None:
-                m = torch.as_tensor(masks[op['site']], dtype=torch.float32)
+                m = torch.as_tensor(masks[op['site']], dtype=torch.float32).to(dtype)
                 x = x * m[:, :, None, None]
             if op['bn']:
                 x = F.batch_norm(x, state[k + '.bn.running_mean'], state[k + '.bn.running_var'],
                                  state[k + '.bn.weight'], state[k + '.bn.bias'], False, 0.0, BN_EPS)
             if op.get('relu', True):
                 x = F.relu(x)
+            if tap is not None:
+                x = tap(op['index'], op, x)
         elif kind == 'res_begin':
             block_in = x
         elif kind == 'res_add':
@@ -124,11 +165,9 @@ def unet_forward(state, x, masks=None, return_features=False, **params):
             skip = skips.pop()
             up = F.interpolate(x, scale_factor=2, mode='nearest')
             up = F.conv2d(up, state[op['key'] + '.weight'], state[op['key'] + '.bias'], padding=1)
-            if tuple(up.shape[-2:]) < tuple(skip.shape[-2:]):  # unet.py:110-116
-                dh = skip.shape[-2] - up.shape[-2]
-                dw = skip.shape[-1] - up.shape[-1]
-                up = F.pad(up, (dw // 2, dw // 2 + dw % 2, dh // 2, dh // 2 + dh % 2))
-            x = torch.cat((up, skip), 1)
+            if tap is not None:
+                up = tap(op['index'], op, up)
+            x = torch.cat((_centre_pad(up, skip), skip), 1)
         elif kind == 'fork':
             trunk = x
         elif kind == 'rewind':
@@ -139,6 +178,15 @@ def unet_forward(state, x, masks=None, return_features=False, **params):
     if return_features:
         result = result + (trunk,)
     return result if len(result) > 1 else result[0]
+
+
+def _centre_pad(up, skip):
+    """unet.py:110-116."""
+    if tuple(up.shape[-2:]) < tuple(skip.shape[-2:]):
+        dh = skip.shape[-2] - up.shape[-2]
+        dw = skip.shape[-1] - up.shape[-1]
+        up = F.pad(up, (dw // 2, dw // 2 + dw % 2, dh // 2, dh // 2 + dh % 2))
+    return up
 
 
 def postnet_forward(state, x, nb_convs=3, masks=None):
@@ -286,3 +334,16 @@ def stress_state(state, bn_gain, head_gain):
             v = v * head_gain
         out[k] = v
     return out
+
+
+def sensitive_state(seed, bn_gain=2.5, **params):
+    """``stress_state(synthetic_state(seed, **params), 2.5, 0.5)``: the weights of the parity tests that have to see the deep levels.  Under
+    synthetic_state alone (torch's default init) every unit shrinks a perturbation, and the 13-16 units between the two deepest levels of the
+    depth-4 net and the classifier fade a lost element, a lost column of a slice or a stray Dropout2d factor at those levels to below the
+    2e-6 the logits are compared within; with the BatchNorm affines x 2.5 each of them moves the logits by a hundred times the bound
+    (2e-5 of the logit range) or more, at every layer, while the activations stay near 3 -- milder than G18's 1e2..1e3.  The power test,
+    tests/test_parity_power_cpu.py, asserts both statements layer by layer; tests/test_gpu_deep_levels.py runs the kernels on these weights.
+    ``bn_gain``: a net with residual blocks, whose sums grow on their own, takes 2.0 -- with 2.5 its logits reach +-140 under Dropout2d(0.3),
+    where the float32 oracle's own softmax is up to 7e-5 from the float64 one; with 2.0 they stay below 10 and the weakest fault still moves
+    them by 75 x the bound."""
+    return stress_state(synthetic_state(seed, **params), bn_gain, 0.5)
