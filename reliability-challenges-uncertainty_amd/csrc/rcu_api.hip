@@ -2,6 +2,7 @@
 // packing, workspace) and thin wrappers around the kernel launchers.
 #include "../../include/rcu.h"
 #include "rcu_kernels.h"
+#include "rcu_wpack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -131,14 +132,6 @@ static bool unit_has_dropout(const rcu_unet_desc& d, int level, bool is_down, in
     if (level == d.depth) return false;                    // 'no'
     if (level + d.dropout_center >= d.depth) return is_down ? (i == 1) : (i == 0);   // 'last' / 'first'
     return false;
-}
-
-// floats of one packed [TAPS][BN][KC+4] weight tile, rounded up to 256 threads x float4
-static size_t conv_tile_floats(const ConvConfigInfo& ci)
-{
-    if (ci.WINO) return (size_t)ci.TAPS * ci.BN * ci.KCP;   // the LDS image, piece by piece (LDS-DMA)
-    const size_t units = (size_t)ci.TAPS * ci.BN * ci.KCP / 4;
-    return (units + 255) / 256 * 256 * 4;
 }
 
 static bool is_head_unit(const ConvLayer& L) { return L.name.rfind("conv_cls.0", 0) == 0; }
@@ -320,12 +313,9 @@ static void add_residual_conv(rcu_unet* h, const std::string& prefix, int cin1, 
 
 static void assign_layouts(rcu_unet* h);
 
-// the kernels whose store side honours ConvArgs::part (a padded level): the Winograd families and rcu_first.hip
-static bool cfg_handles_padding(int cfg)
-{
-    return cfg == CONV_CFG_FIRST_T8x32 || (cfg >= CONV_CFG_WINO_T16x16_N64 && cfg <= CONV_CFG_UPW_S8T4x8_N64) ||
-           (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_UPW4_T32x32_N32);   // (rcu_wino4_up.hip: never chosen on a padded level, pick_config)
-}
+// the kernels whose store side honours ConvArgs::part (a padded level): the Winograd families but rcu_wino4_up.hip (never chosen on a padded level,
+// pick_config), and rcu_first.hip
+static bool cfg_handles_padding(int cfg) { return conv_config_info(cfg).family.part; }
 
 // Builds layers and tensors for the level extents in h->level_ext (build_plan: the real extents; choose_level_extents tries padded ones).
 // *valid = false when a layer that touches a padded tensor got a kernel that cannot: such a plan must not run.
@@ -455,15 +445,17 @@ static double plan_cost(const rcu_unet* h)
         const double tiles = (double)((L.gh + ci.TH - 1) / ci.TH) * ((L.gw + ci.TW - 1) / ci.TW);
         const double px = tiles * ci.TH * ci.TW;           // pixels of the grid the tiles walk (an up-convolution: the low-resolution grid)
         const double kn = (double)(L.c1p + L.c2p) * (double)(L.NT * ci.BN);
-        double mults, eff;
-        if (L.cfg == CONV_CFG_FIRST_T8x32) { mults = 9.0; eff = 0.25; }                 // a write stream, not a matrix kernel
-        else if (ci.WINO == 3) { mults = L.cfg == CONV_CFG_WINO4_S8T12x8_N32 ? 2.4 : 2.25; eff = (L.c1p + L.c2p) <= 32 ? 0.45 : 0.58; }
-        else if (ci.WINO == 2) { mults = 9.0; eff = 0.72; }                              // four classes x 9 / 4 per low-resolution pixel
-        else if (ci.WINO == 4) { mults = 6.25; eff = 0.70; }                             // 25 per 4x4 output tile = 2x2 low-resolution pixels; measured 0.63-0.76
-        else if (ci.WINO == 1) { mults = 4.0; eff = 0.62; }
-        else if (L.upsample) { mults = 16.0; eff = 0.72; }                               // four classes x 2x2 taps per low-resolution pixel
-        else { mults = 9.0; eff = 0.75; }
-        total += px * kn * mults / eff;
+        double eff = 0.0;
+        switch (ci.family.id) {
+            case ConvFamily::First: eff = 0.25; break;                                  // a write stream, not a matrix kernel
+            case ConvFamily::Wino4: eff = (L.c1p + L.c2p) <= 32 ? 0.45 : 0.58; break;
+            case ConvFamily::Wino2Up: eff = 0.72; break;
+            case ConvFamily::Wino4Up: eff = 0.70; break;                                // measured 0.63-0.76
+            case ConvFamily::Wino2: eff = 0.62; break;
+            case ConvFamily::DirectUp: eff = 0.72; break;
+            case ConvFamily::Direct: eff = 0.75; break;
+        }
+        total += px * kn * (ci.family.mults * ci.slot_factor) / eff;
     }
     return total;
 }
@@ -532,12 +524,6 @@ static int build_plan(rcu_unet* h) { return choose_level_extents(h); }
 // producers and consumers are Winograd kernels (rcu_first.hip as a producer), except the network input, the head unit's output
 // (head_kernel reads channels-last) and -- when the caller wants rcu_unet_features -- the feature tensor.  The two sources of a
 // cat-free decoder unit share one layout.  rcu_unet_options.act_layout = 1 keeps everything channels-last (A/B tests).
-static bool cfg_reads_blocked(int cfg)
-{
-    return (cfg >= CONV_CFG_WINO_T16x16_N64 && cfg <= CONV_CFG_UPW_S8T4x8_N64) || (cfg >= CONV_CFG_WINO4_T32x32_N32 && cfg < CONV_CFG_END);   // rcu_wino4_up.hip too
-}
-static bool cfg_writes_blocked(int cfg) { return cfg_reads_blocked(cfg) || cfg == CONV_CFG_FIRST_T8x32; }
-
 static void assign_layouts(rcu_unet* h)
 {
     const bool on = h->opt.act_layout == 0;
@@ -554,11 +540,12 @@ static void assign_layouts(rcu_unet* h)
             }
         };
         for (const ConvLayer& L : h->layers) {
-            if (!cfg_reads_blocked(L.cfg)) {
+            const ConvFamilyTraits& family = conv_config_info(L.cfg).family;
+            if (!family.reads_blocked) {
                 clear(L.t_src1);
                 clear(L.t_src2);
             }
-            if (!cfg_writes_blocked(L.cfg)) {
+            if (!family.writes_blocked) {
                 clear(L.t_out);
                 clear(L.t_pool);
             }
@@ -776,8 +763,6 @@ static int fold_conv(rcu_unet* h, const ConvLayer& L, const std::string& conv, c
                      std::vector<float>& wpack, std::vector<float>& alpha, std::vector<float>& betab,
                      std::vector<float>& beta)
 {
-    const ConvConfigInfo& ci = conv_config_info(L.cfg);
-    const int KC = ci.KC, KCP = ci.KCP, BN = ci.BN;
     const int cin = L.cin1 + L.cin2;
     const std::vector<float>*w, *b;
     std::vector<float> w_centre;
@@ -810,154 +795,7 @@ static int fold_conv(rcu_unet* h, const ConvLayer& L, const std::string& conv, c
         betab[co0 + co] = A * (*b)[co];
         beta[co0 + co] = B;
     }
-    const size_t tile_floats = conv_tile_floats(ci);   // padded to a whole number of float4 per thread
-    // Sub-pixel up-conv: output parity a (rows) folds the 3 kernel rows onto 2 low-res rows,
-    //   a = 0: low-res row y-1 <- {dy 0},   row y   <- {dy 1, 2}
-    //   a = 1: low-res row y   <- {dy 0, 1}, row y+1 <- {dy 2}            (same for columns with b)
-    auto fold_set = [](int parity, int t, int d) { return parity == 0 ? (t == 0 ? d == 0 : d >= 1) : (t == 0 ? d <= 1 : d == 2); };
-    if (ci.WINO == 2) {
-        // F(2x2,2x2) per parity class: U^{ab} = G w^{ab} G^T, G = [[1,0],[1,1],[0,1]], w^{ab} the 2x2 folded taps.  Packed
-        // per Cin chunk as tiles (a, cout tile) of [p = 6 i + 3 b + j][channel pair][cout][2]; column j = 0 of class b = 1
-        // is negated because the kernel feeds P.2 - P.1 where F(2,2) wants P.1 - P.2 (rcu_wino_up.hip).
-        static const double G2[3][2] = {{1, 0}, {1, 1}, {0, 1}};
-        for (int co = 0; co < L.cout; ++co) {
-            const int cop = co0 + co;
-            const int ntile = cop / BN, nn = cop % BN;
-            for (int ci_ = 0; ci_ < cin; ++ci_) {
-                const int chunk = ci_ / KC, kq = ci_ % KC;
-                const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
-                for (int pa = 0; pa < 2; ++pa) {
-                    const size_t tile0 = (((size_t)chunk * 2 + pa) * L.NT + ntile) * tile_floats;
-                    for (int pb = 0; pb < 2; ++pb) {
-                        double wc[2][2];
-                        for (int ty = 0; ty < 2; ++ty)
-                            for (int tx = 0; tx < 2; ++tx) {
-                                double v = 0.0;
-                                for (int dy = 0; dy < 3; ++dy)
-                                    for (int dx = 0; dx < 3; ++dx)
-                                        if (fold_set(pa, ty, dy) && fold_set(pb, tx, dx)) v += (double)w9[dy * 3 + dx];
-                                wc[ty][tx] = v;
-                            }
-                        for (int i = 0; i < 3; ++i)
-                            for (int j = 0; j < 3; ++j) {
-                                double u = 0.0;
-                                for (int ty = 0; ty < 2; ++ty)
-                                    for (int tx = 0; tx < 2; ++tx) u += G2[i][ty] * wc[ty][tx] * G2[j][tx];
-                                if (pb == 1 && j == 0) u = -u;
-                                const int p = 6 * i + 3 * pb + j;
-                                wpack[tile0 + (((size_t)p * 4 + (kq >> 1)) * BN + nn) * 2 + (kq & 1)] = (float)u;
-                            }
-                    }
-                }
-            }
-        }
-        return RCU_OK;
-    }
-    if (ci.WINO == 4) {
-        // F(4x4,3x3) of the up-sampled image (rcu_wino4_up.hip): U = G g G^T as below, without row and column 2 (the point -1, where the up-sampled
-        // input vanishes); rows and columns 3 (the point +2) carry the factor -3 by which the kernel's shared transformed value b - c differs from
-        // B^T's row 3 -- both directions for the corner entry: 9.  Computed in double, rounded once; packed per Cin chunk and cout tile as
-        // [position p = 5 ki + kj][channel pair q][cout][2], k = 0..4 the rows 0, 1, 3, 4, 5.
-        static const double G4[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
-        static const int keep[5] = {0, 1, 3, 4, 5};
-        for (int co = 0; co < L.cout; ++co) {
-            const int cop = co0 + co;
-            const int ntile = cop / BN, nn = cop % BN;
-            for (int ci_ = 0; ci_ < cin; ++ci_) {
-                const int chunk = ci_ / KC, kq = ci_ % KC;
-                const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
-                const size_t tile0 = ((size_t)chunk * L.NT + ntile) * tile_floats;
-                for (int ki = 0; ki < 5; ++ki)
-                    for (int kj = 0; kj < 5; ++kj) {
-                        double u = 0.0;
-                        for (int r = 0; r < 3; ++r)
-                            for (int c = 0; c < 3; ++c) u += G4[keep[ki]][r] * (double)w9[r * 3 + c] * G4[keep[kj]][c];
-                        u *= (keep[ki] == 3 ? -3.0 : 1.0) * (keep[kj] == 3 ? -3.0 : 1.0);
-                        const int p = 5 * ki + kj;
-                        wpack[tile0 + (((size_t)p * 4 + (kq >> 1)) * BN + nn) * 2 + (kq & 1)] = (float)u;
-                    }
-            }
-        }
-        return RCU_OK;
-    }
-    if (ci.WINO == 3) {
-        // F(4x4,3x3): U = G g G^T (6x6) per (cout, cin) with the Lavin-Gray G for the points 0, +-1, +-2, inf; packed per Cin chunk and
-        // cout tile as [position p = 6 i + j][channel pair q][cout][2] (rcu_wino4.hip).  Computed in double, rounded once.
-        static const double G4[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
-        for (int co = 0; co < L.cout; ++co) {
-            const int cop = co0 + co;
-            const int ntile = cop / BN, nn = cop % BN;
-            for (int ci_ = 0; ci_ < cin; ++ci_) {
-                const int kp = ci_ < L.cin1 ? ci_ : L.c1p + (ci_ - L.cin1);
-                const int chunk = kp / KC, kq = kp % KC;
-                const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
-                const size_t tile0 = ((size_t)chunk * L.NT + ntile) * tile_floats;
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) {
-                        double u = 0.0;
-                        for (int r = 0; r < 3; ++r)
-                            for (int c = 0; c < 3; ++c) u += G4[i][r] * (double)w9[r * 3 + c] * G4[j][c];
-                        const int p = 6 * i + j;
-                        wpack[tile0 + (((size_t)p * 4 + (kq >> 1)) * BN + nn) * 2 + (kq & 1)] = (float)u;
-                    }
-            }
-        }
-        return RCU_OK;
-    }
-    if (ci.WINO) {
-        // U = G g G^T per (cout, cin), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]; packed per Cin chunk and cout tile as
-        // [position p][channel pair q][cout][2] (rcu_wino.hip).  Computed in double, rounded once.
-        static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        for (int co = 0; co < L.cout; ++co) {
-            const int cop = co0 + co;
-            const int ntile = cop / BN, nn = cop % BN;
-            for (int ci_ = 0; ci_ < cin; ++ci_) {
-                const int kp = ci_ < L.cin1 ? ci_ : L.c1p + (ci_ - L.cin1);
-                const int chunk = kp / KC, kq = kp % KC;
-                const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
-                const size_t tile0 = ((size_t)chunk * L.NT + ntile) * tile_floats;
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) {
-                        double u = 0.0;
-                        for (int r = 0; r < 3; ++r)
-                            for (int c = 0; c < 3; ++c) u += G[i][r] * (double)w9[r * 3 + c] * G[j][c];
-                        const int p = 4 * i + j;
-                        wpack[tile0 + (((size_t)p * 4 + (kq >> 1)) * BN + nn) * 2 + (kq & 1)] = (float)u;
-                    }
-            }
-        }
-        return RCU_OK;
-    }
-    const int ncls = L.upsample ? 4 : 1;
-    for (int co = 0; co < L.cout; ++co) {
-        const int cop = co0 + co;
-        const int ntile = cop / BN, nn = cop % BN;
-        for (int ci_ = 0; ci_ < cin; ++ci_) {
-            const int kp = ci_ < L.cin1 ? ci_ : L.c1p + (ci_ - L.cin1);   // position in the padded K range
-            const int chunk = kp / KC, kq = kp % KC;
-            const float* w9 = w->data() + ((size_t)co * cin + ci_) * 9;
-            for (int cls = 0; cls < ncls; ++cls) {
-                const size_t tile0 = ((size_t)chunk * (ncls * L.NT) + (size_t)cls * L.NT + ntile) * tile_floats;
-                for (int tap = 0; tap < ci.TAPS; ++tap) {
-                    float v;
-                    if (!L.upsample) {
-                        v = w9[tap];
-                    } else {
-                        const int a = cls >> 1, b = cls & 1, ty = tap >> 1, tx = tap & 1;
-                        v = 0.f;
-                        for (int dy = 0; dy < 3; ++dy)
-                            for (int dx = 0; dx < 3; ++dx)
-                                if (fold_set(a, ty, dy) && fold_set(b, tx, dx)) v += w9[dy * 3 + dx];
-                    }
-                    // swizzled layout: the two 16-byte units of a row swap places for channels 16..31 (mod 32)
-                    const int kdst = ci.SWZ ? ((((kq >> 2) ^ ((nn >> 4) & 1)) << 2) | (kq & 3)) : kq;
-                    wpack[tile0 + ((size_t)tap * BN + nn) * KCP + kdst] = v;
-                }
-            }
-        }
-    }
+    pack_conv_weights(wpack_kernel(conv_config_info(L.cfg)), WpackLayer{L.cin1, L.c1p, L.cin2, L.cout, L.NT, L.upsample}, w->data(), co0, wpack.data());
     return RCU_OK;
 }
 
@@ -968,8 +806,7 @@ extern "C" int rcu_unet_finalize_weights(rcu_unet* h)
     if (h->finalized) return RCU_OK;
     for (ConvLayer& L : h->layers) {
         const ConvConfigInfo& ci = conv_config_info(L.cfg);
-        const int nchunks = (L.c1p + L.c2p) / ci.KC;
-        L.wpack_floats = (size_t)nchunks * L.NT * (ci.WINO == 2 ? 2 : ci.WINO == 4 ? 1 : L.upsample ? 4 : 1) * conv_tile_floats(ci);
+        L.wpack_floats = wpack_floats(wpack_kernel(ci), L.c1p + L.c2p, L.NT);
         std::vector<float> wpack(L.wpack_floats, 0.f);
         const int cpad = L.NT * ci.BN;
         std::vector<float> alpha(cpad, 0.f), betab(cpad, 0.f), beta(cpad, 0.f);
@@ -1015,8 +852,7 @@ extern "C" int rcu_unet_finalize_weights(rcu_unet* h)
 static bool head_fusable(const rcu_unet* h)
 {
     const ConvLayer& last = h->layers.back();
-    return (last.cfg == CONV_CFG_WINO_T16x32_N32 || last.cfg == CONV_CFG_WINO4_T32x32_N32) && h->d.nb_classes == 2 && last.name2.empty() &&
-           h->head_cph == 32;
+    return conv_config_info(last.cfg).head_cfg >= 0 && h->d.nb_classes == 2 && last.name2.empty() && h->head_cph == 32;
 }
 
 struct FusedHead {
@@ -1064,7 +900,7 @@ static int run_layer(rcu_unet* h, const ConvLayer& L, int n, const float* masks,
     }
     a.C1 = L.c1p; a.C2 = L.c2p; a.CoutP = L.coutp;
     a.cin_real = L.cin1;
-    a.x_nchw = L.cfg == CONV_CFG_FIRST_T8x32 ? x_nchw : nullptr;
+    a.x_nchw = ci.family.id == ConvFamily::First ? x_nchw : nullptr;
     a.n_images = n_images;
     a.Cmask = L.cout; a.Csplit = L.csplit; a.Cmask2 = L.cout;
     a.relu = L.relu;
@@ -1073,7 +909,7 @@ static int run_layer(rcu_unet* h, const ConvLayer& L, int n, const float* masks,
     a.tiles_x = (gw + ci.TW - 1) / ci.TW;
     a.slice_groups = (n + ci.TS - 1) / ci.TS;
     a.NT = L.NT;
-    a.NTW_total = L.NT * (ci.WINO == 2 ? 2 : ci.WINO == 4 ? 1 : L.upsample ? 4 : 1);
+    a.NTW_total = L.NT * ci.family.weight_sets;
     {
         const unsigned long long items = (unsigned long long)a.NTW_total * a.tiles_x * a.tiles_y * a.slice_groups;
         auto magic = [&](int d) -> uint32_t {
@@ -1095,7 +931,7 @@ static int run_layer(rcu_unet* h, const ConvLayer& L, int n, const float* masks,
     a.wpack_bytes = (uint32_t)std::min<size_t>(L.wpack_floats * 4, 0xFFFFFFFFu);
     int cfg = L.cfg;
     if (head) {
-        cfg = L.cfg == CONV_CFG_WINO4_T32x32_N32 ? CONV_CFG_WINO4_T32x32_N32_HEAD : CONV_CFG_WINO_T16x32_N32_HEAD;
+        cfg = ci.head_cfg;   // (forward_impl: head_fusable)
         a.head_w = h->w_cls; a.head_b = h->b_cls;
         a.head_logits = head->logits; a.head_stats = head->stats; a.head_flags = head->flags;
         a.head_passes = head->passes;
@@ -1139,7 +975,7 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
         ev = h->prof_events.data() + (size_t)(h->prof_used++) * prof_slots(h);
     if (ev) RCU_HIP(hipEventRecord(*ev++, stream));
     // the first-layer kernel reads the caller's NCHW input itself; every other first layer wants the channels-last copy
-    const bool direct_input = h->layers.front().cfg == CONV_CFG_FIRST_T8x32;
+    const bool direct_input = conv_config_info(h->layers.front().cfg).family.id == ConvFamily::First;
     if (!direct_input)
         RCU_HIP(launch_pack_input(x, h->tensors[h->t_input].dev, n_one, h->d.in_channels, h->in_cp, h->d.height, h->d.width,
                                   h->tensors[h->t_input].H, h->tensors[h->t_input].W, passes, stream));
@@ -1493,22 +1329,15 @@ extern "C" int rcu_unet_layer_info(const rcu_unet* h, int layer, rcu_layer_info*
     // an up-convolution works on the up-sampled grid, which a centre pad leaves smaller than the skip tensor it is padded to
     out->flops_per_slice = 2.0 * out->cin * out->cout * (L.is_1x1 ? 1.0 : 9.0) * (L.upsample ? 4.0 * (L.H / 2) * (L.W / 2) : (double)L.H * L.W);
     {
-        // executed on the matrix pipe: padded K and N, full tiles, 4 taps per output pixel for the sub-pixel form
-        const ConvConfigInfo ci = conv_config_info(L.cfg);
-        const int lh = L.gh, lw = L.gw;   // grid the tiles walk: the allocated extent of the level (rcu_layer_info.grid_height / grid_width)
-        const double tiles = (double)((lh + ci.TH - 1) / ci.TH) * ((lw + ci.TW - 1) / ci.TW);
-        const double px = tiles * ci.TH * ci.TW * (L.upsample ? 4.0 : 1.0);
+        // executed on the matrix pipe: padded K and N, full tiles of the grid the tiles walk (the allocated extent of the level: rcu_layer_info.grid_height /
+        // grid_width), the family's multiplications per pixel of it (ConvFamilyTraits::mults: what plan_cost counts), every tile slot
+        const ConvConfigInfo& ci = conv_config_info(L.cfg);
+        const double tiles = (double)((L.gh + ci.TH - 1) / ci.TH) * ((L.gw + ci.TW - 1) / ci.TW);
+        const double px = tiles * ci.TH * ci.TW;
         const double ncols = (double)L.NT * ci.BN;
-        // Winograd: 16 multiplications per 2x2 output tile instead of 9 per pixel
-        // and 9 per 2x2 low-resolution tile and parity class (= 9 per low-resolution pixel) for the up-convolutions
-        // F(4x4,3x3): 36 per 4x4 output tile; 25 for the up-convolutions on the up-sampled grid
-        out->mfma_flops_per_slice = ci.WINO == 2 ? 2.0 * L.c1p * ncols * 9.0 * (px / 4.0)
-                                    : ci.WINO == 3 ? 2.0 * (L.c1p + L.c2p) * ncols * 36.0 * (px / 16.0)
-                                    : ci.WINO == 4 ? 2.0 * L.c1p * ncols * 25.0 * (px / 16.0)   // px: output pixels; canonical x 25 / 144
-                                                   : 2.0 * (L.c1p + L.c2p) * ncols * (ci.WINO ? 4.0 : (double)ci.TAPS) * px;
-        if (L.cfg == CONV_CFG_WINO4_S8T12x8_N32) out->mfma_flops_per_slice *= 64.0 / 60.0;   // 64 tile slots per ten slices execute, 60 hold tiles
-        if (L.cfg == CONV_CFG_FIRST_T8x32)   // K = 4 channels per tap unless more than four are real
-            out->mfma_flops_per_slice = 2.0 * (L.cin1 > 4 ? 8 : 4) * ncols * 9.0 * px;
+        // (rcu_first.hip: K = 4 channels per tap unless more than four are real)
+        const int k = ci.family.id == ConvFamily::First ? (L.cin1 > 4 ? 8 : 4) : L.c1p + L.c2p;
+        out->mfma_flops_per_slice = 2.0 * k * ncols * ci.family.mults * px * ci.slot_factor;
     }
     return RCU_OK;
 }

@@ -562,18 +562,23 @@ using Cfg8 = ConvTile<1, 16, 16, 32, 8, 4, 1, 4, 1, 1>;
 using Cfg9 = ConvTile<1, 16, 16, 64, 8, 2, 2, 9, 1, 1>;
 using Cfg10 = ConvTile<2, 8, 16, 64, 8, 2, 2, 9, 1, 1>;
 
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: NHWC only, whole tensors only; 9 taps per pixel, or 2x2 taps for each of
+// the four parity classes of a low-resolution pixel (one weight-tile set per class)
+static constexpr ConvFamilyTraits kDirect = {ConvFamily::Direct, false, false, false, false, 1, 9.0};
+static constexpr ConvFamilyTraits kDirectUp = {ConvFamily::DirectUp, false, false, false, false, 4, 16.0};
+
 static const ConvConfigInfo kInfo[CONV_CFG_COUNT] = {
-    {Cfg0::TS, Cfg0::TH, Cfg0::TW, Cfg0::BN, Cfg0::KC, Cfg0::TAPS, "conv3x3_igemm<T8x16,N64,K8,db>", Cfg0::KCP, Cfg0::SWZ ? 1 : 0},
-    {Cfg1::TS, Cfg1::TH, Cfg1::TW, Cfg1::BN, Cfg1::KC, Cfg1::TAPS, "conv3x3_igemm<T8x16,N32,K8,db>", Cfg1::KCP, Cfg1::SWZ ? 1 : 0},
-    {Cfg2::TS, Cfg2::TH, Cfg2::TW, Cfg2::BN, Cfg2::KC, Cfg2::TAPS, "conv3x3_igemm<T8x16,N32,K8>", Cfg2::KCP, Cfg2::SWZ ? 1 : 0},
-    {Cfg3::TS, Cfg3::TH, Cfg3::TW, Cfg3::BN, Cfg3::KC, Cfg3::TAPS, "conv3x3_igemm<S2T12x8,N64,K8,db>", Cfg3::KCP, Cfg3::SWZ ? 1 : 0},
-    {Cfg4::TS, Cfg4::TH, Cfg4::TW, Cfg4::BN, Cfg4::KC, Cfg4::TAPS, "upconv_subpixel_igemm<T8x16,N64,K8,db>", Cfg4::KCP, Cfg4::SWZ ? 1 : 0},
-    {Cfg5::TS, Cfg5::TH, Cfg5::TW, Cfg5::BN, Cfg5::KC, Cfg5::TAPS, "upconv_subpixel_igemm<T8x16,N32,K8,db>", Cfg5::KCP, Cfg5::SWZ ? 1 : 0},
-    {Cfg6::TS, Cfg6::TH, Cfg6::TW, Cfg6::BN, Cfg6::KC, Cfg6::TAPS, "upconv_subpixel_igemm<S2T12x8,N64,K8,db>", Cfg6::KCP, Cfg6::SWZ ? 1 : 0},
-    {Cfg7::TS, Cfg7::TH, Cfg7::TW, Cfg7::BN, Cfg7::KC, Cfg7::TAPS, "conv3x3_igemm<T16x16,N32,K8,db>", Cfg7::KCP, Cfg7::SWZ ? 1 : 0},
-    {Cfg8::TS, Cfg8::TH, Cfg8::TW, Cfg8::BN, Cfg8::KC, Cfg8::TAPS, "upconv_subpixel_igemm<T16x16,N32,K8,db>", Cfg8::KCP, Cfg8::SWZ ? 1 : 0},
-    {Cfg9::TS, Cfg9::TH, Cfg9::TW, Cfg9::BN, Cfg9::KC, Cfg9::TAPS, "conv3x3_igemm<T16x16,N64,K8,db>", Cfg9::KCP, Cfg9::SWZ ? 1 : 0},
-    {Cfg10::TS, Cfg10::TH, Cfg10::TW, Cfg10::BN, Cfg10::KC, Cfg10::TAPS, "conv3x3_igemm<S2T8x16,N64,K8,db>", Cfg10::KCP, Cfg10::SWZ ? 1 : 0},
+    {Cfg0::TS, Cfg0::TH, Cfg0::TW, Cfg0::BN, Cfg0::KC, Cfg0::TAPS, "conv3x3_igemm<T8x16,N64,K8,db>", Cfg0::KCP, Cfg0::SWZ ? 1 : 0, kDirect},
+    {Cfg1::TS, Cfg1::TH, Cfg1::TW, Cfg1::BN, Cfg1::KC, Cfg1::TAPS, "conv3x3_igemm<T8x16,N32,K8,db>", Cfg1::KCP, Cfg1::SWZ ? 1 : 0, kDirect},
+    {Cfg2::TS, Cfg2::TH, Cfg2::TW, Cfg2::BN, Cfg2::KC, Cfg2::TAPS, "conv3x3_igemm<T8x16,N32,K8>", Cfg2::KCP, Cfg2::SWZ ? 1 : 0, kDirect},
+    {Cfg3::TS, Cfg3::TH, Cfg3::TW, Cfg3::BN, Cfg3::KC, Cfg3::TAPS, "conv3x3_igemm<S2T12x8,N64,K8,db>", Cfg3::KCP, Cfg3::SWZ ? 1 : 0, kDirect},
+    {Cfg4::TS, Cfg4::TH, Cfg4::TW, Cfg4::BN, Cfg4::KC, Cfg4::TAPS, "upconv_subpixel_igemm<T8x16,N64,K8,db>", Cfg4::KCP, Cfg4::SWZ ? 1 : 0, kDirectUp},
+    {Cfg5::TS, Cfg5::TH, Cfg5::TW, Cfg5::BN, Cfg5::KC, Cfg5::TAPS, "upconv_subpixel_igemm<T8x16,N32,K8,db>", Cfg5::KCP, Cfg5::SWZ ? 1 : 0, kDirectUp},
+    {Cfg6::TS, Cfg6::TH, Cfg6::TW, Cfg6::BN, Cfg6::KC, Cfg6::TAPS, "upconv_subpixel_igemm<S2T12x8,N64,K8,db>", Cfg6::KCP, Cfg6::SWZ ? 1 : 0, kDirectUp},
+    {Cfg7::TS, Cfg7::TH, Cfg7::TW, Cfg7::BN, Cfg7::KC, Cfg7::TAPS, "conv3x3_igemm<T16x16,N32,K8,db>", Cfg7::KCP, Cfg7::SWZ ? 1 : 0, kDirect},
+    {Cfg8::TS, Cfg8::TH, Cfg8::TW, Cfg8::BN, Cfg8::KC, Cfg8::TAPS, "upconv_subpixel_igemm<T16x16,N32,K8,db>", Cfg8::KCP, Cfg8::SWZ ? 1 : 0, kDirectUp},
+    {Cfg9::TS, Cfg9::TH, Cfg9::TW, Cfg9::BN, Cfg9::KC, Cfg9::TAPS, "conv3x3_igemm<T16x16,N64,K8,db>", Cfg9::KCP, Cfg9::SWZ ? 1 : 0, kDirect},
+    {Cfg10::TS, Cfg10::TH, Cfg10::TW, Cfg10::BN, Cfg10::KC, Cfg10::TAPS, "conv3x3_igemm<S2T8x16,N64,K8,db>", Cfg10::KCP, Cfg10::SWZ ? 1 : 0, kDirect},
 };
 
 hipError_t set_max_dynamic_lds(const void* kernel, int bytes)
@@ -629,11 +634,15 @@ static hipError_t launch_cfg(const ConvArgs& a, hipStream_t stream)
 
 hipError_t launch_conv3x3(int cfg, const ConvArgs& a, hipStream_t stream)
 {
-    if (cfg >= CONV_CFG_UPW4_T32x32_N32) return launch_upconv_wino4(cfg, a, stream);
-    if (cfg >= CONV_CFG_WINO4_T32x32_N32) return launch_conv_wino4(cfg, a, stream);
-    if (cfg == CONV_CFG_FIRST_T8x32) return launch_conv_first(a, stream);
-    if (cfg >= CONV_CFG_UPW_T16x16_N64) return launch_upconv_wino(cfg, a, stream);
-    if (cfg >= CONV_CFG_COUNT) return launch_conv_wino(cfg, a, stream);
+    switch (conv_config_info(cfg).family.id) {   // cfg: a ConvConfig value (pick_config's, or the head_cfg of its row)
+        case ConvFamily::Wino4Up: return launch_upconv_wino4(cfg, a, stream);
+        case ConvFamily::Wino4: return launch_conv_wino4(cfg, a, stream);
+        case ConvFamily::First: return launch_conv_first(a, stream);
+        case ConvFamily::Wino2Up: return launch_upconv_wino(cfg, a, stream);
+        case ConvFamily::Wino2: return launch_conv_wino(cfg, a, stream);
+        case ConvFamily::Direct:
+        case ConvFamily::DirectUp: break;
+    }
     switch (cfg) {
         case CONV_CFG_T8x16_N64: return launch_cfg<Cfg0>(a, stream);
         case CONV_CFG_T8x16_N32: return launch_cfg<Cfg1>(a, stream);

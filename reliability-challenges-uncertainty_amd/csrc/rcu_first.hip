@@ -25,7 +25,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int FIRST_TH = 8, FIRST_TW = 32, FIRST_THREADS = 256;
 constexpr int FIRST_HR = FIRST_TH + 2, FIRST_HC = FIRST_TW + 2;   // halo tile
-constexpr int FIRST_TILE_FLOATS = 3072;                          // packed [tap][32 couts][8 channels], padded (rcu_api.hip)
+constexpr int FIRST_TILE_FLOATS = 3072;                          // packed [tap][32 couts][8 channels], padded (rcu_wpack.h)
 
 template <int KS, int NB>
 __global__ __launch_bounds__(FIRST_THREADS) void conv3x3_first_kernel(const ConvArgs a, const int tiles_total)
@@ -148,7 +148,8 @@ hipError_t launch_first(const ConvArgs& a, hipStream_t stream)
     return hipGetLastError();
 }
 
-const ConvConfigInfo kFirstInfo = {1, FIRST_TH, FIRST_TW, 32, 8, 9, "conv3x3_first<T8x32,K36>", 8, 0, 0};
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: reads the caller's NCHW input or the NHWC copy, writes either layout; 9 taps
+const ConvConfigInfo kFirstInfo = {1, FIRST_TH, FIRST_TW, 32, 8, 9, "conv3x3_first<T8x32,K36>", 8, 0, {ConvFamily::First, false, false, true, true, 1, 9.0}};
 
 }  // namespace
 

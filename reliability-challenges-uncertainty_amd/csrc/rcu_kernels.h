@@ -140,15 +140,36 @@ enum ConvConfig {
     CONV_CFG_END
 };
 
+enum class ConvFamily {
+    Direct,      // 3x3 taps as they are (rcu_conv.hip)
+    DirectUp,    // sub-pixel up-convolution: 2x2 taps on the low-resolution grid per output parity class (rcu_conv.hip)
+    First,       // the network's first conv unit (rcu_first.hip); weights packed like Direct
+    Wino2,       // F(2x2,3x3), TAPS = 16 positions (rcu_wino.hip)
+    Wino2Up,     // F(2x2,2x2) up-convolution, TAPS = 18 = two parity classes of 9 (rcu_wino_up.hip)
+    Wino4,       // F(4x4,3x3), TAPS = 36 positions (rcu_wino4.hip)
+    Wino4Up,     // F(4x4,3x3) up-convolution without the vanishing point, TAPS = 25 positions (rcu_wino4_up.hip)
+};
+// What the host has to know about a kernel family; each family's file defines its record next to its ConvConfigInfo table.  Up-convolutions:
+// TH x TW of a row is the low-resolution tile, the grid the tiles walk.
+struct ConvFamilyTraits {
+    ConvFamily id;
+    bool winograd;        // packed weight tile = [position][channel pair][cout][2], the LDS image; else [tap][cout][KCP] (rcu_wpack.h)
+    bool reads_blocked;   // takes its sources in the channel-blocked layout as well as in NHWC (ConvArgs)
+    bool writes_blocked;  // ... its output and pooled output
+    bool part;            // store side honours ConvArgs::part: may read or write the tensors of a padded level
+    int weight_sets;      // weight-tile sets per (Cin chunk, cout tile): 1, 2 or 4 (one per parity class or pair of classes)
+    double mults;         // multiplications executed per pixel of the walked grid and (cin, cout) pair
+};
 struct ConvConfigInfo {
     int TS, TH, TW, BN, KC, TAPS;
     const char* kernel_name;
     int KCP;   // floats per [tap][channel] row of a packed weight tile (KC, or KC + 4 in the padded layout)
     int SWZ;   // 1: the two 16-byte units of a row are swapped for output channels 16..31 (mod 32), see ConvTile
-    int WINO;  // 1: Winograd F(2x2,3x3) kernel, TAPS = 16 positions; 2: F(2x2,2x2) up-conv, TAPS = 18 (two classes);
-               // 3: F(4x4,3x3), TAPS = 36 positions; 4: F(4x4,3x3) up-conv, TAPS = 25 positions, TH x TW = the low-resolution tile;
-               // packed tile = [p][channel pair][cout][2] (rcu_wino.hip, rcu_wino_up.hip, rcu_wino4.hip, rcu_wino4_up.hip)
+    ConvFamilyTraits family;
+    double slot_factor = 1.0;   // tile slots executed per tile held: 64 / 60 for the folded 12x8 tile of rcu_wino4.hip
+    int head_cfg = -1;          // the ConvConfig of this kernel with the 1x1 head fused into its epilogue, or -1
 };
+// the only function that knows the order of the ConvConfig values
 const ConvConfigInfo& conv_config_info(int cfg);
 const ConvConfigInfo& wino_config_info(int cfg);
 const ConvConfigInfo& wino_up_config_info(int cfg);

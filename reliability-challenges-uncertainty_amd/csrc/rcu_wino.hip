@@ -460,12 +460,15 @@ using WCfg1 = WinoTile<1, 16, 32, 32, 8, 1>;   // 512 pixels x 32 couts (32-chan
 using WCfg2 = WinoTile<2, 8, 16, 64, 4, 2>;    // two 8x16 pieces of consecutive slices (heights not divisible by 16)
 using WCfg3 = WinoTile<8, 4, 8, 64, 4, 2, 2>;  // 4x8 strips of eight slices (8-pixel-wide bottom level)
 
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: 16 multiplications per 2x2 output tile
+static constexpr ConvFamilyTraits kWino2 = {ConvFamily::Wino2, true, true, true, true, 1, 4.0};
+
 static const ConvConfigInfo kWinoInfo[5] = {
-    {WCfg0::TS, WCfg0::TH, WCfg0::TW, WCfg0::BN, 8, 16, "conv3x3_winograd<T16x16,N64,K8>", 8, 0, 1},
-    {WCfg1::TS, WCfg1::TH, WCfg1::TW, WCfg1::BN, 8, 16, "conv3x3_winograd<T16x32,N32,K8>", 8, 0, 1},
-    {WCfg2::TS, WCfg2::TH, WCfg2::TW, WCfg2::BN, 8, 16, "conv3x3_winograd<S2T8x16,N64,K8>", 8, 0, 1},
-    {WCfg3::TS, WCfg3::TH, WCfg3::TW, WCfg3::BN, 8, 16, "conv3x3_winograd<S8T4x8,N64,K8>", 8, 0, 1},
-    {WCfg1::TS, WCfg1::TH, WCfg1::TW, WCfg1::BN, 8, 16, "conv3x3_winograd<T16x32,N32,K8>+head", 8, 0, 1},
+    {WCfg0::TS, WCfg0::TH, WCfg0::TW, WCfg0::BN, 8, 16, "conv3x3_winograd<T16x16,N64,K8>", 8, 0, kWino2},
+    {WCfg1::TS, WCfg1::TH, WCfg1::TW, WCfg1::BN, 8, 16, "conv3x3_winograd<T16x32,N32,K8>", 8, 0, kWino2, 1.0, CONV_CFG_WINO_T16x32_N32_HEAD},
+    {WCfg2::TS, WCfg2::TH, WCfg2::TW, WCfg2::BN, 8, 16, "conv3x3_winograd<S2T8x16,N64,K8>", 8, 0, kWino2},
+    {WCfg3::TS, WCfg3::TH, WCfg3::TW, WCfg3::BN, 8, 16, "conv3x3_winograd<S8T4x8,N64,K8>", 8, 0, kWino2},
+    {WCfg1::TS, WCfg1::TH, WCfg1::TW, WCfg1::BN, 8, 16, "conv3x3_winograd<T16x32,N32,K8>+head", 8, 0, kWino2},
 };
 
 const ConvConfigInfo& wino_config_info(int cfg) { return kWinoInfo[cfg - CONV_CFG_WINO_T16x16_N64]; }

@@ -940,13 +940,16 @@ using W4Cfg4 = Wino4Tile<1, 2, 8, 4, 1, true>;   // 8x32 pixels of four consecut
 
 // "S8T12x8" names the S8 block geometry the folded tile descends from (and the enum, the layer tables and the profiles know it by): the tile holds TEN
 // slices (W4Cfg3::TS).
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: 36 multiplications per 4x4 output tile
+static constexpr ConvFamilyTraits kWino4 = {ConvFamily::Wino4, true, true, true, true, 1, 2.25};
+
 static const ConvConfigInfo kWino4Info[6] = {
-    {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>", 8, 0, 3},
-    {W4Cfg1::TS, W4Cfg1::TH, W4Cfg1::TW, W4Cfg1::BN, 8, 36, "conv3x3_winograd4<S2T16x32,N32,K8>", 8, 0, 3},
-    {W4Cfg2::TS, W4Cfg2::TH, W4Cfg2::TW, W4Cfg2::BN, 8, 36, "conv3x3_winograd4<S8T8x16,N32,K8>", 8, 0, 3},
-    {W4Cfg3::TS, W4Cfg3::TH, W4Cfg3::TW, W4Cfg3::BN, 8, 36, "conv3x3_winograd4<S8T12x8,N32,K8>", 8, 0, 3},
-    {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>+head", 8, 0, 3},
-    {W4Cfg4::TS, W4Cfg4::TH, W4Cfg4::TW, W4Cfg4::BN, 8, 36, "conv3x3_winograd4<S4T8x32,N32,K8>", 8, 0, 3},
+    {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>", 8, 0, kWino4, 1.0, CONV_CFG_WINO4_T32x32_N32_HEAD},
+    {W4Cfg1::TS, W4Cfg1::TH, W4Cfg1::TW, W4Cfg1::BN, 8, 36, "conv3x3_winograd4<S2T16x32,N32,K8>", 8, 0, kWino4},
+    {W4Cfg2::TS, W4Cfg2::TH, W4Cfg2::TW, W4Cfg2::BN, 8, 36, "conv3x3_winograd4<S8T8x16,N32,K8>", 8, 0, kWino4},
+    {W4Cfg3::TS, W4Cfg3::TH, W4Cfg3::TW, W4Cfg3::BN, 8, 36, "conv3x3_winograd4<S8T12x8,N32,K8>", 8, 0, kWino4, 64.0 / 60.0},   // 64 tile slots per ten slices execute, 60 hold tiles
+    {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>+head", 8, 0, kWino4},
+    {W4Cfg4::TS, W4Cfg4::TH, W4Cfg4::TW, W4Cfg4::BN, 8, 36, "conv3x3_winograd4<S4T8x32,N32,K8>", 8, 0, kWino4},
 };
 
 const ConvConfigInfo& wino4_config_info(int cfg) { return kWino4Info[cfg - CONV_CFG_WINO4_T32x32_N32]; }

@@ -439,10 +439,14 @@ using U4Cfg1 = Up4Tile<1, 2, 8, 2, 2>;   // 16x32 output pixels of two consecuti
 using U4Cfg2 = Up4Tile<2, 2, 4, 4, 1>;   // 8x16 output pixels of eight consecutive slices (the 24x16 level)
 
 // TH x TW: the low-resolution tile, as the sub-pixel kernels report it (the tile grid walks the low-resolution level)
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: both layouts, but whole tiles of unpadded levels only (no ConvArgs::part
+// form); 25 multiplications per 4x4 output tile = 2x2 low-resolution pixels
+static constexpr ConvFamilyTraits kWino4Up = {ConvFamily::Wino4Up, true, true, true, false, 1, 6.25};
+
 static const ConvConfigInfo kWino4UpInfo[3] = {
-    {U4Cfg0::TS, U4Cfg0::TH, U4Cfg0::TW, U4Cfg0::BN, 8, 25, "upconv_winograd4<T32x32,N32,K8>", 8, 0, 4},
-    {U4Cfg1::TS, U4Cfg1::TH, U4Cfg1::TW, U4Cfg1::BN, 8, 25, "upconv_winograd4<S2T16x32,N32,K8>", 8, 0, 4},
-    {U4Cfg2::TS, U4Cfg2::TH, U4Cfg2::TW, U4Cfg2::BN, 8, 25, "upconv_winograd4<S8T8x16,N32,K8>", 8, 0, 4},
+    {U4Cfg0::TS, U4Cfg0::TH, U4Cfg0::TW, U4Cfg0::BN, 8, 25, "upconv_winograd4<T32x32,N32,K8>", 8, 0, kWino4Up},
+    {U4Cfg1::TS, U4Cfg1::TH, U4Cfg1::TW, U4Cfg1::BN, 8, 25, "upconv_winograd4<S2T16x32,N32,K8>", 8, 0, kWino4Up},
+    {U4Cfg2::TS, U4Cfg2::TH, U4Cfg2::TW, U4Cfg2::BN, 8, 25, "upconv_winograd4<S8T8x16,N32,K8>", 8, 0, kWino4Up},
 };
 
 const ConvConfigInfo& wino4_up_config_info(int cfg) { return kWino4UpInfo[cfg - CONV_CFG_UPW4_T32x32_N32]; }

@@ -299,11 +299,15 @@ using UCfg1 = WinoTile<1, 16, 32, 32, 8, 1, 1, 18>;
 using UCfg2 = WinoTile<2, 8, 16, 64, 4, 2, 1, 18>;
 using UCfg3 = WinoTile<8, 4, 8, 64, 4, 2, 2, 18>;
 
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: one weight-tile set per row parity (two classes each); 9 multiplications
+// per 2x2 low-resolution tile and parity class = 9 per low-resolution pixel
+static constexpr ConvFamilyTraits kWino2Up = {ConvFamily::Wino2Up, true, true, true, true, 2, 9.0};
+
 static const ConvConfigInfo kWinoUpInfo[4] = {
-    {UCfg0::TS, UCfg0::TH, UCfg0::TW, UCfg0::BN, 8, 18, "upconv_winograd<T16x16,N64,K8>", 8, 0, 2},
-    {UCfg1::TS, UCfg1::TH, UCfg1::TW, UCfg1::BN, 8, 18, "upconv_winograd<T16x32,N32,K8>", 8, 0, 2},
-    {UCfg2::TS, UCfg2::TH, UCfg2::TW, UCfg2::BN, 8, 18, "upconv_winograd<S2T8x16,N64,K8>", 8, 0, 2},
-    {UCfg3::TS, UCfg3::TH, UCfg3::TW, UCfg3::BN, 8, 18, "upconv_winograd<S8T4x8,N64,K8>", 8, 0, 2},
+    {UCfg0::TS, UCfg0::TH, UCfg0::TW, UCfg0::BN, 8, 18, "upconv_winograd<T16x16,N64,K8>", 8, 0, kWino2Up},
+    {UCfg1::TS, UCfg1::TH, UCfg1::TW, UCfg1::BN, 8, 18, "upconv_winograd<T16x32,N32,K8>", 8, 0, kWino2Up},
+    {UCfg2::TS, UCfg2::TH, UCfg2::TW, UCfg2::BN, 8, 18, "upconv_winograd<S2T8x16,N64,K8>", 8, 0, kWino2Up},
+    {UCfg3::TS, UCfg3::TH, UCfg3::TW, UCfg3::BN, 8, 18, "upconv_winograd<S8T4x8,N64,K8>", 8, 0, kWino2Up},
 };
 
 const ConvConfigInfo& wino_up_config_info(int cfg) { return kWinoUpInfo[cfg - CONV_CFG_UPW_T16x16_N64]; }

@@ -236,27 +236,9 @@ def test_uncertain_voxel_table_matches_fixture_g20():
 
 def _plan_rows(h, w, n, cin=4, **options):
     """The planner alone (rcu_unet_plan: no device memory): [(name, kernel, height, width, grid_height, grid_width)] of the shipped BraTS / ISIC architecture."""
-    import ctypes
-    from rcu_amd import _lib
-    lib = _lib.load()
-    desc = _lib.UnetDesc(nb_classes=2, in_channels=cin, depth=4, start_filters=32, has_dropout=1, dropout_center=-1, sigma_out=options.pop('sigma_out', 0),
-                         bn=1, height=h, width=w, max_batch=n, residual=options.pop('residual', 0), provide_features=options.pop('provide_features', 0))
-    opts = _lib.UnetOptions()
-    lib.rcu_unet_default_options(ctypes.byref(opts))
-    for key, value in options.items():
-        setattr(opts, key, value)
-    handle = ctypes.c_void_p()
-    _lib.check(lib.rcu_unet_plan(ctypes.byref(desc), ctypes.byref(opts), ctypes.byref(handle)))
-    try:
-        assert lib.rcu_unet_finalize_weights(handle) == -4      # RCU_ERR_STATE: a plan is inspected, never run
-        rows = []
-        for i in range(lib.rcu_unet_num_layers(handle)):
-            info = _lib.LayerInfo()
-            _lib.check(lib.rcu_unet_layer_info(handle, i, ctypes.byref(info)))
-            rows.append((info.name.decode(), info.kernel.decode(), info.height, info.width, info.grid_height, info.grid_width))
-        return rows
-    finally:
-        lib.rcu_unet_destroy(handle)
+    from plan_rows import plan_rows      # (asserts on every plan that a plan is inspected, never run: rcu_unet_finalize_weights gives RCU_ERR_STATE)
+    desc = {k: options.pop(k) for k in ('sigma_out', 'residual', 'provide_features') if k in options}
+    return [(r['name'], r['kernel'], r['height'], r['width']) + r['grid'] for r in plan_rows(h, w, n, options, in_channels=cin, **desc)]
 
 
 def test_planner_pads_the_levels_of_the_references_real_shapes():

@@ -1,34 +1,11 @@
 """Planner rows of the folded F(4x4,3x3) tile of the 12x8 level, which holds ten slices per work item (csrc/rcu_api.hip pick_config, csrc/rcu_wino4.hip):
 through rcu_unet_plan, no GPU."""
-import ctypes
-
 import pytest
+
+from plan_rows import plan_rows
 
 FOLDED = 'conv3x3_winograd4<S8T12x8,N32,K8>'
 STRIP = 'conv3x3_winograd<S8T4x8,N64,K8>'
-
-
-def _plan_rows(h, w, n, **options):
-    from rcu_amd import _lib
-    lib = _lib.load()
-    desc = _lib.UnetDesc(nb_classes=2, in_channels=4, depth=4, start_filters=32, has_dropout=1, dropout_center=-1, sigma_out=0, bn=1, height=h, width=w,
-                         max_batch=n, residual=0, provide_features=0)
-    opts = _lib.UnetOptions()
-    lib.rcu_unet_default_options(ctypes.byref(opts))
-    for key, value in options.items():
-        setattr(opts, key, value)
-    handle = ctypes.c_void_p()
-    _lib.check(lib.rcu_unet_plan(ctypes.byref(desc), ctypes.byref(opts), ctypes.byref(handle)))
-    try:
-        rows = []
-        for i in range(lib.rcu_unet_num_layers(handle)):
-            info = _lib.LayerInfo()
-            _lib.check(lib.rcu_unet_layer_info(handle, i, ctypes.byref(info)))
-            rows.append(dict(name=info.name.decode(), kernel=info.kernel.decode(), height=info.height, width=info.width, cin=info.cin, cout=info.cout,
-                             flops=info.flops_per_slice, mfma_flops=info.mfma_flops_per_slice))
-        return rows
-    finally:
-        lib.rcu_unet_destroy(handle)
 
 
 # The 192x128 BraTS shape.  Plans of the pass-group launches (480 samples and up) count the folded kernel's rounds in groups of ten slices; smaller
@@ -37,10 +14,10 @@ def _plan_rows(h, w, n, **options):
 # 160-sample plan gives the bits of an 8-sample one (tests/test_gpu_fullsize.py).
 @pytest.mark.parametrize('n,kernel', [(640, FOLDED), (480, FOLDED), (448, FOLDED), (400, STRIP), (320, STRIP), (160, STRIP), (8, STRIP)])
 def test_bottom_level_kernel_by_plan_size(n, kernel):
-    rows = _plan_rows(192, 128, n)
+    rows = plan_rows(192, 128, n)
     assert (rows[9]['height'], rows[9]['width']) == (12, 8) and rows[9]['name'].startswith('bottom_convs')
     assert [r['kernel'] for r in rows if (r['height'], r['width']) == (12, 8)] == [kernel, kernel]
-    forced = _plan_rows(192, 128, n, conv_winograd4=2)
+    forced = plan_rows(192, 128, n, dict(conv_winograd4=2))
     assert [r['kernel'] for r in forced if (r['height'], r['width']) == (12, 8)] == [FOLDED, FOLDED]
     # nothing else of the plan depends on the rule
     assert [r['kernel'] for r in forced if (r['height'], r['width']) != (12, 8)] == [r['kernel'] for r in rows if (r['height'], r['width']) != (12, 8)]
@@ -48,7 +25,7 @@ def test_bottom_level_kernel_by_plan_size(n, kernel):
 
 def test_folded_kernel_reports_64_slots_per_60_tiles():
     for n in (640, 8):
-        rows = [r for r in _plan_rows(192, 128, n, conv_winograd4=2) if r['kernel'] == FOLDED]
+        rows = [r for r in plan_rows(192, 128, n, dict(conv_winograd4=2)) if r['kernel'] == FOLDED]
         assert [(r['cin'], r['cout']) for r in rows] == [(256, 512), (512, 512)]
         for r in rows:
             six_tiles = 2.0 * r['cin'] * r['cout'] * 36.0 * 6.0          # 36 products per 4x4 tile, six tiles per 12x8 slice

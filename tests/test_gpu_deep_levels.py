@@ -5,13 +5,12 @@ those faults moves the logits by at least 75 x the bound at every layer of a lev
 are the smallest shapes that reach the eight- and ten-slice work items, the four-slice tile, the padded levels of the reference's real shapes,
 the up-convolutions that read them and the residual blocks.  Run on the GPU box: ``python -m pytest tests/test_gpu_deep_levels.py -m gpu``; the
 one test without the mark needs the library but no device."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import parity_power as pp
+from plan_rows import plan_rows
 
 # Logits within pp.bound = 2e-5 of the oracle's logit range (the project's bound for weights with BatchNorm gains, golden G18, whose measured
 # worst is 8.4e-6), against the float32 oracle and against the float64 one.  The float32 oracle is 6.5e-7 .. 2.6e-6 of the range from the
@@ -97,31 +96,14 @@ def _split(rows):
 def test_expected_kernels_are_the_planners_and_cover_every_winograd_instantiation():
     """No device: rcu_unet_plan on each case's shape, batch and options gives the literals above, and over all cases every Winograd instantiation
     that the suite names appears in a plan that test_deep_levels_vs_oracle runs."""
-    from rcu_amd import _lib
-    lib = _lib.load()
     assert set(EXPECTED) == set(RUNS)
     seen = set()
     for name, plan in RUNS:
         case = pp.CASES[name]
         n, _, h, w = case['shape']
         p = case['params']
-        desc = _lib.UnetDesc(nb_classes=p['nb_classes'], in_channels=p['in_channels'], depth=p['depth'], start_filters=p['start_filters'], has_dropout=1,
-                             dropout_center=-1, sigma_out=0, bn=1, height=h, width=w, max_batch=n, residual=int(p.get('residual', False)), provide_features=0)
-        opts = _lib.UnetOptions()
-        lib.rcu_unet_default_options(ctypes.byref(opts))
-        for key, value in OPTIONS[name, plan].items():
-            setattr(opts, key, value)
-        handle = ctypes.c_void_p()
-        _lib.check(lib.rcu_unet_plan(ctypes.byref(desc), ctypes.byref(opts), ctypes.byref(handle)))
-        try:
-            rows = []
-            for i in range(lib.rcu_unet_num_layers(handle)):
-                info = _lib.LayerInfo()
-                _lib.check(lib.rcu_unet_layer_info(handle, i, ctypes.byref(info)))
-                rows.append(dict(kernel=info.kernel.decode(), height=info.height, width=info.width))
-        finally:
-            lib.rcu_unet_destroy(handle)
-        deep, rest = _split(rows)
+        deep, rest = _split(plan_rows(h, w, n, OPTIONS[name, plan], nb_classes=p['nb_classes'], in_channels=p['in_channels'], depth=p['depth'],
+                                      start_filters=p['start_filters'], residual=p.get('residual', False)))
         assert deep == EXPECTED[name, plan]['deep'], (name, plan, deep)
         assert rest == EXPECTED[name, plan]['rest'], (name, plan, sorted(rest))
         seen.update(deep, rest)

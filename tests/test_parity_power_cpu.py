@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import parity_power as pp
+from plan_rows import plan_rows
 from oracle import unet_oracle as uo
 
 LOGIT_TOL = 2e-6      # the bound of the parity tests that run synthetic_state nets (tests/test_gpu_parity.py)
@@ -24,8 +25,6 @@ def test_oracle_hooks_number_the_layers_as_the_planner_and_resume_bit_exactly(ex
     """unet_forward's ``tap`` and ``dtype`` on a small net: the tap sees every conv unit and up-convolution under the index and name of its row
     in rcu_unet_layer_info; an identity tap and the default dtype change no bit; a forward resumed behind layer k from a recorded one is the
     full forward with the same mutation, bit for bit; float64 is float64 throughout and a rounding error away from float32."""
-    import ctypes
-    from rcu_amd import _lib
     params = dict(nb_classes=3, in_channels=2, depth=2, start_filters=8, dropout=0.2, **extra)
     state = uo.synthetic_state(3, **params)
     g = torch.Generator().manual_seed(4)
@@ -42,20 +41,8 @@ def test_oracle_hooks_number_the_layers_as_the_planner_and_resume_bit_exactly(ex
     taped = uo.unet_forward(state, x, masks, tap=record, **params)
     assert torch.equal(first(taped), first(plain)) and first(plain).dtype == torch.float32
     # the planner's rows (no device): same indices, same names; the rows the tap does not see are the residual 1x1 convs
-    lib = _lib.load()
-    desc = _lib.UnetDesc(nb_classes=3, in_channels=2, depth=2, start_filters=8, has_dropout=1, dropout_center=extra.get('dropout_center', -1),
-                         sigma_out=int(extra.get('sigma_out', False)), bn=1, height=22, width=24, max_batch=2, residual=int(extra.get('residual', False)),
-                         provide_features=0)
-    handle = ctypes.c_void_p()
-    _lib.check(lib.rcu_unet_plan(ctypes.byref(desc), None, ctypes.byref(handle)))
-    try:
-        names = []
-        for i in range(lib.rcu_unet_num_layers(handle)):
-            info = _lib.LayerInfo()
-            _lib.check(lib.rcu_unet_layer_info(handle, i, ctypes.byref(info)))
-            names.append(info.name.decode())
-    finally:
-        lib.rcu_unet_destroy(handle)
+    names = [r['name'] for r in plan_rows(22, 24, 2, nb_classes=3, in_channels=2, depth=2, start_filters=8, dropout_center=extra.get('dropout_center', -1),
+                                          sigma_out=extra.get('sigma_out', False), residual=extra.get('residual', False))]
     for index, calls in seen.items():
         key = calls[0][0]
         assert names[index] == (key[:-len('.conv2d_batch_relu')] + '.conv2d_batch_relu.conv' if key.endswith('.conv2d_batch_relu') else key), (index, key)

@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from plan_rows import plan_rows
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Lavin & Gray's F(4x4,3x3), interpolation points 0, +-1, +-2, inf
@@ -76,29 +78,6 @@ def test_25_products_match_upsample_then_conv(cin, cout):
     assert np.max(np.abs(got - ref)) < 1e-12
 
 
-def _plan_rows(h, w, n, depth=4, **options):
-    from rcu_amd import _lib
-    lib = _lib.load()
-    desc = _lib.UnetDesc(nb_classes=2, in_channels=4, depth=depth, start_filters=32, has_dropout=1, dropout_center=-1, sigma_out=0, bn=1, height=h, width=w,
-                         max_batch=n, residual=0, provide_features=0)
-    opts = _lib.UnetOptions()
-    lib.rcu_unet_default_options(ctypes.byref(opts))
-    for key, value in options.items():
-        setattr(opts, key, value)
-    handle = ctypes.c_void_p()
-    _lib.check(lib.rcu_unet_plan(ctypes.byref(desc), ctypes.byref(opts), ctypes.byref(handle)))
-    try:
-        rows = []
-        for i in range(lib.rcu_unet_num_layers(handle)):
-            info = _lib.LayerInfo()
-            _lib.check(lib.rcu_unet_layer_info(handle, i, ctypes.byref(info)))
-            rows.append(dict(name=info.name.decode(), kernel=info.kernel.decode(), height=info.height, width=info.width, grid=(info.grid_height, info.grid_width),
-                             cin=info.cin, cout=info.cout, flops=info.flops_per_slice, mfma_flops=info.mfma_flops_per_slice))
-        return rows
-    finally:
-        lib.rcu_unet_destroy(handle)
-
-
 OLD = ['upconv_winograd<S8T4x8,N64,K8>', 'upconv_winograd<S2T8x16,N64,K8>', 'upconv_winograd<T16x16,N64,K8>', 'upconv_winograd<T16x32,N32,K8>']
 NEW = ['upconv_winograd4<S8T8x16,N32,K8>', 'upconv_winograd4<S2T16x32,N32,K8>', 'upconv_winograd4<T32x32,N32,K8>', 'upconv_winograd4<T32x32,N32,K8>']
 # what the default rule (csrc/rcu_api.hip, upconv4_wins) takes per plan size of the 192x128 BraTS shape: the per-layer gate admitted every size
@@ -118,19 +97,19 @@ def test_planner_takes_the_25_product_upconvolutions_by_option_and_plan_size():
     lib.rcu_unet_default_options(ctypes.byref(opts))
     assert opts.upconv_winograd4 == 1 and ctypes.sizeof(_lib.UnetOptions) == 8 * 4
     for n, want in DEFAULT_PLANS.items():
-        assert _ups(_plan_rows(192, 128, n)) == want, n
-        assert _ups(_plan_rows(192, 128, n, upconv_winograd4=0)) == OLD, n
-        assert sum('winograd' in r['kernel'] for r in _plan_rows(192, 128, n)) == 22
-    small = _plan_rows(192, 128, 8, upconv_winograd4=2)
+        assert _ups(plan_rows(192, 128, n)) == want, n
+        assert _ups(plan_rows(192, 128, n, dict(upconv_winograd4=0))) == OLD, n
+        assert sum('winograd' in r['kernel'] for r in plan_rows(192, 128, n)) == 22
+    small = plan_rows(192, 128, 8, dict(upconv_winograd4=2))
     assert _ups(small) == NEW                                    # all three geometries, whatever the fill
     for r in small:
         if 'upconv' in r['name']:
             assert r['grid'] == (r['height'] // 2, r['width'] // 2)      # the tiles walk the low-resolution level
             assert r['mfma_flops'] == pytest.approx(r['flops'] * 25 / 144, rel=1e-12)      # executed = canonical x 25 / 144
     # everything but the up-convolutions is the option-0 plan
-    zero = _plan_rows(192, 128, 8, upconv_winograd4=0)
+    zero = plan_rows(192, 128, 8, dict(upconv_winograd4=0))
     assert [r for r in small if 'upconv' not in r['name']] == [r for r in zero if 'upconv' not in r['name']]
-    assert zero == _plan_rows(192, 128, 8)
+    assert zero == plan_rows(192, 128, 8)
     # a value outside 0..2 is refused
     desc = _lib.UnetDesc(nb_classes=2, in_channels=4, depth=4, start_filters=32, has_dropout=1, dropout_center=-1, sigma_out=0, bn=1, height=192, width=128,
                          max_batch=8)
@@ -141,11 +120,11 @@ def test_planner_takes_the_25_product_upconvolutions_by_option_and_plan_size():
         assert b'rcu_unet_options' in lib.rcu_last_error()
     # padded levels (the native 240x240 slices) keep the sub-pixel kernels under every value
     for value in (0, 1, 2):
-        native = _plan_rows(240, 240, 155, upconv_winograd4=value)
-        assert native == _plan_rows(240, 240, 155, upconv_winograd4=0)
+        native = plan_rows(240, 240, 155, dict(upconv_winograd4=value))
+        assert native == plan_rows(240, 240, 155, dict(upconv_winograd4=0))
         assert all(k.startswith('upconv_winograd<') for k in _ups(native)), value
     # a level of exactly one 32x32 tile
-    assert _ups(_plan_rows(64, 64, 2, depth=2, upconv_winograd4=2)) == ['upconv_winograd4<T32x32,N32,K8>'] * 2
+    assert _ups(plan_rows(64, 64, 2, dict(upconv_winograd4=2), depth=2)) == ['upconv_winograd4<T32x32,N32,K8>'] * 2
 
 
 @pytest.mark.timeout(600)

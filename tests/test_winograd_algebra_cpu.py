@@ -1,4 +1,4 @@
-"""The algebra the Winograd kernels rely on (csrc/rcu_wino.hip, csrc/rcu_wino_up.hip, weight packing in csrc/rcu_api.hip),
+"""The algebra the Winograd kernels rely on (csrc/rcu_wino.hip, csrc/rcu_wino_up.hip, weight packing in csrc/rcu_wpack.h),
 checked in float64 on the CPU against torch's conv2d / nearest interpolation -- the operations of the reference
 (common/model/unet.py:8-23, 98-120; common/model/helpers.py:5-16).  No product code runs here: the GPU tests compare the
 kernels themselves with the oracle; this file pins the transforms, the sub-pixel fold and the sign fold they implement."""
@@ -35,7 +35,7 @@ def test_f23_equals_conv3x3():
 
 def _fold(parity, t, d):
     """Kernel row d of the 3x3 window lands on low-resolution row t (0 / 1) of the 2x2 window of output parity `parity`
-    (fold_set in csrc/rcu_api.hip)."""
+    (fold_set in csrc/rcu_wpack.h)."""
     return (d == 0 if t == 0 else d >= 1) if parity == 0 else (d <= 1 if t == 0 else d == 2)
 
 
