@@ -188,19 +188,12 @@ hipError_t launch_conv_first(const ConvArgs& a, hipStream_t stream);
 // Measured round 4 (profiles/r04_nt_loads.txt): head kernel 116 -> 98 us (0.61 -> 0.72 of the HBM peak), ece_hist / unc_counts 0.72 / 0.74 -> 0.79 /
 // 0.82.  NOT for the conv kernels' input staging (their input was written by the previous kernel and neighbouring tiles re-read its halo: +4..5 %
 // time with nt there) and NOT for mc_accumulate / mc_finalize (their logits and statistics were written by the kernel before them and one volume's
-// worth sits in the 256 MB memory-side cache: finalize 13.3 -> 15.3 us with nt).  -DRCU_STREAM_NT=0: plain loads everywhere.
-#ifndef RCU_STREAM_NT
-#define RCU_STREAM_NT 1
-#endif
+// worth sits in the 256 MB memory-side cache: finalize 13.3 -> 15.3 us with nt).
 #if defined(__HIPCC__)
 template <class V>
 __device__ __forceinline__ V stream_load_as(const void* p)
 {
-#if RCU_STREAM_NT
     return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-#else
-    return *reinterpret_cast<const V*>(p);
-#endif
 }
 __device__ __forceinline__ float stream_load(const float* p) { return stream_load_as<float>(p); }
 __device__ __forceinline__ unsigned stream_load(const unsigned* p) { return stream_load_as<unsigned>(p); }

@@ -37,8 +37,6 @@
 #include "rcu_head_common.h"
 #include "rcu_wino_common.h"
 
-#include <cstdlib>
-
 namespace rcu {
 
 // Output transform + conv-unit epilogue of one finished tile.  acc[b][p][r]: MFMA block b (cout 2n+b), position p,
@@ -256,15 +254,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_stream(const ConvArgs a, con
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             const int yy = yy0 + 2 * i2, swz = (yy >> 1) & 1;
-#if RCU_WINO_IMAGE8
-            const int rowbase = (sl * T::SLICE_POS + yy * T::PITCH) * 8 + kq * 2;   // [slice][row][position][8 channels]
-            aA[i2] = rowbase + 8 * (x0l + swz);
-            aB[i2] = rowbase + 8 * (x0l - swz);
-#else
             const int rowbase = ((kq >> 1) * T::HALF_POS + sl * T::SLICE_POS + yy * T::PITCH) * 4 + (kq & 1) * 2;
             aA[i2] = rowbase + 4 * (x0l + swz);   // even patch columns j: pixel x0l + j sits at position x0l + j + swz
             aB[i2] = rowbase + 4 * (x0l - swz);   // odd  patch columns j: pixel x0l + j sits at position x0l + j - swz
-#endif
         }
     }
     const int b_addr = T::A_DW + (kq * T::BN + wn * 32 + 2 * m16) * 2;
@@ -320,10 +312,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_stream(const ConvArgs a, con
             if (job.active && ((j + 1) * T::WAVES <= T::A_PIECES || j * T::WAVES + wave < T::A_PIECES)) {
                 if (job.first)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr_t)(uintptr_t)(lds_base + job.lb + (j * T::WAVES + wave) * 1024), 16,
-                                                             dp[j], job.cb, 0, RCU_DMA_IN_AUX);
+                                                             dp[j], job.cb, 0, 0);
                 else
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs2, (lds_ptr_t)(uintptr_t)(lds_base + job.lb + (j * T::WAVES + wave) * 1024), 16,
-                                                             dp[j], job.cb, 0, RCU_DMA_IN_AUX);
+                                                             dp[j], job.cb, 0, 0);
             }
         }
     };

@@ -34,8 +34,6 @@
 #include "rcu_wino_common.h"
 #include "rcu_head_common.h"
 
-#include <cstdlib>
-
 namespace rcu {
 
 // Workgroup tile: WS slice groups x WR block rows of MFMA row blocks; a block = SB slices x BR tile rows x BC tile columns = 16
@@ -191,10 +189,9 @@ __host__ __device__ constexpr bool wino4_in_vgpr(int b, int p) { return b == 1 &
 // first AGPR of the accumulator tuple of (cout block b, position p)
 __host__ __device__ constexpr int wino4_areg(int b, int p) { return 4 * (b == 0 ? p : 36 + (p < 18 ? p : p - 8)); }
 
-template <int B, int P, bool ZERO, bool NOP, bool PROBE = false>
+template <int B, int P, bool ZERO>
 __device__ __forceinline__ void wino4_mfma(f32x4 (&accv)[8], float av, float wv)
 {
-    if constexpr (PROBE) asm volatile("s_nop 7\n\ts_nop 7");
     if constexpr (wino4_in_vgpr(B, P)) {
         if constexpr (ZERO)
             asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, 0\n\ts_nop 11" : "=v"(accv[P - 18]) : "v"(av), "v"(wv));
@@ -202,14 +199,10 @@ __device__ __forceinline__ void wino4_mfma(f32x4 (&accv)[8], float av, float wv)
             asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 11" : "+v"(accv[P - 18]) : "v"(av), "v"(wv));
     } else {
         constexpr int R = wino4_areg(B, P);
-        if constexpr (ZERO && NOP)
+        if constexpr (ZERO)
             asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, 0" ::"v"(av), "v"(wv), "i"(R), "i"(R + 3) : WINO4_ALL_AGPRS);
-        else if constexpr (ZERO)
-            asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, 0" ::"v"(av), "v"(wv), "i"(R), "i"(R + 3) : WINO4_ALL_AGPRS);
-        else if constexpr (NOP)
-            asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(av), "v"(wv), "i"(R), "i"(R + 3) : WINO4_ALL_AGPRS);
         else
-            asm volatile("v_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(av), "v"(wv), "i"(R), "i"(R + 3) : WINO4_ALL_AGPRS);
+            asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(av), "v"(wv), "i"(R), "i"(R + 3) : WINO4_ALL_AGPRS);
     }
 }
 
@@ -250,44 +243,37 @@ __device__ __forceinline__ Wino4StorePlan wino4_store_plan(const ConvArgs& a, in
 
 // Output transform A^T M A + conv-unit epilogue (scale, shift, ReLU) of tile R of the lane's four: y[row][col], components = the lane's two
 // couts -- packed operations throughout (one instruction costs the same matrix time whether it is packed or not, see the chunk pipeline).
-template <int R, int EV = 0>
+template <int R>
 __device__ __forceinline__ void wino4_output_tile(const f32x4 (&accv)[8], const WinoEpi& ep, float relu_floor, f32x2 (&y)[4][4])
 {
     constexpr int r = R;
     const f32x2 scale = {ep.scale[0], ep.scale[1]}, shift = {ep.shift[0], ep.shift[1]}, floor2 = {relu_floor, relu_floor};
     f32x2 nn[6][4];   // N[i][q] = sum_j M[i][j] A[j][q]
-    if constexpr ((EV & 4) != 0) {
-        wino_static_for<0, 16>([&](auto k_c) {
-            constexpr int k = decltype(k_c)::value;
-            y[k >> 2][k & 3] = f32x2{wino4_acc<0, k, r>(accv), wino4_acc<1, k, r>(accv)};
-        });
-    } else {
-        wino_static_for<0, 6>([&](auto i_c) {
-            constexpr int i = decltype(i_c)::value;
-            auto m = [&](auto j_c) {
-                constexpr int j = decltype(j_c)::value;
-                return f32x2{wino4_acc<0, 6 * i + j, r>(accv), wino4_acc<1, 6 * i + j, r>(accv)};
-            };
-            const f32x2 m0 = m(std::integral_constant<int, 0>{}), m1 = m(std::integral_constant<int, 1>{}), m2 = m(std::integral_constant<int, 2>{}),
-                        m3 = m(std::integral_constant<int, 3>{}), m4 = m(std::integral_constant<int, 4>{}), m5 = m(std::integral_constant<int, 5>{});
-            const f32x2 s1 = m1 + m2, s2 = m1 - m2, s3 = m3 + m4, s4 = m3 - m4;
-            nn[i][0] = (m0 + s1) + s3;
-            nn[i][1] = s2 + 2.f * s4;
-            nn[i][2] = s1 + 4.f * s3;
-            nn[i][3] = (s2 + 8.f * s4) + m5;
-        });
+    wino_static_for<0, 6>([&](auto i_c) {
+        constexpr int i = decltype(i_c)::value;
+        auto m = [&](auto j_c) {
+            constexpr int j = decltype(j_c)::value;
+            return f32x2{wino4_acc<0, 6 * i + j, r>(accv), wino4_acc<1, 6 * i + j, r>(accv)};
+        };
+        const f32x2 m0 = m(std::integral_constant<int, 0>{}), m1 = m(std::integral_constant<int, 1>{}), m2 = m(std::integral_constant<int, 2>{}),
+                    m3 = m(std::integral_constant<int, 3>{}), m4 = m(std::integral_constant<int, 4>{}), m5 = m(std::integral_constant<int, 5>{});
+        const f32x2 s1 = m1 + m2, s2 = m1 - m2, s3 = m3 + m4, s4 = m3 - m4;
+        nn[i][0] = (m0 + s1) + s3;
+        nn[i][1] = s2 + 2.f * s4;
+        nn[i][2] = s1 + 4.f * s3;
+        nn[i][3] = (s2 + 8.f * s4) + m5;
+    });
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x2 s1 = nn[1][q] + nn[2][q], s2 = nn[1][q] - nn[2][q], s3 = nn[3][q] + nn[4][q], s4 = nn[3][q] - nn[4][q];
-            const f32x2 v0 = (nn[0][q] + s1) + s3;
-            const f32x2 v1 = s2 + 2.f * s4;
-            const f32x2 v2 = s1 + 4.f * s3;
-            const f32x2 v3 = (s2 + 8.f * s4) + nn[5][q];
-            y[0][q] = __builtin_elementwise_max(v0 * scale + shift, floor2);
-            y[1][q] = __builtin_elementwise_max(v1 * scale + shift, floor2);
-            y[2][q] = __builtin_elementwise_max(v2 * scale + shift, floor2);
-            y[3][q] = __builtin_elementwise_max(v3 * scale + shift, floor2);
-        }
+    for (int q = 0; q < 4; ++q) {
+        const f32x2 s1 = nn[1][q] + nn[2][q], s2 = nn[1][q] - nn[2][q], s3 = nn[3][q] + nn[4][q], s4 = nn[3][q] - nn[4][q];
+        const f32x2 v0 = (nn[0][q] + s1) + s3;
+        const f32x2 v1 = s2 + 2.f * s4;
+        const f32x2 v2 = s1 + 4.f * s3;
+        const f32x2 v3 = (s2 + 8.f * s4) + nn[5][q];
+        y[0][q] = __builtin_elementwise_max(v0 * scale + shift, floor2);
+        y[1][q] = __builtin_elementwise_max(v1 * scale + shift, floor2);
+        y[2][q] = __builtin_elementwise_max(v2 * scale + shift, floor2);
+        y[3][q] = __builtin_elementwise_max(v3 * scale + shift, floor2);
     }
 }
 
@@ -295,16 +281,10 @@ __device__ __forceinline__ void wino4_output_tile(const f32x4 (&accv)[8], const 
 // tile r of the lane's four.
 // PART: the level is padded (ConvArgs::part) -- the tile may hang over the real image: pixels at or beyond (Hr, Wr) go out of range like the
 // slices beyond the batch, and the output / pooled tensors have extents of their own.
-template <class T, int EV = 0, bool PART = false>   // EV (ablation build): 1 stores out of range, 2 no store instructions, 4 no output transform
+template <class T, bool PART = false>
 __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&accv)[8], const WinoEpi& ep, int ntile, int n0, int y0, int x0,
                                                int wave, int lane, const Wino4StorePlan& plan)
 {
-    auto store16 = [&](const f32x4& o, const __amdgpu_buffer_rsrc_t& rs, uint32_t voff, uint32_t soff) {
-        if constexpr ((EV & 2) != 0)
-            asm volatile("" ::"v"(o));
-        else
-            wino_store16(o, rs, (EV & 1) != 0 ? WINO_OOB : voff, soff);
-    };
     // every MFMA has long retired: the last chunk's barrier lies between them and this point; the nops cover the asm-to-asm case
     // (an MFMA's D read by v_accvgpr_read) the compiler cannot see
     asm volatile("s_nop 15\n\ts_nop 7");
@@ -370,7 +350,7 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
             }
         }
         f32x2 y[4][4];   // [row][col], components = the two couts
-        wino4_output_tile<r, EV>(accv, ep_r, relu_floor, y);
+        wino4_output_tile<r>(accv, ep_r, relu_floor, y);
         // Neighbouring lanes (couts 2n, 2n+1 | 2n+2, 2n+3 of the same pixels) trade pixel columns: the even lane ends up with four
         // couts of columns 0 and 2 of the tile, the odd lane with four couts of columns 1 and 3 -> 16-byte stores.
 #pragma unroll
@@ -384,7 +364,7 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
                 recv.y = wino_swap_adjacent(send.y);
                 const f32x4 o = odd ? f32x4{recv.x, recv.y, keep.x, keep.y} : f32x4{keep.x, keep.y, recv.x, recv.y};
                 const uint32_t vo_s = (PART && !(tdy + aa < ylim && tdx + 2 * h2 < xlim)) ? WINO_OOB : vo_r;
-                store16(o, ro, vo_s, (uint32_t)(tdx + 2 * h2) * px_bytes + (uint32_t)(tdy + aa) * row_bytes);
+                wino_store16(o, ro, vo_s, (uint32_t)(tdx + 2 * h2) * px_bytes + (uint32_t)(tdy + aa) * row_bytes);
             }
         }
         if (!T::FOLD && pool) {   // wave-uniform; 2x2 pooled pixels per tile: the even lane stores four couts of pooled column 0, the odd lane of column 1 (the folded geometry -- the bottom level -- has no pooled output: launcher)
@@ -402,7 +382,7 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
                 recv.y = wino_swap_adjacent(send.y);
                 const f32x4 o = odd ? f32x4{recv.x, recv.y, keep.x, keep.y} : f32x4{keep.x, keep.y, recv.x, recv.y};
                 const uint32_t vp_s = (PART && !(a2 < pylim && 2 * r < pxlim)) ? WINO_OOB : vp;
-                store16(o, rp, vp_s, (uint32_t)(2 * r) * ppx_bytes + (uint32_t)a2 * prow_bytes);
+                wino_store16(o, rp, vp_s, (uint32_t)(2 * r) * ppx_bytes + (uint32_t)a2 * prow_bytes);
             }
         }
     });
@@ -516,54 +496,10 @@ __device__ __forceinline__ void wino4_epilogue_head(const ConvArgs& a, const f32
 __host__ __device__ constexpr int wino4_row_of(int k) { return k == 0 ? 0 : k == 1 ? 5 : k - 1; }
 __host__ __device__ constexpr int wino4_pos_of(int q) { return 6 * wino4_row_of(q / 6) + q % 6; }
 
-// VAR: timing ablations for tools/wino4_check.py (wrong results): bit 0 no LDS-DMA inside the chunks, bit 1 no epilogue, bit 2 no
-// input transform, bit 3 no chunk barrier
-#ifdef RCU_WINO4_ABLATIONS
-// VAR bits 8..10: epilogue ablations (EV of wino4_epilogue); bit 7: s_memtime per tile and wave (tile start, chunks done, epilogue
-// done, vmcnt(0), barrier, first fragments read) -- kept in a type that is empty for the other variants, so that they compile to what
-// they would be without it (the kernel sits at 500 of 512 registers: a dead variable is enough to make hipcc spill)
-__device__ uint64_t g_w4_trace[256 * 4 * 4 * 8];
-extern "C" __attribute__((visibility("default"))) int rcu_debug_w4_trace(uint64_t* dst)   // copies the trace out and clears it
-{
-    void* p = nullptr;
-    hipError_t e = hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_w4_trace), sizeof(g_w4_trace));
-    if (e == hipSuccess) e = hipGetSymbolAddress(&p, HIP_SYMBOL(g_w4_trace));
-    if (e == hipSuccess) e = hipMemset(p, 0, sizeof(g_w4_trace));
-    return (int)e;
-}
-template <bool ON>
-struct Wino4Trace {
-    uint32_t t[8];   // 0 tile start, 1 chunks done, 2 epilogue done, 3 vmcnt(0), 4 barrier, 5 first fragments read, 6 / 7 end of the tile's chunk 0 / 1
-    __device__ __forceinline__ void mark(int i) { t[i] = (uint32_t)__builtin_amdgcn_s_memtime(); }
-    __device__ __forceinline__ void flush(int item, int wave, int lane)
-    {
-        const int k = (item - (int)blockIdx.x) / (int)gridDim.x;   // the workgroup's k-th tile
-        if (lane == 0 && k < 4) {
-            uint64_t* o = g_w4_trace + (((size_t)blockIdx.x * 4 + wave) * 4 + k) * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = (1u << 30) + (t[i] - t[0]);
-        }
-        t[0] = t[5];
-    }
-};
-template <>
-struct Wino4Trace<false> {
-    __device__ __forceinline__ void mark(int) {}
-    __device__ __forceinline__ void flush(int, int, int) {}
-};
-#define WINO4_TRACE_DECL Wino4Trace<(VAR & 128) != 0> w4trace
-#define WINO4_TRACE_MARK(i) w4trace.mark(i)
-#define WINO4_TRACE_FLUSH() w4trace.flush(item, wave, lane)
-#else
-#define WINO4_TRACE_DECL
-#define WINO4_TRACE_MARK(i)
-#define WINO4_TRACE_FLUSH()
-#endif
-
 // HEAD: the classifier head in the epilogue (wino4_epilogue_head).  total_items counts the tiles of ONE pass; the workgroup that owns a tile runs
 // the tile of every pass of the group back to back (sample n0 + pass * head_images), so the passes' read-modify-writes of a voxel's statistics
 // are ordered (pass 0 first, as head_kernel adds them) -- as rcu_wino.hip.
-template <class T, int VAR = 0, bool HEAD = false, bool PART = false>
+template <class T, bool HEAD = false, bool PART = false>
 __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, const int total_items)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -655,7 +591,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
             constexpr int j = I;
             if ((j + 1) * T::WAVES <= T::A_PIECES || j * T::WAVES + wave < T::A_PIECES)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(job.rs, (lds_ptr_t)(uintptr_t)(lds_base + job.lb + (j * T::WAVES + wave) * 1024), 16, off[j],
-                                                         job.cb, 0, RCU_DMA_IN_AUX);
+                                                         job.cb, 0, 0);
         } else if constexpr (I < T::NW + T::NA) {
             constexpr int k = I - T::NA;
             if ((k + 1) * T::WAVES <= T::W_PIECES || k * T::WAVES + wave < T::W_PIECES)
@@ -798,7 +734,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
         // back part (behind the barrier): the first pieces of the chunk after that into THIS chunk's buffer, which the barrier frees
         const DmaJob job = dma_job(dp_wtile, more ? kc + 1 : 0, BUF ^ 1, more || has_next);
         const DmaJob jobb = dma_job(dpn_wtile, more2 ? kc + 2 : kc + 2 - nchunks, BUF, more2 || has_next);
-        if constexpr ((VAR & 4) == 0) transform_head(d);
+        transform_head(d);
         wino_static_for<0, 18>([&](auto g_c) {
             constexpr int G = decltype(g_c)::value;
             constexpr int p0 = wino4_pos_of(2 * G), p1 = wino4_pos_of(2 * G + 1);
@@ -806,16 +742,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
             if constexpr (G == NPRE) {
                 // behind a tile's last chunk the wait comes after the epilogue (main loop): the first chunk of the next tile is a
                 // cold fetch, and the epilogue is the work to hide it behind
-                if constexpr ((VAR & 8) == 0) {
-                    // vmcnt(0): this wave's pieces of the next chunk (the next tile's first chunk behind a tile's last) have landed.
-                    // INVARIANT the two-chunks-ahead LDS-DMA relies on: when a wave leaves __syncthreads(), every LDS read any wave has issued
-                    // from buffer BUF is COMPLETE -- __syncthreads() lowers to `s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier` (checked in the gfx950
-                    // assembly of every in-loop barrier), and the weights of groups 14..17 were read in groups 10..13 -- so the back-part DMA issued
-                    // right behind it may overwrite BUF.  A bare __builtin_amdgcn_s_barrier() here would be a write-after-read race on BUF; if
-                    // the barrier is ever hand-rolled it needs an explicit s_waitcnt lgkmcnt(0) in front.
-                    __builtin_amdgcn_s_waitcnt(0x0F70);
-                    __syncthreads();   // everyone past the LDS reads of buffer BUF and done filling the other one
-                }
+                // vmcnt(0): this wave's pieces of the next chunk (the next tile's first chunk behind a tile's last) have landed.
+                // INVARIANT the two-chunks-ahead LDS-DMA relies on: when a wave leaves __syncthreads(), every LDS read any wave has issued
+                // from buffer BUF is COMPLETE -- __syncthreads() lowers to `s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier` (checked in the gfx950
+                // assembly of every in-loop barrier), and the weights of groups 14..17 were read in groups 10..13 -- so the back-part DMA issued
+                // right behind it may overwrite BUF.  A bare __builtin_amdgcn_s_barrier() here would be a write-after-read race on BUF; if
+                // the barrier is ever hand-rolled it needs an explicit s_waitcnt lgkmcnt(0) in front.
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+                __syncthreads();   // everyone past the LDS reads of buffer BUF and done filling the other one
                 __builtin_amdgcn_sched_barrier(0);
             }
             // what goes between the 8 MFMAs of the group: unit u follows MFMA u
@@ -831,9 +765,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
                         constexpr int q = 2 * NPRE + 2 * (G - (NPRE - 4)) + (U == 6 ? 1 : 0);
                         load_weights(bv, Ab, wino4_pos_of(q));
                     }
-                    if constexpr ((VAR & 1) == 0 && G < 10 && (U == 1 || U == 5)) dma_piece(job, dp, std::integral_constant<int, PB + 2 * G + (U == 5 ? 1 : 0)>{});
+                    if constexpr (G < 10 && (U == 1 || U == 5)) dma_piece(job, dp, std::integral_constant<int, PB + 2 * G + (U == 5 ? 1 : 0)>{});
                 } else {
-                    if constexpr ((VAR & 1) == 0 && (U == 1 || U == 5) && 2 * (G - NPRE) + (U == 5 ? 1 : 0) < PB)
+                    if constexpr ((U == 1 || U == 5) && 2 * (G - NPRE) + (U == 5 ? 1 : 0) < PB)
                         dma_piece(jobb, dpn, std::integral_constant<int, 2 * (G - NPRE) + (U == 5 ? 1 : 0)>{});
                     // behind the barrier: the raw patch of the next chunk (rows 0, 2, 4, 1, 3, 5) and its first weights.  Unconditional
                     // (a conditional load would keep the old contents of dn alive through the whole chunk); in a tile's last
@@ -852,31 +786,25 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            wino4_mfma<0, p0, FIRST, true, (VAR & 16) != 0>(accv, d[p0].x, bv[p0].x);
+            wino4_mfma<0, p0, FIRST>(accv, d[p0].x, bv[p0].x);
             filler(std::integral_constant<int, 0>{});
-            wino4_mfma<1, p0, FIRST, true, (VAR & 16) != 0>(accv, d[p0].x, bv[p0].z);
+            wino4_mfma<1, p0, FIRST>(accv, d[p0].x, bv[p0].z);
             filler(std::integral_constant<int, 1>{});
-            wino4_mfma<0, p1, FIRST, true, (VAR & 16) != 0>(accv, d[p1].x, bv[p1].x);
+            wino4_mfma<0, p1, FIRST>(accv, d[p1].x, bv[p1].x);
             filler(std::integral_constant<int, 2>{});
-            wino4_mfma<1, p1, FIRST, true, (VAR & 16) != 0>(accv, d[p1].x, bv[p1].z);
+            wino4_mfma<1, p1, FIRST>(accv, d[p1].x, bv[p1].z);
             filler(std::integral_constant<int, 3>{});
-            wino4_mfma<0, p0, false, true, (VAR & 16) != 0>(accv, d[p0].y, bv[p0].y);
+            wino4_mfma<0, p0, false>(accv, d[p0].y, bv[p0].y);
             filler(std::integral_constant<int, 4>{});
-            wino4_mfma<1, p0, false, true, (VAR & 16) != 0>(accv, d[p0].y, bv[p0].w);
+            wino4_mfma<1, p0, false>(accv, d[p0].y, bv[p0].w);
             filler(std::integral_constant<int, 5>{});
-            wino4_mfma<0, p1, false, true, (VAR & 16) != 0>(accv, d[p1].y, bv[p1].y);
+            wino4_mfma<0, p1, false>(accv, d[p1].y, bv[p1].y);
             filler(std::integral_constant<int, 6>{});
-            wino4_mfma<1, p1, false, true, (VAR & 16) != 0>(accv, d[p1].y, bv[p1].w);
+            wino4_mfma<1, p1, false>(accv, d[p1].y, bv[p1].w);
             filler(std::integral_constant<int, 7>{});
             // transform work for the coming position rows: one clump
-            if constexpr ((VAR & 4) == 0) transform_clump(d, G);
+            transform_clump(d, G);
         });
-        if constexpr ((VAR & 64) != 0) {   // probe: read the next chunk's patch and first weights again behind the chunk
-            __syncthreads();
-#pragma unroll
-            for (int ii = 0; ii < 6; ++ii) load_patch_row(dn, An, ii);
-            wino_static_for<0, AHEAD>([&](auto q_c) { load_weights(bvn, An, wino4_pos_of(decltype(q_c)::value)); });
-        }
     };
 
     f32x2 dA[36], dB[36];
@@ -888,38 +816,21 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
         wino_static_for<0, AHEAD>([&](auto q_c) { load_weights(bvA, smem, wino4_pos_of(decltype(q_c)::value)); });
     };
     load_first();
-    WINO4_TRACE_DECL;
-    WINO4_TRACE_MARK(0);
 
     for (;;) {
-        if constexpr ((VAR & 32) != 0) {   // probe (wrong results): no zero-accumulator form of the tile's first chunk -- two copies of the chunk code instead of four
-            for (int kc = 0; kc < nchunks; kc += 2) {
-                chunk(std::integral_constant<int, 0>{}, std::false_type{}, kc, dA, dB, bvA, bvB);
-                chunk(std::integral_constant<int, 1>{}, std::false_type{}, kc + 1, dB, dA, bvB, bvA);
-            }
-        } else {
         chunk(std::integral_constant<int, 0>{}, std::true_type{}, 0, dA, dB, bvA, bvB);
-        WINO4_TRACE_MARK(6);
         chunk(std::integral_constant<int, 1>{}, std::false_type{}, 1, dB, dA, bvB, bvA);
-        WINO4_TRACE_MARK(7);
         for (int kc = 2; kc < nchunks; kc += 2) {
             chunk(std::integral_constant<int, 0>{}, std::false_type{}, kc, dA, dB, bvA, bvB);
             chunk(std::integral_constant<int, 1>{}, std::false_type{}, kc + 1, dB, dA, bvB, bvA);
         }
-        }
-        WINO4_TRACE_MARK(1);
         if constexpr (HEAD)
             wino4_epilogue_head<T, PART>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.n0, tile.n0 - pass * wino_cold_args().head_images, tile.y0, tile.x0,
                                          wave, lane, lds_base + (uint32_t)(T::BUF_DW + T::A_DW) * 4u, lds_base + (uint32_t)(2 * T::BUF_DW) * 4u);
-        else if constexpr ((VAR & 2) == 0)
-            wino4_epilogue<T, (VAR >> 8), PART>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.wtile, tile.n0, tile.y0, tile.x0, wave, lane, store_plan);
-        WINO4_TRACE_MARK(2);
+        else
+            wino4_epilogue<T, PART>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.wtile, tile.n0, tile.y0, tile.x0, wave, lane, store_plan);
         if (!has_next) break;
-        WINO4_TRACE_MARK(3);   // (no wait and no barrier here any more: the tile's last chunk waited for the next tile's first chunk at its barrier)
-        WINO4_TRACE_MARK(4);
-        load_first();
-        WINO4_TRACE_MARK(5);
-        WINO4_TRACE_FLUSH();
+        load_first();   // (no wait and no barrier here any more: the tile's last chunk waited for the next tile's first chunk at its barrier)
         if (more_passes()) {
             ++pass;
         } else {
@@ -954,17 +865,17 @@ static const ConvConfigInfo kWino4Info[6] = {
 
 const ConvConfigInfo& wino4_config_info(int cfg) { return kWino4Info[cfg - CONV_CFG_WINO4_T32x32_N32]; }
 
-template <class T, int VAR, bool HEAD = false, bool PART = false>
-static hipError_t launch_wino4_var(const ConvArgs& a, hipStream_t stream)
+template <class T, bool HEAD, bool PART>
+static hipError_t launch_wino4_kernel(const ConvArgs& a, hipStream_t stream)
 {
     constexpr int lds_bytes = T::LDS_BYTES + (HEAD ? WINO4_HEAD_LDS_BYTES : 0);
     static_assert(lds_bytes <= 160 * 1024, "LDS");
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino4_stream<T, VAR, HEAD, PART>), lds_bytes);
+    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino4_stream<T, HEAD, PART>), lds_bytes);
     if (e != hipSuccess) return e;
     // HEAD: the work items of one pass (TS == 1: a slice group is a sample); the kernel runs every pass of the group on each
     const unsigned items = (unsigned)a.NT * a.tiles_x * a.tiles_y * (HEAD ? a.head_images : a.slice_groups);
     const unsigned grid = wino_persistent_grid(items);
-    hipLaunchKernelGGL((conv_wino4_stream<T, VAR, HEAD, PART>), dim3(grid), dim3(T::THREADS), lds_bytes, stream, a, (int)items);
+    hipLaunchKernelGGL((conv_wino4_stream<T, HEAD, PART>), dim3(grid), dim3(T::THREADS), lds_bytes, stream, a, (int)items);
     return hipGetLastError();
 }
 
@@ -985,35 +896,8 @@ static hipError_t launch_wino4_cfg(const ConvArgs& a, hipStream_t stream)
                    (size_t)a.N * a.out_H * a.out_W * a.CoutP * 4 >= ((size_t)1 << 31) ||
                    (a.pooled != nullptr && (a.pool_H < (a.Hr >> 1) || a.pool_W < (a.Wr >> 1)))))
         return hipErrorInvalidValue;
-#ifdef RCU_WINO4_ABLATIONS   // timing experiments of tools/wino4_check.py (make EXTRA=-DRCU_WINO4_ABLATIONS); results are wrong
-    const char* const v = HEAD ? nullptr : getenv("RCU_W4_VARIANT");
-    switch (v ? atoi(v) : 0) {
-        case 1: return launch_wino4_var<T, 1>(a, stream);
-        case 2: return launch_wino4_var<T, 2>(a, stream);
-        case 3: return launch_wino4_var<T, 3>(a, stream);
-        case 4: return launch_wino4_var<T, 4>(a, stream);
-        case 5: return launch_wino4_var<T, 5>(a, stream);
-        case 6: return launch_wino4_var<T, 6>(a, stream);
-        case 7: return launch_wino4_var<T, 7>(a, stream);
-        case 8: return launch_wino4_var<T, 8>(a, stream);
-        case 11: return launch_wino4_var<T, 11>(a, stream);
-        case 15: return launch_wino4_var<T, 15>(a, stream);
-        case 16: return launch_wino4_var<T, 16>(a, stream);
-        case 64: return launch_wino4_var<T, 64>(a, stream);
-        case 128: return launch_wino4_var<T, 128>(a, stream);
-        case 128 + 32: return launch_wino4_var<T, 128 + 32>(a, stream);
-        case 256: return launch_wino4_var<T, 256>(a, stream);
-        case 512: return launch_wino4_var<T, 512>(a, stream);
-        case 1024: return launch_wino4_var<T, 1024>(a, stream);
-        case 128 + 256: return launch_wino4_var<T, 128 + 256>(a, stream);
-        case 128 + 512: return launch_wino4_var<T, 128 + 512>(a, stream);
-        case 128 + 1024: return launch_wino4_var<T, 128 + 1024>(a, stream);
-        case 128 + 1024 + 512: return launch_wino4_var<T, 128 + 1024 + 512>(a, stream);
-        default: break;
-    }
-#endif
-    if (a.part) return launch_wino4_var<T, 0, HEAD, true>(a, stream);
-    return launch_wino4_var<T, 0, HEAD>(a, stream);
+    if (a.part) return launch_wino4_kernel<T, HEAD, true>(a, stream);
+    return launch_wino4_kernel<T, HEAD, false>(a, stream);
 }
 
 hipError_t launch_conv_wino4(int cfg, const ConvArgs& a, hipStream_t stream)

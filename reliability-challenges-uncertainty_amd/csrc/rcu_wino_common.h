@@ -1,7 +1,6 @@
 // Shared pieces of the Winograd kernels (rcu_wino.hip: F(2x2,3x3) conv unit; rcu_wino_up.hip: F(2x2,2x2) sub-pixel
 // up-convolution): tile geometry, LDS-DMA staging plan, epilogue constants.  gfx950 only.
 #pragma once
-#include <cstdlib>
 #include "rcu_kernels.h"
 
 #include <type_traits>
@@ -12,12 +11,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// Cache policy of the LDS-DMA loads of INPUT activations (the aux immediate of buffer_load ... lds: 1 sc0, 2 nt, 16 sc1).  0 = cached; experiment builds set
-// it (profiles/r04_nt_loads.txt).
-#ifndef RCU_DMA_IN_AUX
-#define RCU_DMA_IN_AUX 0
-#endif
 
 // Exchange with the neighbouring lane (lane ^ 1): DPP quad_perm [1,0,3,2].
 __device__ __forceinline__ float wino_swap_adjacent(float v)
@@ -42,10 +35,7 @@ __device__ __forceinline__ const ConvArgs& wino_cold_args()
 // pixels, different ones per run).  Two wait states, pinned right behind the store.
 __device__ __forceinline__ void wino_store16(const f32x4& v, __amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff)
 {
-#ifndef RCU_STORE_AUX
-#define RCU_STORE_AUX 0
-#endif
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, soff, RCU_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, soff, 0);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_nop 1");
     __builtin_amdgcn_sched_barrier(0);
@@ -205,25 +195,15 @@ __device__ __forceinline__ WinoTileId wino_tile_id(const A& a, int item)
 // buffer load returns zeros.  The tile-independent part -- which (channel half, slice, halo row, pixel column) the slot
 // holds -- is packed into one register per slot at kernel start (wino_slot_geometry).
 // The LDS input image of the F(2x2,3x3) / F(2x2,2x2) kernels is [channel half][slice][halo row][position][4 channels]: the patch reads
-// (ds_read_b64: 32 lanes per cycle over 64 banks) are free of bank conflicts on it.  -DRCU_WINO_IMAGE8=1 (experiment builds) stages
-// rcu_wino4.hip's image [slice][halo row][position][8 channels] instead -- adjacent lanes of an LDS-DMA instruction fetch the two 16-byte
-// halves of one pixel's chunk, so an instruction touches 8 whole 128-byte lines of a channel-blocked tensor instead of 16 half lines --
-// at the price of 2-way conflicts on the patch reads (16 tiles x 2 channel pairs cannot fall on 16 distinct 16-byte slots without a
-// per-column half swizzle).  Measured round 4 (profiles/r04_layout_ab.txt): every one of the seven layers 0..+2.8 % SLOWER, 2.17 -> 2.19 ms
-// per 160-slice forward, the headline unchanged: the halved L2 requests do not pay for the conflicts with two waves per SIMD.  Not the default.
-#ifndef RCU_WINO_IMAGE8
-#define RCU_WINO_IMAGE8 0
-#endif
-constexpr int WINO_POS_DW = RCU_WINO_IMAGE8 ? 8 : 4;   // dwords from one position of the input image to the next
+// (ds_read_b64: 32 lanes per cycle over 64 banks) are free of bank conflicts on it.  rcu_wino4.hip's image [slice][halo row][position][8 channels]
+// halves the L2 requests of the LDS-DMA but puts 2-way conflicts on the patch reads: measured here (profiles/r04_layout_ab.txt) every one of the
+// seven layers was 0..+2.8 % slower with it, the headline unchanged -- the halved requests do not pay for the conflicts with two waves per SIMD.
+constexpr int WINO_POS_DW = 4;   // dwords from one position of the input image to the next
 template <class T>
 __device__ __forceinline__ uint32_t wino_slot_geometry(int j, int wave, int lane)
 {
     const int f = (j * T::WAVES + wave) * 64 + lane;       // 16-byte unit of the LDS image
-#if RCU_WINO_IMAGE8
-    const int hh = f & 1, rem = f >> 1;
-#else
     const int hh = f / T::HALF_POS, rem = f % T::HALF_POS;
-#endif
     const int s = rem / T::SLICE_POS, r2 = rem % T::SLICE_POS;
     const int yy = r2 / T::PITCH, pos = r2 % T::PITCH;
     const int x = pos ^ ((yy >> 1) & 1);                    // pixel column stored at this position
@@ -267,19 +247,10 @@ __device__ __forceinline__ uint32_t wino_slot_offset(uint32_t plan, const WinoTi
     return (plan & t.border) != 0u ? WINO_OOB : ((plan + t.off) & ~15u);
 }
 
-// workgroups of a persistent Winograd kernel: one per CU (experiment builds, -DRCU_EXPERIMENTS: RCU_PERSISTENT_GRID overrides it --
-// kernels of two streams side by side)
+// workgroups of a persistent Winograd kernel: one per CU
 inline unsigned wino_persistent_grid(unsigned items)
 {
-#ifdef RCU_EXPERIMENTS
-    static const unsigned cap = [] {
-        const char* const v = getenv("RCU_PERSISTENT_GRID");
-        const int n = v ? atoi(v) : 0;
-        return n > 0 ? (unsigned)n : 256u;
-    }();
-#else
     constexpr unsigned cap = 256u;
-#endif
     return items < cap ? items : cap;
 }
 

@@ -18,8 +18,6 @@
 // mapping and the streaming pipeline are those of rcu_wino.hip; see there.
 #include "rcu_wino_common.h"
 
-#include <cstdlib>
-
 namespace rcu {
 
 // Output transform + epilogue.  acc[blk][p][r]; the lane's tile r of class (pa, b) yields the output pixels
@@ -118,15 +116,9 @@ __global__ __launch_bounds__(512, 1) void upconv_wino_stream(const ConvArgs a, c
 #pragma unroll
         for (int i2 = 0; i2 < 2; ++i2) {
             const int yy = yy0 + 2 * i2, swz = (yy >> 1) & 1;
-#if RCU_WINO_IMAGE8
-            const int rowbase = (sl * T::SLICE_POS + yy * T::PITCH) * 8 + kq * 2;   // [slice][row][position][8 channels]
-            aA[i2] = rowbase + 8 * (x0l + swz);
-            aB[i2] = rowbase + 8 * (x0l - swz);
-#else
             const int rowbase = ((kq >> 1) * T::HALF_POS + sl * T::SLICE_POS + yy * T::PITCH) * 4 + (kq & 1) * 2;
             aA[i2] = rowbase + 4 * (x0l + swz);
             aB[i2] = rowbase + 4 * (x0l - swz);
-#endif
         }
     }
     const int b_addr = T::A_DW + (kq * T::BN + wn * 32 + 2 * m16) * 2;
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void upconv_wino_stream(const ConvArgs a, c
             constexpr int j = I - T::NW;
             if (job.active && ((j + 1) * T::WAVES <= T::A_PIECES || j * T::WAVES + wave < T::A_PIECES))
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr_t)(uintptr_t)(lds_base + job.lb + (j * T::WAVES + wave) * 1024), 16, dp[j],
-                                                         job.cb, 0, RCU_DMA_IN_AUX);
+                                                         job.cb, 0, 0);
         }
     };
 
