@@ -782,6 +782,47 @@ size_t rcu_corrupt_workspace_bytes(size_t n, int channels, int height, int width
 int rcu_corrupt(const float* x_dev, size_t n, int channels, int height, int width, int kind, double amount, uint64_t key, uint64_t first_sample,
                 const float* aux_host, int n_aux, float* out_dev, void* workspace_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adaptive MC (EXTENSION: the reference runs T passes over every slice; rcu_amd.steps.McPredictStep(adaptive=...), rcu_amd.steps.AdaptiveMcStatistics
+ * and the `others.mc_adaptive` key of the two default test scripts)
+ *   Slices on which more passes cannot change the answer are retired at pass checkpoints and finalised from the passes they have seen.  Opt-in and
+ *   approximate by design; without the key nothing changes.
+ *   Schedule: checkpoints t_1 < t_2 < ... (at most RCU_ADAPTIVE_MAX_CHECKPOINTS, 2 <= t_1, the last below T), a tolerance 0 <= eps < 1 and
+ *   max_unsettled >= 0; nb_classes >= 2.  At checkpoint t, with S_c(v) the RCU_MC_EXACT sum of p_c(v) over the t passes a still-active slice has seen
+ *   (a multiple of 2^-40 below 2^13: S_c * 2^40 is an integer float64 holds exactly),
+ *     voxel v is SETTLED    iff  (int64)(max_c S_c(v) * 2^40) >= thr_q,
+ *     thr_q = ceil((1.0 - eps) * t * 2^40), computed by the HOST in exact rational arithmetic on the float64 value of 1.0 - eps
+ *             (rcu_amd.steps.adaptive_threshold; tests/adaptive_reference.py) and passed as an int64 -- nothing on the device rounds;
+ *     in words: the mean probability of the leading class over the t passes is at least 1 - eps;
+ *     a slice is RETIRED at t iff its number of unsettled voxels is <= max_unsettled.  It keeps the statistics of its t passes and is finalised with
+ *     count t; the other slices go on to pass t + 1, and after the last checkpoint to T.
+ *   The decision is a comparison of integers that are exact sums: it cannot depend on the pass groups, the stream lanes, the batch a slice arrives in
+ *   or the geometry of the launch that scores it.  Pass j keeps its mask key whatever span it runs in, and the masks are keyed by the slice's global
+ *   index (rcu_dropout_masks), so a slice moved into a smaller batch keeps its samples.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_ADAPTIVE_MAX_CHECKPOINTS 4
+/* Per slice i of an RCU_MC_EXACT blob (flags without RCU_MC_EXACT are refused: RCU_ERR_INVALID): unsettled_dev[i] = the number of voxels with
+ * (int64)(max_c S_c * 2^40) < thr_q, margin_q_dev[i] = the minimum of that integer over the slice.  Reads the nb_classes class-sum planes once
+ * (8 * nb_classes bytes per voxel), 16 bytes per lane where hw is even and the blob is 16-byte aligned, one value otherwise -- the same integers
+ * either way.  Reduction: in-wave, one LDS step per workgroup, one 32-bit integer add and one 64-bit integer min per workgroup and slice.
+ * n <= 2^20, hw <= 2^30, thr_q >= 0. */
+int rcu_mc_slice_scores(const void* stats_dev, size_t n, size_t hw, int nb_classes, int flags, int64_t thr_q, uint32_t* unsettled_dev,
+                        int64_t* margin_q_dev, void* stream);
+/* rcu_dropout_masks with a DEVICE array of n global sample indices in place of first_sample: row i of every pass is drawn at the counter of sample
+ * sample_index_dev[i] (>= 0) -- bit for bit the row of that sample in a contiguous draw that covers it.  Same output layout. */
+int rcu_dropout_masks_indexed(const uint64_t* seeds_host, int passes, int n, const int64_t* sample_index_dev, const int32_t* site_channels_host,
+                              const float* site_keep_host, int n_sites, float* out_dev, void* stream);
+/* A compact blob of m slices added into a blob of n slices (same hw, nb_classes, flags): for every plane
+ * dst[plane * n*hw + index[i]*hw + pix] += src[plane * m*hw + i*hw + pix].  An entry index[i] < 0 (or >= n) is skipped.  The other entries of a call
+ * MUST be distinct: there are no atomics, and the entry point cannot check a device array cheaply.  With RCU_MC_EXACT the additions are exact, so the
+ * order of merges is irrelevant.  Moves are 16 bytes where hw and the blobs' alignment allow.  src and dst must not overlap. */
+int rcu_mc_merge_slices(const void* src_stats_dev, size_t m, void* dst_stats_dev, size_t n, size_t hw, int nb_classes, int flags,
+                        const int32_t* index_dev, void* stream);
+/* rcu_mc_finalize with the pass count of slice i read from counts_dev[i] (DEVICE array of n entries, each >= 1; >= 2 for the variance; not checked)
+ * in place of T: the same arithmetic per voxel, so with all counts equal to T it writes the bits rcu_mc_finalize writes. */
+int rcu_mc_finalize_counts(const void* stats_dev, size_t n, size_t hw, int nb_classes, const int32_t* counts_dev, int flags, float* mean_dev,
+                           float* entropy_dev, float* mutual_info_dev, float* variance_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

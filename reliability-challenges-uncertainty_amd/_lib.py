@@ -33,6 +33,8 @@ RCU_TEMPERATURE_MAX_CANDIDATES = 128
 RCU_LOGIT_MAX_SAMPLES = 1024
 # sample agreement (include/rcu.h): passes a vote plane holds (32 per uint32 word)
 RCU_VOTES_MAX_PASSES = 64
+# adaptive MC (include/rcu.h): checkpoints of a schedule
+RCU_ADAPTIVE_MAX_CHECKPOINTS = 4
 # patch-level uncertainty (include/rcu.h): the largest extent of a patch along an axis
 RCU_PATCH_MAX_EXTENT = 16
 # input corruptions (include/rcu.h): code -> name of the kinds of rcu_corrupt
@@ -177,6 +179,10 @@ SIGNATURES = {
     'rcu_corrupt_workspace_bytes': (c_size_t, [c_size_t, c_int, c_int, c_int, c_int]),
     'rcu_corrupt': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint64, POINTER(c_float), c_int, c_void_p, c_void_p,
                             c_void_p]),
+    'rcu_mc_slice_scores': (c_int, [c_void_p, c_size_t, c_size_t, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'rcu_dropout_masks_indexed': (c_int, [POINTER(c_uint64), c_int, c_int, c_void_p, POINTER(c_int32), POINTER(c_float), c_int, c_void_p, c_void_p]),
+    'rcu_mc_merge_slices': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    'rcu_mc_finalize_counts': (c_int, [c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1410,18 +1410,18 @@ extern "C" int rcu_prediction_and_foreground(const float* probs, size_t n, size_
     return RCU_OK;
 }
 
-extern "C" int rcu_dropout_masks(const uint64_t* seeds, int passes, int n, uint64_t first_sample, const int32_t* site_channels,
-                                 const float* site_keep, int n_sites, float* out, void* stream)
+// The two mask draws: the site table is checked and laid out once; sample_index_dev == nullptr draws at first_sample + i
+static int draw_dropout_masks(const std::string& fn, const uint64_t* seeds, int passes, int n, uint64_t first_sample, const int64_t* sample_index_dev,
+                              const int32_t* site_channels, const float* site_keep, int n_sites, float* out, void* stream)
 {
-    if (!seeds || !site_channels || !site_keep || !out) return fail(RCU_ERR_INVALID, "rcu_dropout_masks: null argument");
-    if (passes < 1 || n < 1 || n_sites < 1 || n_sites > MASK_MAX_SITES)
-        return fail(RCU_ERR_INVALID, "rcu_dropout_masks: passes, n >= 1 and 1 <= n_sites <= 40");
+    if (!seeds || !site_channels || !site_keep || !out) return fail(RCU_ERR_INVALID, fn + ": null argument");
+    if (passes < 1 || n < 1 || n_sites < 1 || n_sites > MASK_MAX_SITES) return fail(RCU_ERR_INVALID, fn + ": passes, n >= 1 and 1 <= n_sites <= 40");
     MaskArgs a{};
     long end = 0;
     for (int s = 0; s < n_sites; ++s) {
-        if (site_channels[s] < 1 || !(site_keep[s] <= 1.f)) return fail(RCU_ERR_INVALID, "rcu_dropout_masks: site_channels >= 1, site_keep <= 1");
+        if (site_channels[s] < 1 || !(site_keep[s] <= 1.f)) return fail(RCU_ERR_INVALID, fn + ": site_channels >= 1, site_keep <= 1");
         end += (long)n * site_channels[s];
-        if (end * (long)passes >= (1l << 31)) return fail(RCU_ERR_INVALID, "rcu_dropout_masks: more than 2^31 factors");
+        if (end * (long)passes >= (1l << 31)) return fail(RCU_ERR_INVALID, fn + ": more than 2^31 factors");
         a.site_end[s] = (int)end;
         a.site_keep[s] = site_keep[s];
         a.site_ch[s] = site_channels[s];
@@ -1436,8 +1436,81 @@ extern "C" int rcu_dropout_masks(const uint64_t* seeds, int passes, int n, uint6
     for (a.first = 0; a.first < passes; a.first += MASK_MAX_PASSES) {
         a.count = std::min(MASK_MAX_PASSES, passes - a.first);
         for (int t = 0; t < a.count; ++t) a.seed[t] = seeds[a.first + t];
-        RCU_HIP(launch_dropout_masks(a, out, static_cast<hipStream_t>(stream)));
+        if (sample_index_dev) {
+            RCU_HIP(launch_dropout_masks_indexed(a, reinterpret_cast<const long long*>(sample_index_dev), out, static_cast<hipStream_t>(stream)));
+        } else {
+            RCU_HIP(launch_dropout_masks(a, out, static_cast<hipStream_t>(stream)));
+        }
     }
+    return RCU_OK;
+}
+
+extern "C" int rcu_dropout_masks(const uint64_t* seeds, int passes, int n, uint64_t first_sample, const int32_t* site_channels,
+                                 const float* site_keep, int n_sites, float* out, void* stream)
+{
+    return draw_dropout_masks("rcu_dropout_masks", seeds, passes, n, first_sample, nullptr, site_channels, site_keep, n_sites, out, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// adaptive MC (kernels: rcu_adaptive.hip)
+// ------------------------------------------------------------------------------------------------
+// slices of hw voxels whose rows, row blocks and voxel quads stay inside the kernels' 32-bit indices
+static int check_adaptive_shape(const char* fn, size_t n, size_t hw, int C)
+{
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n < 1 || hw < 1 || n > ((size_t)1 << 20) || hw > ((size_t)1 << 30))
+        return fail(RCU_ERR_INVALID, std::string(fn) + ": n must be in 1..2^20 and hw in 1..2^30");
+    return RCU_OK;
+}
+
+extern "C" int rcu_mc_slice_scores(const void* stats_dev, size_t n, size_t hw, int C, int flags, int64_t thr_q, uint32_t* unsettled_dev,
+                                   int64_t* margin_q_dev, void* stream)
+{
+    if (!stats_dev || !unsettled_dev || !margin_q_dev) return fail(RCU_ERR_INVALID, "rcu_mc_slice_scores: null argument");
+    if (check_adaptive_shape("rcu_mc_slice_scores", n, hw, C)) return RCU_ERR_INVALID;
+    if (!(flags & RCU_MC_EXACT) || (flags & ~(RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT)))
+        return fail(RCU_ERR_INVALID, "rcu_mc_slice_scores: needs RCU_MC_EXACT statistics (the decision is made on exact integer sums), got flags " +
+                                         std::to_string(flags));
+    if (thr_q < 0) return fail(RCU_ERR_INVALID, "rcu_mc_slice_scores: thr_q must be >= 0");
+    if (reinterpret_cast<uintptr_t>(stats_dev) % 8 != 0) return fail(RCU_ERR_INVALID, "rcu_mc_slice_scores: stats must be 8-byte aligned");
+    RCU_HIP(launch_mc_slice_scores(stats_dev, C, n, hw, (long long)thr_q, unsettled_dev, reinterpret_cast<long long*>(margin_q_dev),
+                                   static_cast<hipStream_t>(stream)));
+    return RCU_OK;
+}
+
+extern "C" int rcu_dropout_masks_indexed(const uint64_t* seeds, int passes, int n, const int64_t* sample_index_dev, const int32_t* site_channels,
+                                         const float* site_keep, int n_sites, float* out, void* stream)
+{
+    if (!sample_index_dev) return fail(RCU_ERR_INVALID, "rcu_dropout_masks_indexed: null argument");
+    return draw_dropout_masks("rcu_dropout_masks_indexed", seeds, passes, n, 0, sample_index_dev, site_channels, site_keep, n_sites, out, stream);
+}
+
+extern "C" int rcu_mc_merge_slices(const void* src_stats_dev, size_t m, void* dst_stats_dev, size_t n, size_t hw, int C, int flags,
+                                   const int32_t* index_dev, void* stream)
+{
+    if (!src_stats_dev || !dst_stats_dev || !index_dev) return fail(RCU_ERR_INVALID, "rcu_mc_merge_slices: null argument");
+    if (check_adaptive_shape("rcu_mc_merge_slices", n, hw, C) || check_adaptive_shape("rcu_mc_merge_slices", m, hw, C)) return RCU_ERR_INVALID;
+    if (flags & ~(RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT))
+        return fail(RCU_ERR_INVALID, "rcu_mc_merge_slices: flags must be a combination of RCU_MC_MI, RCU_MC_VAR and RCU_MC_EXACT, got " +
+                                         std::to_string(flags));
+    const uintptr_t s = reinterpret_cast<uintptr_t>(src_stats_dev), d = reinterpret_cast<uintptr_t>(dst_stats_dev);
+    const size_t element = (flags & (RCU_MC_VAR | RCU_MC_EXACT)) ? 8 : 4;
+    if (s % element != 0 || d % element != 0) return fail(RCU_ERR_INVALID, "rcu_mc_merge_slices: blobs must be aligned to their element");
+    if (s < d + rcu_mc_stats_bytes(n, hw, C, flags) && d < s + rcu_mc_stats_bytes(m, hw, C, flags))
+        return fail(RCU_ERR_INVALID, "rcu_mc_merge_slices: src and dst must not overlap");
+    RCU_HIP(launch_mc_merge_slices(src_stats_dev, m, dst_stats_dev, n, hw, C, flags, index_dev, static_cast<hipStream_t>(stream)));
+    return RCU_OK;
+}
+
+extern "C" int rcu_mc_finalize_counts(const void* stats, size_t n, size_t hw, int C, const int32_t* counts_dev, int flags, float* mean,
+                                      float* entropy, float* mi, float* var, void* stream)
+{
+    if (!stats || !counts_dev) return fail(RCU_ERR_INVALID, "rcu_mc_finalize_counts: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (mi && !(flags & RCU_MC_MI)) return fail(RCU_ERR_INVALID, "mutual_info requested without RCU_MC_MI statistics");
+    if (var && !(flags & RCU_MC_VAR)) return fail(RCU_ERR_INVALID, "variance requested without RCU_MC_VAR statistics");
+    if (n * hw == 0) return RCU_OK;
+    RCU_HIP(launch_mc_finalize_counts(stats, C, n, hw, counts_dev, flags, mean, entropy, mi, var, static_cast<hipStream_t>(stream)));
     return RCU_OK;
 }
 

@@ -325,6 +325,20 @@ struct MaskArgs {
 hipError_t launch_dropout_masks(const MaskArgs& a, float* out, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
+// adaptive MC (rcu_adaptive.hip; include/rcu.h "Adaptive MC")
+// ---------------------------------------------------------------------------------------------
+// float64 statistics only (MC_EXACT): unsettled[i] = #{v in slice i : (int64)(max_c S_c(v) * 2^40) < thr_q}, margin_q[i] = the smallest such integer
+hipError_t launch_mc_slice_scores(const void* stats, int C, size_t N, size_t HW, long long thr_q, uint32_t* unsettled, long long* margin_q,
+                                  hipStream_t stream);
+// launch_dropout_masks with row i drawn at the global sample sample_index[i] (device array of a.site_end[0] / a.site_ch[0] entries); a.first_sample unused
+hipError_t launch_dropout_masks_indexed(const MaskArgs& a, const long long* sample_index, float* out, hipStream_t stream);
+// every plane: dst[plane][index[i]] += src[plane][i], i < M; entries outside [0, N) are skipped; the others must be distinct
+hipError_t launch_mc_merge_slices(const void* src, size_t M, void* dst, size_t N, size_t HW, int C, int flags, const int32_t* index, hipStream_t stream);
+// launch_mc_finalize with T = counts[slice] (device array of N entries >= 1)
+hipError_t launch_mc_finalize_counts(const void* stats, int C, size_t N, size_t HW, const int32_t* counts, int flags, float* mean, float* entropy,
+                                     float* mi, float* var, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
 // calibration kernels (rcu_calib.hip)
 // ---------------------------------------------------------------------------------------------
 constexpr int MAX_BINS = 32;

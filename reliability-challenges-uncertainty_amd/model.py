@@ -310,18 +310,28 @@ class UNet(nn.Module):
             return None
         return chunks[0] if len(chunks) == 1 else torch.cat(chunks)
 
-    def seeded_masks(self, n, device, seeds, first_sample=0):
+    def seeded_masks(self, n, device, seeds, first_sample=0, sample_index=None):
         """The Dropout2d factors of ``len(seeds)`` MC passes over n images, drawn on the device by ONE kernel (include/rcu.h,
         rcu_dropout_masks) on the current stream: the factors of image i in pass t from ``seeds[t]`` and the image's GLOBAL index
         ``first_sample + i`` alone -- the same values whatever batch the image arrives in and whatever group, lane or rank the pass is
         launched in -- in the ``[site][passes * n][C_site]`` layout ``forward_accumulate(..., passes=len(seeds))`` reads (one pass: the layout
-        of ``sample_masks``).  Sites whose Dropout2d is in eval mode get ones, p = 1 zeros, as ``sample_masks`` gives them."""
+        of ``sample_masks``).  Sites whose Dropout2d is in eval mode get ones, p = 1 zeros, as ``sample_masks`` gives them.
+        ``sample_index`` (int64 device tensor ``[n]``, in place of ``first_sample``): image i is the sample with global index ``sample_index[i]``
+        -- any order, gaps allowed (rcu_dropout_masks_indexed: the rows a contiguous draw gives those samples, bit for bit)."""
         sites = self.dropout_sites()
         if not sites:
             return None
         g, count = len(seeds), len(sites)
         keeps = [(max(0.0, 1.0 - float(m.p)) if (m.training and m.p > 0) else -1.0) for m in self._site_modules]
         out = torch.empty(g * n * sum(c for _, c in sites), device=device, dtype=torch.float32)
+        if sample_index is not None:
+            if (not torch.is_tensor(sample_index) or sample_index.dtype != torch.int64 or sample_index.numel() != n or
+                    not sample_index.is_contiguous() or sample_index.device != out.device):
+                raise ValueError('sample_index must be a contiguous int64 tensor of {} entries on {}'.format(n, out.device))
+            _lib.check(_lib.load().rcu_dropout_masks_indexed((ctypes.c_uint64 * g)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds]), g, n,
+                                                             _lib.ptr(sample_index), (ctypes.c_int32 * count)(*[c for _, c in sites]),
+                                                             (ctypes.c_float * count)(*keeps), count, _lib.ptr(out), _lib.current_stream()))
+            return out
         _lib.check(_lib.load().rcu_dropout_masks((ctypes.c_uint64 * g)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds]), g, n, int(first_sample),
                                                  (ctypes.c_int32 * count)(*[c for _, c in sites]), (ctypes.c_float * count)(*keeps), count,
                                                  _lib.ptr(out), _lib.current_stream()))

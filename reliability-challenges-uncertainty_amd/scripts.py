@@ -445,6 +445,103 @@ class AgreementCsvHook(loops.TestLoopHook):
             writer.writerows(self.rows)
 
 
+def _refuse_adaptive(context, script):
+    if hasattr(context.config.others, 'mc_adaptive'):
+        raise ValueError('others.mc_adaptive (adaptive MC dropout) applies to the default test scripts with others.mc only; the {} script does not '
+                         'take it'.format(script))
+
+
+def _adaptive(context, world):
+    """``others.mc_adaptive: {check_at: [5, 10], tolerance: 0.01, max_unsettled: 0}`` (an rcu_amd extension, include/rcu.h "Adaptive MC") next to
+    ``others.mc``: slices settled at a pass checkpoint are retired and finalised from the passes they have seen -> the checked schedule, or None
+    without the key.  One process, MC dropout alone, exact statistics: a ValueError that names the key otherwise."""
+    if not hasattr(context.config.others, 'mc_adaptive'):
+        return None
+    others = context.config.others
+    value = others.mc_adaptive
+    if not isinstance(value, dict):
+        value = dict(vars(value)) if hasattr(value, '__dict__') else value
+    if hasattr(others, 'tta'):
+        raise ValueError('others.mc_adaptive does not compose with others.tta (test-time augmentation): the transforms of a slice share its statistics')
+    if not hasattr(others, 'mc'):
+        raise ValueError('others.mc_adaptive needs others.mc: there are no passes to save without MC dropout')
+    if getattr(others, 'agreement', False):
+        raise ValueError('others.mc_adaptive does not compose with others.agreement: the vote planes assume every slice sees every pass')
+    if not bool(getattr(others, 'exact', True)):
+        raise ValueError('others.mc_adaptive needs exact statistics (others.exact: false is refused): the decision is made on exact integer sums')
+    if world.world > 1:
+        raise ValueError('others.mc_adaptive is not sharded: run the script in one process')
+    try:
+        return steps.check_adaptive(value, others.mc)
+    except ValueError as e:
+        raise ValueError('others.mc_adaptive: {}'.format(e)) from None
+
+
+def _adaptive_seed(context):
+    if context.config.seed is None:
+        raise ValueError('others.mc_adaptive needs the YAML file\'s seed: a slice moved into a smaller batch keeps its samples through its mask keys')
+    return context.config.seed
+
+
+class AdaptiveRowsStep(steps.BatchStep):
+    """Behind the adaptive predict step: ``output['adaptive']``, one int64 row per slice (on the host) -- the slice's pass count, then for every
+    checkpoint of the schedule its ``margin_q`` there, or -1 where the slice was no longer active.  Assembled like ``'confusion'`` rows."""
+
+    def __init__(self, check_at):
+        self.check_at = [int(t) for t in check_at]
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        import torch
+        passes = batch_context.output['mc_passes']
+        rows = torch.full((passes.shape[0], 1 + len(self.check_at)), -1, dtype=torch.int64)
+        rows[:, 0] = passes.view(-1).cpu()
+        for record in batch_context.more.get('adaptive_checkpoints', ()):
+            k = self.check_at.index(record['t'])
+            for i, q in zip(record['active'], record['margin_q']):
+                rows[i, 1 + k] = q
+        batch_context.output['adaptive'] = rows
+
+
+def adaptive_csv_row(rows, check_at, mc_steps):
+    """The ``adaptive.csv`` columns of one subject from its slice rows (``AdaptiveRowsStep``) -> list: slices, slices retired at each checkpoint,
+    passes run, passes a plain run would make, the smallest margin of a retired slice and of a slice that stayed active (each
+    ``margin_q / (t * 2^40)`` at the checkpoint of the decision; empty without such a slice)."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 1 + len(check_at))
+    passes = rows[:, 0]
+    retired_margin, active_margin = [], []
+    for k, t in enumerate(check_at):
+        scale = float(t) * float(1 << 40)
+        retired_margin += [q / scale for q in rows[passes == t, 1 + k]]
+        active_margin += [q / scale for q in rows[(passes > t) & (rows[:, 1 + k] >= 0), 1 + k]]
+    return ([int(rows.shape[0])] + [int((passes == t).sum()) for t in check_at] + [int(passes.sum()), int(rows.shape[0]) * int(mc_steps)] +
+            [min(retired_margin) if retired_margin else '', min(active_margin) if active_margin else ''])
+
+
+class AdaptiveCsvHook(loops.TestLoopHook):
+    """``others.mc_adaptive``: ``<test_dir>/adaptive.csv``, one row per subject (``adaptive_csv_row``)."""
+
+    def __init__(self, check_at, mc_steps, file_name='adaptive.csv'):
+        self.check_at, self.mc_steps, self.file_name = [int(t) for t in check_at], int(mc_steps), file_name
+        self.rows = []
+
+    def on_test_start(self, task_context, context):
+        self.rows.clear()
+
+    def on_test_subject_end(self, subject_context, task_context, context):
+        data = subject_context.subject_data
+        rows = data.get('adaptive')
+        if rows is None:
+            raise ValueError('others.mc_adaptive: subject {} came without its adaptive rows'.format(subject_context.subject_index))
+        self.rows.append([data.get('subject', subject_context.subject_index)] + adaptive_csv_row(rows, self.check_at, self.mc_steps))
+
+    def on_test_end(self, task_context, context):
+        with open(os.path.join(context.test_dir, self.file_name), 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['subject', 'slices'] + ['retired_at_{}'.format(t) for t in self.check_at] +
+                            ['passes_run', 'passes_plain', 'min_margin_retired', 'min_margin_active'])
+            writer.writerows(self.rows)
+
+
 def _logit_samples(context):
     """``others.logit_samples`` (an rcu_amd extension): S in 1..RCU_LOGIT_MAX_SAMPLES, or None when the key is absent."""
     if not hasattr(context.config.others, 'logit_samples'):
@@ -537,11 +634,16 @@ def _refuse_corruption(context, script):
 
 
 def _default_steps(context, world):
+    adaptive = _adaptive(context, world)      # (refuses others.mc_adaptive beside tta, agreement, exact: false, several ranks, or without mc)
     if hasattr(context.config.others, 'tta'):
         _agreement(context, world)      # (refuses others.agreement: true)
         return _tta_steps(context, world)
     if not hasattr(context.config.others, 'mc'):
         _agreement(context, world)
+    if adaptive is not None:
+        return [steps.McPredictStep(context.config.others.mc, seed=_adaptive_seed(context), lanes=_other(context, 'stream_lanes'),
+                                    group_pixels=_other(context, 'group_pixels'), adaptive=adaptive),
+                steps.MultiPredictionSummary(), AdaptiveRowsStep(adaptive['check_at'])]
     if hasattr(context.config.others, 'mc'):
         lanes = _other(context, 'stream_lanes')
         # ``others.group_pixels`` / ``others.exact`` (rcu_amd extensions): the memory / reproducibility trade of the MC step.  Every stream lane of every
@@ -694,6 +796,10 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     if any(isinstance(s_, steps.SampleAgreementStep) for s_ in test_steps):
         entries = None if entries is None else entries + ('agreement',)
         extra.append(AgreementCsvHook(context.config.others.mc))
+    rows_step = next((s_ for s_ in test_steps if isinstance(s_, AdaptiveRowsStep)), None)
+    if rows_step is not None:      # (the written map files keep their names: the slice rows only feed adaptive.csv)
+        entries = None if entries is None else entries + ('adaptive',)
+        extra.append(AdaptiveCsvHook(rows_step.check_at, context.config.others.mc))
     return _run(context, dataset, test_steps, WriteHook(link_inputs=dataset == 'isic'), entries, world,
                 startup_hooks=_temperature_hooks(context) + corrupt_hooks, subject_hooks=extra)
 
@@ -703,6 +809,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
     _refuse_tta(context, 'ensemble')
     _refuse_temperature(context, 'ensemble')
     _refuse_agreement(context, 'ensemble')
+    _refuse_adaptive(context, 'ensemble')
     _refuse_logit_samples(context, 'ensemble')
     corrupt_steps, corrupt_hooks = _corruption(context)
     members = _load_additional_models(context)
@@ -719,6 +826,7 @@ def test_aleatoric(dataset, config_file=None, device='cuda'):
     _refuse_tta(context, 'aleatoric')
     _refuse_temperature(context, 'aleatoric')
     _refuse_agreement(context, 'aleatoric')
+    _refuse_adaptive(context, 'aleatoric')
     corrupt_steps, corrupt_hooks = _corruption(context)
     return _run(context, dataset, corrupt_steps + _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world, startup_hooks=corrupt_hooks)
@@ -863,6 +971,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     _refuse_tta(context, 'auxiliary_feat')
     _refuse_temperature(context, 'auxiliary_feat')
     _refuse_agreement(context, 'auxiliary_feat')
+    _refuse_adaptive(context, 'auxiliary_feat')
     _refuse_logit_samples(context, 'auxiliary_feat')
     corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
@@ -888,6 +997,7 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     _refuse_tta(context, 'auxiliary_segm')
     _refuse_temperature(context, 'auxiliary_segm')
     _refuse_agreement(context, 'auxiliary_segm')
+    _refuse_adaptive(context, 'auxiliary_segm')
     _refuse_logit_samples(context, 'auxiliary_segm')
     corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
@@ -953,6 +1063,7 @@ def fit_temperature(dataset, config_file, device='cuda'):
     _refuse_temperature(context, 'fit_temperature')
     _refuse_logit_samples(context, 'fit_temperature')
     _refuse_agreement(context, 'fit_temperature')
+    _refuse_adaptive(context, 'fit_temperature')
     _refuse_corruption(context, 'fit_temperature')
     mc = int(getattr(others, 'mc', 0) or 0)
     seed = 0 if context.config.seed is None else int(context.config.seed)

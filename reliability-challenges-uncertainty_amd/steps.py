@@ -22,6 +22,7 @@ sums, updated by the fused forward+softmax+accumulate kernel) under ``multi_prob
 (a real ``[T, N, C, H, W]`` tensor), and the summary accepts either form.
 """
 import abc
+import fractions
 import logging
 import operator
 
@@ -191,15 +192,133 @@ class McStatistics:
         entropy = torch.empty(shape1, device=dev, dtype=torch.float32)
         mi = torch.empty(shape1, device=dev, dtype=torch.float32) if do_mi else None
         var = torch.empty(shape1, device=dev, dtype=torch.float32) if do_var else None
-        _lib.check(_lib.load().rcu_mc_finalize(_lib.ptr(self.blob), self.n, self.hw, self.nb_classes, int(t), self.flags,
-                                               _lib.ptr(mean), _lib.ptr(entropy), _lib.ptr(mi), _lib.ptr(var),
-                                               _lib.current_stream()))
+        self._finalize_into(t, mean, entropy, mi, var)
         out = {'probabilities': mean, 'entropy': entropy}
         if do_mi:
             out['mutual_info'] = mi
         if do_var:
             out['variance'] = var
         return out
+
+    def _finalize_into(self, t, mean, entropy, mi, var):
+        _lib.check(_lib.load().rcu_mc_finalize(_lib.ptr(self.blob), self.n, self.hw, self.nb_classes, int(t), self.flags,
+                                               _lib.ptr(mean), _lib.ptr(entropy), _lib.ptr(mi), _lib.ptr(var),
+                                               _lib.current_stream()))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# EXTENSION adaptive MC (include/rcu.h "Adaptive MC"): slices settled at a pass checkpoint are retired and finalised from fewer passes
+# ------------------------------------------------------------------------------------------------------------------------------
+def adaptive_threshold(tolerance, t):
+    """``thr_q`` of checkpoint t: ceil((1.0 - tolerance) * t * 2^40) in exact rational arithmetic on the float64 value of ``1.0 - tolerance``
+    -- the integer the leading class sum of a voxel (times 2^40) has to reach for the voxel to be settled.  Nothing rounds."""
+    x = fractions.Fraction(1.0 - float(tolerance)) * int(t) * (1 << 40)
+    return -((-x.numerator) // x.denominator)
+
+
+def check_adaptive(adaptive, mc_steps):
+    """The schedule ``dict(check_at=[t1 < t2 < ...], tolerance=eps, max_unsettled=0)`` of ``McPredictStep(adaptive=...)`` -> the same with plain
+    values, or a ValueError that names the limit: 2 <= t1, the last checkpoint < T, at most 4 checkpoints, 0 <= eps < 1, max_unsettled >= 0."""
+    if not isinstance(adaptive, dict):
+        raise ValueError('adaptive must be a dict with the keys check_at, tolerance[, max_unsettled], got {!r}'.format(adaptive))
+    unknown = set(adaptive) - {'check_at', 'tolerance', 'max_unsettled'}
+    if unknown:
+        raise ValueError('adaptive: unknown keys {} (check_at, tolerance, max_unsettled)'.format(sorted(unknown)))
+    for key in ('check_at', 'tolerance'):
+        if key not in adaptive:
+            raise ValueError('adaptive: {} is missing'.format(key))
+    try:
+        check_at = [operator.index(t) for t in adaptive['check_at']]
+    except TypeError:
+        raise ValueError('adaptive: check_at must be a list of integer pass counts, got {!r}'.format(adaptive['check_at'])) from None
+    if not 1 <= len(check_at) <= _lib.RCU_ADAPTIVE_MAX_CHECKPOINTS:
+        raise ValueError('adaptive: check_at needs 1..{} checkpoints, got {}'.format(_lib.RCU_ADAPTIVE_MAX_CHECKPOINTS, len(check_at)))
+    if any(b <= a for a, b in zip(check_at, check_at[1:])):
+        raise ValueError('adaptive: check_at must be strictly increasing, got {}'.format(check_at))
+    if check_at[0] < 2:
+        raise ValueError('adaptive: the first checkpoint must be at least 2 passes, got {}'.format(check_at[0]))
+    if check_at[-1] >= int(mc_steps):
+        raise ValueError('adaptive: the last checkpoint ({}) must be below mc_steps ({})'.format(check_at[-1], mc_steps))
+    tolerance = float(adaptive['tolerance'])
+    if not 0.0 <= tolerance < 1.0:
+        raise ValueError('adaptive: tolerance must be in [0, 1), got {}'.format(adaptive['tolerance']))
+    max_unsettled = operator.index(adaptive.get('max_unsettled', 0))
+    if max_unsettled < 0:
+        raise ValueError('adaptive: max_unsettled must be >= 0, got {}'.format(max_unsettled))
+    return dict(check_at=check_at, tolerance=tolerance, max_unsettled=max_unsettled)
+
+
+def adaptive_counts(n, check_at, mc_steps, spans):
+    """Pass count per slice from the index lists ``spans`` of a step over n slices: spans[0] = all slices (passes 1..t_1), spans[k] = the slices
+    still active after checkpoint k (passes t_k + 1 .. t_{k+1}, the last span to T).  A slice that is in spans[k - 1] and not in spans[k] was
+    retired at t_k.  -> list of n ints."""
+    ends = list(check_at) + [int(mc_steps)]
+    counts = [0] * n
+    for k, span in enumerate(spans):
+        for i in span:
+            counts[i] = ends[k]
+    return counts
+
+
+def compact_group_size(model, m, h, w, group_pixels, plan_samples):
+    """MC passes per launch of a compact batch of m slices: ``pass_group_size`` for m, capped so that no launch exceeds the ``plan_samples``
+    samples of the plan the full batch reserved (``reserve_canonical_plans``): a compact span never re-plans."""
+    return max(1, min(pass_group_size(model, m, h, w, group_pixels), int(plan_samples) // int(m)))
+
+
+def slice_scores(stats, thr_q, out=None):
+    """rcu_mc_slice_scores of exact statistics -> one int64 device tensor ``[2 n]`` (``out``): margin_q in [:n], the unsettled counts as the
+    int32 view of [n:] -- one buffer, so one device-to-host copy brings both (``split_scores``)."""
+    if not stats.exact:
+        raise ValueError('slice scores need exact statistics (exact=True): the decision is made on exact integer sums')
+    n = stats.n
+    buf = torch.empty(2 * n, device=stats.blob.device, dtype=torch.int64) if out is None else out
+    _lib.check(_lib.load().rcu_mc_slice_scores(_lib.ptr(stats.blob), n, stats.hw, stats.nb_classes, stats.flags, int(thr_q),
+                                               _lib.ptr(buf[n:]), _lib.ptr(buf[:n]), _lib.current_stream()))
+    return buf
+
+
+def split_scores(buf):
+    """The host copy of a ``slice_scores`` buffer -> (unsettled, margin_q), two lists of n ints."""
+    host = buf.cpu()
+    n = host.numel() // 2
+    return host[n:].view(torch.int32)[:n].tolist(), host[:n].tolist()
+
+
+def merge_slices(src, dst, index):
+    """rcu_mc_merge_slices: the statistics of the m slices of ``src`` added into the slices ``index`` (int32 device tensor ``[m]``, distinct
+    entries; negative ones are skipped) of ``dst``."""
+    if (src.hw, src.nb_classes, src.flags) != (dst.hw, dst.nb_classes, dst.flags):
+        raise ValueError('merge_slices: the two statistics differ in shape, classes or flags')
+    if index.dtype != torch.int32 or index.numel() != src.n or not index.is_contiguous() or index.device != dst.blob.device:
+        raise ValueError('merge_slices: index must be a contiguous int32 tensor of {} entries on the statistics device'.format(src.n))
+    _lib.check(_lib.load().rcu_mc_merge_slices(_lib.ptr(src.blob), src.n, _lib.ptr(dst.blob), dst.n, dst.hw, dst.nb_classes, dst.flags,
+                                               _lib.ptr(index), _lib.current_stream()))
+
+
+class AdaptiveMcStatistics(McStatistics):
+    """The statistics of an adaptive step: exact sums in which slice i holds the passes 1..counts[i].  ``counts``: int32 ``[n]`` on the device;
+    ``checkpoints``: one record per checkpoint reached, ``dict(t=, thr_q=, active=[slice indices scored], unsettled=[...], margin_q=[...],
+    retired=[slice indices retired])``; ``spans``: the index lists the pass spans ran on (``adaptive_counts``).  ``finalize`` divides every
+    slice by its own count (rcu_mc_finalize_counts); the stacked tensor does not exist (slices have different pass counts): ``as_tensor``
+    raises.  The ``recipe`` replays the recorded index lists -- it does not decide again."""
+
+    def __init__(self, n, nb_classes, height, width, device, do_mi=False, do_var=False, blob=None):
+        super().__init__(n, nb_classes, height, width, device, do_mi, do_var, blob=blob, exact=True)
+        self.counts = None
+        self.checkpoints = []
+        self.spans = []
+        self.passes_run = 0       # slice passes of the stochastic spans (a plain step runs n * T)
+
+    def as_tensor(self):
+        raise ValueError('adaptive MC statistics have no [T, N, C, H, W] stack: the slices have seen different numbers of passes')
+
+    def _finalize_into(self, t, mean, entropy, mi, var):
+        """Every slice by its own count (``t``, the largest of them, is not used)."""
+        if self.counts is None:
+            raise ValueError('adaptive MC statistics without pass counts: they are set by the predict step')
+        _lib.check(_lib.load().rcu_mc_finalize_counts(_lib.ptr(self.blob), self.n, self.hw, self.nb_classes, _lib.ptr(self.counts), self.flags,
+                                                      _lib.ptr(mean), _lib.ptr(entropy), _lib.ptr(mi), _lib.ptr(var), _lib.current_stream()))
 
 
 class StreamLanes:
@@ -444,11 +563,14 @@ class HipEngine:
         else:                                                     # float64 statistics: the reduce buffer's tail is float64 too
             ws_out.copy_(softmax(self.model(x)))
 
-    def seeded_masks(self, x, seeds, first_sample=0):
+    def seeded_masks(self, x, seeds, first_sample=0, sample_index=None):
         """The masks of the passes seeded with ``seeds`` over x, in the layout of their group launch (UNet.seeded_masks: one kernel, the factors
-        of sample i in pass t a function of seeds[t] and the sample's global index ``first_sample + i`` alone)."""
+        of sample i in pass t a function of seeds[t] and the sample's global index ``first_sample + i`` -- or ``sample_index[i]``, an int64
+        device tensor -- alone)."""
         set_dropout_mode(self.model, True)
         try:
+            if sample_index is not None:
+                return self.model.seeded_masks(x.shape[0], x.device, seeds, sample_index=sample_index)
             return self.model.seeded_masks(x.shape[0], x.device, seeds, first_sample)
         finally:
             set_dropout_mode(self.model, False)
@@ -795,8 +917,25 @@ class McPredictStep(BatchStep):
     LANES = 2      # HIP streams the pass groups of a batch alternate over (StreamLanes); the ``lanes`` argument overrides it
 
     def __init__(self, mc_steps, do_mi=False, do_var=False, materialize=False, masks=None, ws_pass=True,
-                 group_pixels=None, lanes=None, seed=None, exact=True, agreement=False) -> None:
+                 group_pixels=None, lanes=None, seed=None, exact=True, agreement=False, adaptive=None) -> None:
         super().__init__()
+        # EXTENSION ``adaptive`` (include/rcu.h "Adaptive MC"): ``dict(check_at=[t1 < t2 < ...], tolerance=eps, max_unsettled=0)``.  At checkpoint
+        # t a slice whose voxels all (but max_unsettled) have a leading class of mean probability >= 1 - eps over its t passes is retired: it
+        # keeps those t passes and is finalised from them, the other slices run on as a smaller batch.  ``multi_probabilities`` is then an
+        # AdaptiveMcStatistics and ``output['mc_passes']`` the int32 pass count per slice.  Approximate by design, opt-in.
+        self.adaptive = None
+        if adaptive is not None:
+            self.adaptive = check_adaptive(adaptive, mc_steps)
+            if not exact or mc_steps > _lib.RCU_MC_EXACT_MAX_PASSES:
+                raise ValueError('adaptive MC needs exact statistics (exact=True, mc_steps <= {}): the decision is made on exact integer '
+                                 'sums'.format(_lib.RCU_MC_EXACT_MAX_PASSES))
+            if seed is None and masks is None:
+                raise ValueError('adaptive MC needs a seed (or injected masks): a slice moved into a smaller batch must keep its samples')
+            if materialize:
+                raise ValueError('adaptive MC needs the fused path (materialize=False): there is no [T, N, C, H, W] stack of slices with '
+                                 'different pass counts')
+            if agreement:
+                raise ValueError('adaptive MC needs agreement=False: the vote planes assume every slice sees every pass')
         # EXTENSION ``agreement`` (include/rcu.h "Sample agreement"): ``output['sample_votes']`` (SampleVotes) -- one bit per (voxel, pass), set
         # where the pass's arg-max is not background; written by the head kernel of the fused path (every lane votes into a plane of its own,
         # OR-merged at the end), by ``sample_votes`` on the materialised one.  The weight-scaling pass casts no vote.
@@ -830,12 +969,22 @@ class McPredictStep(BatchStep):
         images = _images_to_device(batch_context, context)
         model = context.model
         k = first_sample_of(batch_context, images.shape[0])      # global index of the batch's first sample: what the seeded masks are keyed by
+        if self.adaptive is not None:
+            if not isinstance(model, model_mod.UNet):
+                raise ValueError('adaptive MC needs the fused path: the model must be a rcu_amd.model.UNet, got {}'.format(type(model).__name__))
+            if model.nb_classes < 2:
+                raise ValueError('adaptive MC needs nb_classes >= 2: the criterion is the mean probability of the leading class')
         if not self.materialize and isinstance(model, model_mod.UNet):
             n, _, h, w = images.shape
             ws = torch.empty((n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
             if ws is not None:
                 batch_context.output['ws_probabilities'] = ws
-            stats = self._fused(model, images, self.do_mi, self.do_var, k, ws, votes=self.agreement)
+            if self.adaptive is not None:
+                stats = self._fused_adaptive(model, images, self.do_mi, self.do_var, k, ws)
+                batch_context.output['mc_passes'] = stats.counts.view(n, 1)      # (a column: slice rows travel like 'confusion' rows, channel last)
+                batch_context.more['adaptive_checkpoints'] = stats.checkpoints
+            else:
+                stats = self._fused(model, images, self.do_mi, self.do_var, k, ws, votes=self.agreement)
             batch_context.output['multi_probabilities'] = stats
             if self.agreement:
                 batch_context.output['sample_votes'] = stats.votes
@@ -906,6 +1055,94 @@ class McPredictStep(BatchStep):
                 set_dropout_mode(model, is_train=False)
                 if now is not None:
                     torch.cuda.set_rng_state(now, dev)
+
+        stats.recipe = recipe
+        return stats
+
+    def _gathered_mask_set(self, model, mask_set, n, index):
+        """The rows ``index`` (device int64 tensor) of one injected mask set over n images -> a list of per-site ``[m, C_site]`` device tensors."""
+        sites = model.dropout_sites()
+        if isinstance(mask_set, (list, tuple)):
+            rows = [torch.as_tensor(a, dtype=torch.float32).to(index.device) for a in mask_set]
+        else:
+            rows = [r.view(n, c) for r, (_, c) in zip(torch.split(mask_set.to(index.device), [n * c for _, c in sites]), sites)]
+        return [r.index_select(0, index) for r in rows]
+
+    def _fused_adaptive(self, model, images, do_mi, do_var, first_sample=0, ws=None, replay=None):
+        """The adaptive form of ``_fused`` (include/rcu.h "Adaptive MC").  Passes 1..t_1 run on all slices through ``launch_plan`` / ``run_plan``
+        as ``McPredictStep(mc_steps=t_1)`` runs them; at every checkpoint the lanes are joined, the slices are scored on the device
+        (rcu_mc_slice_scores: one small copy to the host) and the still-active ones are gathered into a compact batch whose next span of passes
+        runs -- under the same keys: pass j is drawn under ``pass_seed(seed, j)`` at the slices' GLOBAL indices -- into compact statistics that
+        rcu_mc_merge_slices adds into the rows of the full ones.  Everything runs on the plans the plain step reserves for (n, T): a compact
+        launch never holds more samples than they do.  ``replay``: the ``spans`` of an earlier run -- they are used as recorded and nothing is
+        scored (the statistics' recipe)."""
+        n, _, h, w = images.shape
+        dev = images.device
+        cfg, total = self.adaptive, self.mc_steps
+        engine = HipEngine(model, do_mi, do_var, True)
+        stats = AdaptiveMcStatistics(n, model.nb_classes, h, w, dev, do_mi, do_var)
+        group = pass_group_size(model, n, h, w, self.group_pixels)
+        lanes = min(self.lanes, total)
+        plan_samples = reserve_canonical_plans(model, n, h, w, total, group, lanes)
+        ends = cfg['check_at'] + [total]
+        active = list(range(n))
+        scores = torch.empty(2 * n, device=dev, dtype=torch.int64) if replay is None else None
+        try:
+            for k, end in enumerate(ends):
+                begin = ends[k - 1] if k else 0
+                jobs = list(range(begin + 1, end + 1))
+                stats.spans.append(list(active))
+                stats.passes_run += len(active) * len(jobs)
+                if k == 0:
+                    span_lanes = min(lanes, len(jobs))
+                    plan = launch_plan(([0] if ws is not None else []) + jobs, (0,), total, group, span_lanes)
+                    run_plan(plan, engine, images, stats, ws, span_lanes,
+                             draw=lambda e, js: launch_masks(engine, images, e, js, total, self.seed, first_sample, self.masks))
+                else:
+                    m = len(active)
+                    index = torch.tensor(active, device=dev, dtype=torch.int64)
+                    x = images.index_select(0, index)
+                    sample_index = index + int(first_sample)
+                    if self.masks is not None:
+                        sets = {j: self._gathered_mask_set(model, self.masks[j - 1], n, index) for j in jobs}
+
+                        def draw(e, js, sets=sets):
+                            return sets[js[0]] if len(js) == 1 else [sets[j] for j in js]
+                    else:
+                        def draw(e, js, x=x, sample_index=sample_index):
+                            return engine.seeded_masks(x, [pass_seed(self.seed, j) for j in js], sample_index=sample_index)
+                    compact = engine.side_statistics(x)
+                    span_lanes = min(lanes, len(jobs))
+                    plan = launch_plan(jobs, (0,), total, compact_group_size(model, m, h, w, self.group_pixels, plan_samples), span_lanes)
+                    run_plan(plan, engine, x, compact, None, span_lanes, draw=draw)
+                    merge_slices(compact, stats, index.to(torch.int32))
+                if k == len(ends) - 1:
+                    break
+                # the checkpoint: behind run_plan the lanes are joined on the caller's stream
+                if replay is not None:
+                    active = list(replay[k + 1]) if k + 1 < len(replay) else []
+                else:
+                    thr = adaptive_threshold(cfg['tolerance'], end)
+                    unsettled, margin_q = split_scores(slice_scores(stats, thr, out=scores))
+                    gone = [i for i in active if unsettled[i] <= cfg['max_unsettled']]
+                    stats.checkpoints.append(dict(t=end, thr_q=thr, active=list(active), unsettled=[unsettled[i] for i in active],
+                                                  margin_q=[margin_q[i] for i in active], retired=gone))
+                    active = [i for i in active if unsettled[i] > cfg['max_unsettled']]
+                if not active:
+                    break
+        finally:
+            set_dropout_mode(model, is_train=False)
+        counts = adaptive_counts(n, cfg['check_at'], total, stats.spans)
+        stats.counts = torch.tensor(counts, device=dev, dtype=torch.int32)
+        stats.count = max(counts)
+        spans = [list(s) for s in stats.spans]
+
+        def recipe(mi, var, materialize=False):
+            if materialize:
+                raise ValueError('adaptive MC statistics have no [T, N, C, H, W] stack: the slices have seen different numbers of passes')
+            again = self._fused_adaptive(model, images, mi, var, first_sample, replay=spans)
+            again.checkpoints = stats.checkpoints
+            return again
 
         stats.recipe = recipe
         return stats
