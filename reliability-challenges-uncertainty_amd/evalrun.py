@@ -72,6 +72,14 @@ CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities',
 
 
 # ------------------------------------------------------------------------------------- CSV hooks
+def write_table(path, header, rows):
+    """A CSV file of one header row and ``rows``."""
+    with open(path, 'w', newline='') as f:
+        writer = csv.writer(f)
+        writer.writerow(header)
+        writer.writerows(rows)
+
+
 class EvalHook:
     def on_run_start(self, run_id: str):
         pass
@@ -132,10 +140,7 @@ class WriteCsvHook(EvalHook):
         self.rows.append([run_id, subject_name] + [flat[e] for e in self.entries])
 
     def on_run_end(self, results_history: dict, run_id: str):
-        with open(self.file_path, 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(self.header)
-            writer.writerows(self.rows)
+        write_table(self.file_path, self.header, self.rows)
 
 
 class WriteBinsCsvHook(WriteCsvHook):
@@ -163,11 +168,8 @@ class WriteSummaryCsvHook(EvalHook):
         self.confidence_entry = confidence_entry
 
     def on_run_end(self, results_history: dict, run_id: str):
-        with open(self.file_path, 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['confidence_entry'] + self.entries)
-            writer.writerow([self.confidence_entry] + [fn(results_history[e]) for e, fn in
-                                                       zip(self.entries, self.summary_fn)])
+        write_table(self.file_path, ['confidence_entry'] + self.entries,
+                    [[self.confidence_entry] + [fn(results_history[e]) for e, fn in zip(self.entries, self.summary_fn)]])
 
 
 def read_min_max(min_max_file: str):
@@ -349,15 +351,34 @@ class EvalCase:
 
 
 class EvalAction(abc.ABC):
+    """An action of the evaluation script.  The plain loop calls ``eval_subject``; what the fused loop (``_evaluate_fused``, the
+    device-metrics hook) needs to serve the action from the one `evaluation.SubjectBatch.metrics` call of a batch is declared here too:
+    ``scans``, ``fused_arguments`` and ``record_fused``."""
+
+    scans = None              # the scans (names of ``want``) of `SubjectBatch.metrics` the action is recorded from; None: it cannot run fused
+    need_mask = False         # whether it evaluates inside the T2 brain mask
+    checks_range = True       # whether its preparation refuses maps outside [0, 1] (helper.add_background_probability)
+
     def __init__(self) -> None:
         self.load_params = None
         self.prepare = None
         self.eval_cases = []
         self.id_ = ''
+        self.out_dir = None
 
     @abc.abstractmethod
     def setup_eval(self, eval_data: EvalData):
         pass
+
+    def fused_arguments(self):
+        """The keyword arguments of `SubjectBatch.metrics` this action fixes ('mask': whether the batch holds the brain mask)."""
+        return {}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        """Subject ``slot`` of a `SubjectBatch.metrics` result -> the rows ``eval_subject`` would have recorded."""
+
+    def path(self, placeholder):
+        return os.path.join(self.out_dir, placeholder.format(self.id_))
 
     def start_eval(self):
         print(self.id_ + ', '.join(c.id_ for c in self.eval_cases if c.id_ != ''))
@@ -383,6 +404,9 @@ def _minmax_for(min_max_dir, run_id, rescale):
 
 
 class SaveMinMaxAction(EvalAction):
+    scans = ('minmax',)
+    checks_range = False      # (it moves the confidence entry as it is)
+
     def __init__(self, min_max_dir: str) -> None:
         super().__init__()
         self.min_max_dir = min_max_dir
@@ -398,65 +422,33 @@ class SaveMinMaxAction(EvalAction):
                                    confidence_entry=eval_data.confidence_entry)
         self.eval_cases = [EvalCase(metric, hook)]
 
+    def record_fused(self, res, slot, subject, n_dim):
+        self.eval_cases[0].record({'min': res['min'][slot], 'max': res['max'][slot]}, subject, self.id_)
 
-class EceAction(EvalAction):
-    def __init__(self, base_dir, details, rescale_confidence='subject', rescale_sigma='subject', min_max_dir=None):
+
+def _confusion(res, slot):
+    """tp, tn, fp, fn of a subject: the first four of the uncertainty-error counts at any threshold (the 'ue' scan)."""
+    return tuple(int(v) for v in res['counts'][slot][0][:4])
+
+
+class PreparedAction(EvalAction):
+    """What the actions on a prepared confidence entry share: the preparation function (``get_probability_preparation`` or
+    ``get_uncertainty_preparation``) with its rescale arguments, the output directory ``<base_dir>/<out_name>``, the mask flag, the
+    preparation of a run (``setup_run`` is the subclass's part of ``setup_eval``), a subject's prepared entries, the usual file of one row
+    per subject and the one-row file of a pooled result."""
+
+    def __init__(self, preparation, out_name, need_mask, base_dir, rescale_confidence, rescale_sigma, min_max_dir):
         super().__init__()
+        self.preparation, self.need_mask = preparation, need_mask
         self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.need_t2_mask = details == 'foreground'
-        self.out_dir = os.path.join(base_dir, ECE_FOREGROUND_NAME if self.need_t2_mask else ECE_NAME)
+        self.out_dir = os.path.join(base_dir, out_name)
         os.makedirs(self.out_dir, exist_ok=True)
 
     def setup_eval(self, eval_data):
         rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
         mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_probability_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry, need_t2_mask=self.need_t2_mask)
-        metric = ev.ComposeEvaluation([ev.EceBinaryNumpy(threshold_range=None, with_mask=self.need_t2_mask),
-                                       ev.DiceNumpy(), ev.ConfusionMatrix()])
-        hook = WriteCsvHook(os.path.join(self.out_dir, ECE_PLACEHOLDER.format(self.id_)),
-                            entries=('ece', 'dice', 'tp', 'tn', 'fp', 'fn', 'n'))
-        self.eval_cases = [EvalCase(metric, hook)]
-
-
-class EceCalibrationAction(EvalAction):
-    def __init__(self, base_dir, details='', rescale_confidence='subject', rescale_sigma='subject', min_max_dir=None):
-        super().__init__()
-        self.need_mask = details == 'foreground'
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, CALIB_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
-
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_probability_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
+        self.prepare, self.id_ = self.preparation(eval_data.confidence_entry, eval_data.id_, self.rescale_confidence, self.rescale_sigma, mm)
         self.load_params = Loader.Params(eval_data.confidence_entry, need_t2_mask=self.need_mask)
-        metric = ev.ComposeEvaluation([ev.EceBinaryNumpy(threshold_range=None, return_bins=True,
-                                                         with_mask=self.need_mask), ev.DiceNumpy()])
-        hook = WriteBinsCsvHook(os.path.join(self.out_dir, CALIBRATION_PLACEHOLDER.format(self.id_)))
-        self.eval_cases = [EvalCase(metric, hook)]
-
-
-class UncertaintyAction(EvalAction):
-    """What the actions on the prepared 'uncertainty' entry share: the rescale arguments and the output directory ``<base_dir>/uncertainty``,
-    the preparation of a run (``setup_run`` is the subclass's part of ``setup_eval``), a subject's prepared entries, the check of
-    ``levels`` and the one-row file of a pooled result."""
-
-    def __init__(self, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
-        super().__init__()
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, UNCERTAINTY_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
-
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_uncertainty_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry)
         self.setup_run()
 
     @abc.abstractmethod
@@ -465,23 +457,73 @@ class UncertaintyAction(EvalAction):
 
     def subject_rows(self, placeholder, keys):
         """The usual ``eval_cases``: one CSV file of one row per subject, filled through ``eval_cases[0].record``."""
-        self.eval_cases = [EvalCase(None, WriteCsvHook(os.path.join(self.out_dir, placeholder.format(self.id_)), entries=keys))]
+        self.eval_cases = [EvalCase(None, WriteCsvHook(self.path(placeholder), entries=keys))]
 
     def prepared(self, sf, loader):
         to_eval = loader.get_data(sf, self.load_params)
         return self.prepare(to_eval) if self.prepare else to_eval
+
+    def write_pooled_row(self, path, keys, row):
+        write_table(path, ['test_id'] + list(keys), [[self.id_] + [row[k] for k in keys]])
+
+
+class EceAction(PreparedAction):
+    scans = ('ece', 'ue')
+
+    def __init__(self, base_dir, details, rescale_confidence='subject', rescale_sigma='subject', min_max_dir=None):
+        foreground = details == 'foreground'
+        super().__init__(ev.get_probability_preparation, ECE_FOREGROUND_NAME if foreground else ECE_NAME, foreground, base_dir, rescale_confidence,
+                         rescale_sigma, min_max_dir)
+
+    def setup_run(self):
+        metric = ev.ComposeEvaluation([ev.EceBinaryNumpy(threshold_range=None, with_mask=self.need_mask),
+                                       ev.DiceNumpy(), ev.ConfusionMatrix()])
+        hook = WriteCsvHook(self.path(ECE_PLACEHOLDER), entries=('ece', 'dice', 'tp', 'tn', 'fp', 'fn', 'n'))
+        self.eval_cases = [EvalCase(metric, hook)]
+
+    def fused_arguments(self):
+        return {'mask': self.need_mask}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        tp, tn, fp, fn = _confusion(res, slot)
+        results = {'ece': ev.ece_from_histogram(*(h[slot] for h in res['hist']), n_dim=n_dim), 'dice': ev._dice(tp, fp, fn)}
+        results.update(tp=tp, tn=tn, fp=fp, fn=fn, n=tp + tn + fp + fn)
+        self.eval_cases[0].record(results, subject, self.id_)
+
+
+class EceCalibrationAction(PreparedAction):
+    scans = ('ece', 'ue')
+
+    def __init__(self, base_dir, details='', rescale_confidence='subject', rescale_sigma='subject', min_max_dir=None):
+        super().__init__(ev.get_probability_preparation, CALIB_NAME, details == 'foreground', base_dir, rescale_confidence, rescale_sigma, min_max_dir)
+
+    def setup_run(self):
+        metric = ev.ComposeEvaluation([ev.EceBinaryNumpy(threshold_range=None, return_bins=True,
+                                                         with_mask=self.need_mask), ev.DiceNumpy()])
+        self.eval_cases = [EvalCase(metric, WriteBinsCsvHook(self.path(CALIBRATION_PLACEHOLDER)))]
+
+    def fused_arguments(self):
+        return {'mask': self.need_mask}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        tp, _, fp, fn = _confusion(res, slot)
+        results = {}             # key order of EceBinaryNumpy(return_bins=True) + DiceNumpy: the bins, ece, dice
+        results['ece'] = ev.ece_from_histogram(*(h[slot] for h in res['hist']), n_dim=n_dim, out_bins=results)
+        results['dice'] = ev._dice(tp, fp, fn)
+        self.eval_cases[0].record(results, subject, self.id_)
+
+
+class UncertaintyAction(PreparedAction):
+    """The actions on the prepared 'uncertainty' entry: files in ``<base_dir>/uncertainty``, no brain mask; and the check of ``levels``."""
+
+    def __init__(self, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        super().__init__(ev.get_uncertainty_preparation, UNCERTAINTY_NAME, False, base_dir, rescale_confidence, rescale_sigma, min_max_dir)
 
     @staticmethod
     def checked_levels(levels):
         if not 2 <= int(levels) <= ev._lib.RCU_UNC_HIST_MAX_LEVELS:
             raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_UNC_HIST_MAX_LEVELS, levels))
         return int(levels)
-
-    def write_pooled_row(self, path, keys, row):
-        with open(path, 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id'] + list(keys))
-            writer.writerow([self.id_] + [row[k] for k in keys])
 
 
 class CorrectionAction(UncertaintyAction):
@@ -490,6 +532,13 @@ class CorrectionAction(UncertaintyAction):
     def __init__(self, thresholds, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
         super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.thresholds = list(thresholds)
+
+    @property
+    def scans(self):         # fused only where the library's table of the reference's uncertain-voxel sets covers the thresholds
+        return ('ue',) if ev.from_p_supported(self.thresholds) else None
+
+    def fused_arguments(self):
+        return {'thresholds': tuple(self.thresholds)}
 
     def setup_run(self):
         self.sweep = ev.UncertaintyAndCorrectionSweep(self.thresholds)
@@ -505,8 +554,55 @@ class CorrectionAction(UncertaintyAction):
         for thr, case in zip(self.thresholds, self.eval_cases):
             case.record(results[thr], sf.subject, self.id_)
 
+    def record_fused(self, res, slot, subject, n_dim):
+        for t, case in enumerate(self.eval_cases):
+            case.record(ev.correction_results(res['counts'][slot][t]), subject, self.id_)
 
-class UeCurvesAction(UncertaintyAction):
+
+class LevelHistogramAction(UncertaintyAction):
+    """The body of ``UeCurvesAction`` and ``PatchesAction``: one integer histogram ``[ROWS, levels]`` per subject (``histogram`` in the plain
+    loop, ``res[RESULT]`` in the fused one), ``metrics`` of it as the subject's row (``KEYS``), the histograms summed, and at the end the
+    same metrics of the sum and the sum itself, one row per level.  ``FILES``: the placeholders of these three files."""
+
+    RESULT = ROWS = KEYS = metrics = FILES = LEVELS_COLUMNS = None
+
+    def __init__(self, levels, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
+        self.levels = self.checked_levels(levels)
+        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
+        self.pooled = None
+
+    def fused_arguments(self):
+        return {'levels': self.levels}
+
+    def setup_run(self):
+        self.subject_rows(self.FILES[0], self.KEYS)
+        self.pooled = np.zeros((self.ROWS, self.levels), dtype=np.uint64)
+
+    def record_histogram(self, hist, subject_name):
+        """One subject's histogram ``[ROWS, levels]``: its metrics row, and its share of the pooled histogram."""
+        self.eval_cases[0].record(self.metrics(hist), subject_name, self.id_)
+        self.pooled += np.asarray(hist, dtype=np.uint64)
+
+    def eval_subject(self, sf, loader):
+        to_eval = self.prepared(sf, loader)
+        self.record_histogram(self.histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty']), sf.subject)
+
+    def record_fused(self, res, slot, subject, n_dim):
+        self.record_histogram(res[self.RESULT][slot], subject)
+
+    def extra_levels_columns(self):
+        """What the levels file holds per level behind ``level, threshold`` and the pooled integers."""
+        return [[]] * self.levels
+
+    def finish_eval(self):
+        super().finish_eval()
+        self.write_pooled_row(self.path(self.FILES[1]), self.KEYS, self.metrics(self.pooled))
+        extra = self.extra_levels_columns()
+        write_table(self.path(self.FILES[2]), self.LEVELS_COLUMNS,
+                    ([level, level / self.levels] + [int(v) for v in self.pooled[:, level]] + extra[level] for level in range(self.levels)))
+
+
+class UeCurvesAction(LevelHistogramAction):
     """EXTENSION (the reference has no such action): threshold-free uncertainty-error metrics from one level histogram per subject
     (evaluation.uncertainty_histogram / ue_curve_metrics), prepared exactly like ``CorrectionAction`` and, like it, without a brain mask.
     Files in ``<base_dir>/uncertainty``:
@@ -516,37 +612,16 @@ class UeCurvesAction(UncertaintyAction):
                                        levels, the boundary below the level; the rows from level k on add up to the voxels with
                                        uncertainty > k / levels, so risk-coverage and uncertainty-error Dice curves need no second run"""
 
-    def __init__(self, levels, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
-        self.levels = self.checked_levels(levels)
-        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
-        self.pooled = None
+    scans = ('ue_hist',)
+    RESULT, ROWS, KEYS, metrics = 'ue_hist', 4, ev.UE_CURVE_KEYS, staticmethod(ev.ue_curve_metrics)
+    FILES = (UE_CURVES_PLACEHOLDER, UE_CURVES_POOLED_PLACEHOLDER, UE_LEVELS_PLACEHOLDER)
+    LEVELS_COLUMNS = ('level', 'threshold', 'tp', 'tn', 'fp', 'fn')
 
-    def setup_run(self):
-        self.subject_rows(UE_CURVES_PLACEHOLDER, ev.UE_CURVE_KEYS)
-        self.pooled = np.zeros((4, self.levels), dtype=np.uint64)
-
-    def record_histogram(self, hist, subject_name):
-        """One subject's level histogram ``[4, levels]``: its metrics row, and its share of the pooled histogram."""
-        self.eval_cases[0].record(ev.ue_curve_metrics(hist), subject_name, self.id_)
-        self.pooled += np.asarray(hist, dtype=np.uint64)
-
-    def eval_subject(self, sf, loader):
-        to_eval = self.prepared(sf, loader)
-        self.record_histogram(ev.uncertainty_histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], self.levels)[0],
-                              sf.subject)
-
-    def finish_eval(self):
-        super().finish_eval()
-        self.write_pooled_row(os.path.join(self.out_dir, UE_CURVES_POOLED_PLACEHOLDER.format(self.id_)), ev.UE_CURVE_KEYS,
-                              ev.ue_curve_metrics(self.pooled))
-        with open(os.path.join(self.out_dir, UE_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['level', 'threshold', 'tp', 'tn', 'fp', 'fn'])
-            for level in range(self.levels):
-                writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]])
+    def histogram(self, prediction, target, uncertainty):
+        return ev.uncertainty_histogram(prediction, target, uncertainty, self.levels)[0]
 
 
-class PatchesAction(UncertaintyAction):
+class PatchesAction(LevelHistogramAction):
     """EXTENSION (the reference has no such action): patch accuracy vs. patch uncertainty (Mukhoti & Gal, 2018) from one patch histogram per
     subject (evaluation.patch_histogram / pavpu_metrics) over a grid of non-overlapping windows of ``patch`` = (depth, height, width) voxels,
     a patch being accurate when more than ``accuracy_per_mille`` / 1000 of its voxels are.  Prepared exactly like ``UeCurvesAction`` -- any
@@ -558,48 +633,32 @@ class PatchesAction(UncertaintyAction):
                                      certain) and p(uncertain | inaccurate) over all patches with "uncertain" := level >= this one (empty
                                      at level 0, where there is no threshold)"""
 
+    scans = ('patches',)
+    RESULT, ROWS, KEYS, metrics = 'patch_hist', 3, ev.PAVPU_KEYS, staticmethod(ev.pavpu_metrics)
+    FILES = (PATCHES_PLACEHOLDER, PATCHES_POOLED_PLACEHOLDER, PATCH_LEVELS_PLACEHOLDER)
+    LEVELS_COLUMNS = PATCH_LEVELS_COLUMNS
+
     def __init__(self, levels, patch, accuracy_per_mille, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
         self.levels = self.checked_levels(levels)
         self.patch, self.accuracy_per_mille = ev._check_patch(patch), ev._check_per_mille(accuracy_per_mille)
-        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
-        self.pooled = None
+        super().__init__(levels, base_dir, rescale_confidence, rescale_sigma, min_max_dir)
 
-    def setup_run(self):
-        self.subject_rows(PATCHES_PLACEHOLDER, ev.PAVPU_KEYS)
-        self.pooled = np.zeros((3, self.levels), dtype=np.uint64)
+    def fused_arguments(self):
+        return {'levels': self.levels, 'patch': self.patch, 'accuracy_per_mille': self.accuracy_per_mille}
 
-    def record_histogram(self, hist, subject_name):
-        """One subject's patch histogram ``[3, levels]``: its metrics row, and its share of the pooled histogram."""
-        self.eval_cases[0].record(ev.pavpu_metrics(hist), subject_name, self.id_)
-        self.pooled += np.asarray(hist, dtype=np.uint64)
+    def histogram(self, prediction, target, uncertainty):
+        return ev.patch_histogram(prediction, target, uncertainty, patch=self.patch, levels=self.levels,
+                                  accuracy_per_mille=self.accuracy_per_mille)[0]
 
-    def eval_subject(self, sf, loader):
-        to_eval = self.prepared(sf, loader)
-        self.record_histogram(ev.patch_histogram(to_eval['prediction'], to_eval['target'], to_eval['uncertainty'], patch=self.patch,
-                                                 levels=self.levels, accuracy_per_mille=self.accuracy_per_mille)[0], sf.subject)
-
-    def finish_eval(self):
-        super().finish_eval()
-        self.write_pooled_row(os.path.join(self.out_dir, PATCHES_POOLED_PLACEHOLDER.format(self.id_)), ev.PAVPU_KEYS, ev.pavpu_metrics(self.pooled))
-        curve = ev.pavpu_curve(self.pooled)
-        with open(os.path.join(self.out_dir, PATCH_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(PATCH_LEVELS_COLUMNS)
-            for level in range(self.levels):
-                writer.writerow([level, level / self.levels] + [int(v) for v in self.pooled[:, level]] + list(curve[level] or ('', '', '')))
+    def extra_levels_columns(self):
+        return [list(point or ('', '', '')) for point in ev.pavpu_curve(self.pooled)]
 
 
-class ComponentsAction(UncertaintyAction):
-    """EXTENSION (the reference has no such action): component-level uncertainty metrics from connected components labelled on the GPU
-    (evaluation.component_table / component_metrics).  The uncertainty is prepared exactly like ``UeCurvesAction``'s -- the entropy of a
-    probability map in registers, the rescaled map of a 'confidence' / 'sigma' run -- and there is no brain mask.  Files in
-    ``<base_dir>/uncertainty``:
-      eval_components_<id>.csv          one row per subject: the keys of evaluation.COMPONENT_METRIC_KEYS
-      eval_components_pooled_<id>.csv   the same metrics of all subjects' tables together (whatever the batching or the subject order)
-      eval_component_list_<id>.csv      one row per predicted component: subject, component (1..K in raster order of first voxels), root_index,
-                                        voxels, target_voxels, mean_uncertainty, max_uncertainty, is_fp"""
+class RegionTablesAction(UncertaintyAction):
+    """What ``ComponentsAction`` and ``LesionsAction`` share: ``levels`` and the check of ``connectivity``, a run's tables and the rows
+    of its list file (one row per region: ``LIST_PLACEHOLDER``, ``LIST_HEADER``), next to the file of one row per subject."""
 
-    LIST_HEADER = ('subject', 'component', 'root_index', 'voxels', 'target_voxels', 'mean_uncertainty', 'max_uncertainty', 'is_fp')
+    SUBJECT_PLACEHOLDER = KEYS = LIST_PLACEHOLDER = LIST_HEADER = None
 
     def __init__(self, levels, connectivity, base_dir, rescale_confidence='', rescale_sigma='global', min_max_dir=None):
         self.levels, self.connectivity = self.checked_levels(levels), int(connectivity)
@@ -609,8 +668,32 @@ class ComponentsAction(UncertaintyAction):
         self.tables, self.list_rows = [], []
 
     def setup_run(self):
-        self.subject_rows(COMPONENTS_PLACEHOLDER, ev.COMPONENT_METRIC_KEYS)
+        self.subject_rows(self.SUBJECT_PLACEHOLDER, self.KEYS)
         self.tables, self.list_rows = [], []
+
+    def write_list(self):
+        write_table(self.path(self.LIST_PLACEHOLDER), self.LIST_HEADER, self.list_rows)
+
+
+class ComponentsAction(RegionTablesAction):
+    """EXTENSION (the reference has no such action): component-level uncertainty metrics from connected components labelled on the GPU
+    (evaluation.component_table / component_metrics).  The uncertainty is prepared exactly like ``UeCurvesAction``'s -- the entropy of a
+    probability map in registers, the rescaled map of a 'confidence' / 'sigma' run -- and there is no brain mask.  Files in
+    ``<base_dir>/uncertainty``:
+      eval_components_<id>.csv          one row per subject: the keys of evaluation.COMPONENT_METRIC_KEYS
+      eval_components_pooled_<id>.csv   the same metrics of all subjects' tables together (whatever the batching or the subject order)
+      eval_component_list_<id>.csv      one row per predicted component: subject, component (1..K in raster order of first voxels), root_index,
+                                        voxels, target_voxels, mean_uncertainty, max_uncertainty, is_fp"""
+
+    scans = ('components',)
+    SUBJECT_PLACEHOLDER, KEYS, LIST_PLACEHOLDER = COMPONENTS_PLACEHOLDER, ev.COMPONENT_METRIC_KEYS, COMPONENT_LIST_PLACEHOLDER
+    LIST_HEADER = ('subject', 'component', 'root_index', 'voxels', 'target_voxels', 'mean_uncertainty', 'max_uncertainty', 'is_fp')
+
+    def fused_arguments(self):
+        return {'connectivity': self.connectivity}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        self.record_tables(*res['components'][slot], subject)
 
     def record_tables(self, pred_table, target_table, subject_name):
         """One subject's two tables: its metrics row, its components' rows, and its share of the pooled tables."""
@@ -632,14 +715,11 @@ class ComponentsAction(UncertaintyAction):
         empty = np.zeros(0, dtype=ev.COMPONENT_DTYPE)
         pooled = ev.component_metrics(np.concatenate([empty] + [t[0] for t in self.tables]), np.concatenate([empty] + [t[1] for t in self.tables]),
                                       self.levels)
-        self.write_pooled_row(os.path.join(self.out_dir, COMPONENTS_POOLED_PLACEHOLDER.format(self.id_)), ev.COMPONENT_METRIC_KEYS, pooled)
-        with open(os.path.join(self.out_dir, COMPONENT_LIST_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(self.LIST_HEADER)
-            writer.writerows(self.list_rows)
+        self.write_pooled_row(self.path(COMPONENTS_POOLED_PLACEHOLDER), self.KEYS, pooled)
+        self.write_list()
 
 
-class LesionsAction(UncertaintyAction):
+class LesionsAction(RegionTablesAction):
     """EXTENSION (the reference has no such action): lesion-wise metrics -- BraTS 2023's lesion-wise Dice, lesion F1, panoptic quality, a
     one-to-one matching and the filtering of predicted lesions by their uncertainty -- from the joint table of the predicted components and
     the target's lesions, made on the GPU (evaluation.lesion_tables / lesion_metrics).  The uncertainty is prepared exactly like
@@ -650,25 +730,25 @@ class LesionsAction(UncertaintyAction):
       eval_lesion_curve_<id>.csv     the pooled filtering curve, one row per threshold k / levels: level, threshold and the keys of
                                      evaluation.LESION_CURVE_KEYS with the components of mean uncertainty > threshold removed"""
 
+    scans = ('lesions',)
+    SUBJECT_PLACEHOLDER, KEYS, LIST_PLACEHOLDER = LESIONS_PLACEHOLDER, ev.LESION_METRIC_KEYS, LESION_LIST_PLACEHOLDER
     LIST_HEADER = ('subject',) + ev.LESION_LIST_KEYS
 
     def __init__(self, levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, rescale_confidence='', rescale_sigma='global',
                  min_max_dir=None):
-        self.levels, self.connectivity = self.checked_levels(levels), int(connectivity)
-        if self.connectivity not in (6, 26):
-            raise ValueError('connectivity must be 6 or 26, got {}'.format(connectivity))
+        super().__init__(levels, connectivity, base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.merge_radius = ev._check_merge_radius(merge_radius)
         self.min_lesion_voxels, self.match_iou = int(min_lesion_voxels), float(match_iou)
         if self.min_lesion_voxels < 0:
             raise ValueError('min_lesion_voxels must be >= 0, got {}'.format(min_lesion_voxels))
         if not 0.5 <= self.match_iou < 1.0:
             raise ValueError('match_iou must be in [0.5, 1): only above an IoU of 0.5 is the matching one-to-one; got {}'.format(match_iou))
-        super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
-        self.tables, self.list_rows = [], []
 
-    def setup_run(self):
-        self.subject_rows(LESIONS_PLACEHOLDER, ev.LESION_METRIC_KEYS)
-        self.tables, self.list_rows = [], []
+    def fused_arguments(self):
+        return {'connectivity': self.connectivity, 'merge_radius': self.merge_radius}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        self.record_tables(res['lesions'][slot], subject)
 
     def analysis(self, tables):
         return ev.lesion_analysis(tables, self.levels, self.match_iou, self.min_lesion_voxels)
@@ -688,16 +768,10 @@ class LesionsAction(UncertaintyAction):
     def finish_eval(self):
         super().finish_eval()
         pooled, curve, _ = self.analysis([t for _, t in sorted(self.tables, key=lambda entry: entry[0])])
-        self.write_pooled_row(os.path.join(self.out_dir, LESIONS_POOLED_PLACEHOLDER.format(self.id_)), ev.LESION_METRIC_KEYS, pooled)
-        with open(os.path.join(self.out_dir, LESION_LIST_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(self.LIST_HEADER)
-            writer.writerows(self.list_rows)
-        with open(os.path.join(self.out_dir, LESION_CURVE_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['level', 'threshold'] + list(ev.LESION_CURVE_KEYS))
-            for k, row in enumerate(curve):
-                writer.writerow([k, k / self.levels] + [row[key] for key in ev.LESION_CURVE_KEYS])
+        self.write_pooled_row(self.path(LESIONS_POOLED_PLACEHOLDER), self.KEYS, pooled)
+        self.write_list()
+        write_table(self.path(LESION_CURVE_PLACEHOLDER), ['level', 'threshold'] + list(ev.LESION_CURVE_KEYS),
+                    ([k, k / self.levels] + [row[key] for key in ev.LESION_CURVE_KEYS] for k, row in enumerate(curve)))
 
 
 class BoundaryAction(UncertaintyAction):
@@ -713,6 +787,7 @@ class BoundaryAction(UncertaintyAction):
       eval_boundary_bands_<id>.csv    the pooled table, one row per (side, band): side, band, voxels, errors, unc_sum, unc_err_sum and
                                       evaluation.BOUNDARY_BAND_KEYS"""
 
+    scans = ('boundary',)
     SURFACE_KEYS = ('hd', 'hd95', 'assd')
     OFF_BORDER_KEYS = tuple(k + '_off_border' for k in ev.UE_CURVE_KEYS)
     SUBJECT_KEYS = ev.BOUNDARY_TABLE_KEYS + SURFACE_KEYS + OFF_BORDER_KEYS
@@ -724,6 +799,12 @@ class BoundaryAction(UncertaintyAction):
             raise ValueError('bands must be in 1..{}, got {}'.format(ev._lib.RCU_BOUNDARY_MAX_BANDS, bands))
         super().__init__(base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.pooled_table = self.pooled_hist = None
+
+    def fused_arguments(self):
+        return {'levels': self.levels, 'bands': self.bands}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        self.record_boundary(*res['boundary'][slot], subject)
 
     def setup_run(self):
         self.subject_rows(BOUNDARY_PLACEHOLDER, self.SUBJECT_KEYS)
@@ -756,16 +837,11 @@ class BoundaryAction(UncertaintyAction):
 
     def finish_eval(self):
         super().finish_eval()
-        self.write_pooled_row(os.path.join(self.out_dir, BOUNDARY_POOLED_PLACEHOLDER.format(self.id_)), self.POOLED_KEYS,
-                              self._row(self.pooled_table, self.pooled_hist))
+        self.write_pooled_row(self.path(BOUNDARY_POOLED_PLACEHOLDER), self.POOLED_KEYS, self._row(self.pooled_table, self.pooled_hist))
         bands = ev.boundary_metrics(self.pooled_table)
-        with open(os.path.join(self.out_dir, BOUNDARY_BANDS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['side', 'band'] + list(ev.BOUNDARY_DTYPE.names) + list(ev.BOUNDARY_BAND_KEYS))
-            for side in range(2):
-                for band in range(self.bands + 1):
-                    writer.writerow([side, band] + [int(self.pooled_table[side, band][k]) for k in ev.BOUNDARY_DTYPE.names] +
-                                    [float(bands[k][side, band]) for k in ev.BOUNDARY_BAND_KEYS])
+        write_table(self.path(BOUNDARY_BANDS_PLACEHOLDER), ['side', 'band'] + list(ev.BOUNDARY_DTYPE.names) + list(ev.BOUNDARY_BAND_KEYS),
+                    ([side, band] + [int(self.pooled_table[side, band][k]) for k in ev.BOUNDARY_DTYPE.names] +
+                     [float(bands[k][side, band]) for k in ev.BOUNDARY_BAND_KEYS] for side in range(2) for band in range(self.bands + 1)))
 
 
 def read_recalibration_map(path, levels):
@@ -778,7 +854,7 @@ def read_recalibration_map(path, levels):
     return np.array([float(r['isotonic']) for r in rows], dtype=np.float64)
 
 
-class CalibCurvesAction(EvalAction):
+class CalibCurvesAction(PreparedAction):
     """EXTENSION (the reference's calibration measure is a 10-bin ECE): proper scoring rules, the Brier decomposition, equal-width /
     equal-mass / maximum / Kolmogorov-Smirnov calibration errors and a reliability curve from one calibration level histogram per subject
     (evaluation.calibration_levels / calibration_curve_metrics), prepared exactly like ``EceCalibrationAction`` -- every confidence entry,
@@ -791,9 +867,10 @@ class CalibCurvesAction(EvalAction):
     ``recalibrate_from``: such a levels file of ANOTHER run evaluated with the same ``levels``; its isotonic map adds the columns
     ``brier_recal``, ``nll_recal``, ``ece_recal`` to the two metrics files."""
 
+    scans = ('calib_levels',)
+
     def __init__(self, levels, base_dir, details='', calib_bins=10, mass_bins=10, recalibrate_from=None, rescale_confidence='subject',
                  rescale_sigma='subject', min_max_dir=None):
-        super().__init__()
         self.levels, self.calib_bins, self.mass_bins = int(levels), int(calib_bins), int(mass_bins)
         if not 2 <= self.levels <= ev._lib.RCU_CALIB_CURVE_MAX_LEVELS:
             raise ValueError('levels must be in 2..{}, got {}'.format(ev._lib.RCU_CALIB_CURVE_MAX_LEVELS, levels))
@@ -803,19 +880,17 @@ class CalibCurvesAction(EvalAction):
             raise ValueError('mass_bins must be >= 1, got {}'.format(mass_bins))
         self.recalibration = None if recalibrate_from is None else read_recalibration_map(recalibrate_from, self.levels)
         self.keys = ev.CALIB_CURVE_KEYS + (ev.CALIB_RECAL_KEYS if self.recalibration is not None else ())
-        self.need_mask = details == 'foreground'
-        self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
-        self.out_dir = os.path.join(base_dir, CALIB_NAME)
-        os.makedirs(self.out_dir, exist_ok=True)
+        super().__init__(ev.get_probability_preparation, CALIB_NAME, details == 'foreground', base_dir, rescale_confidence, rescale_sigma, min_max_dir)
         self.pooled_levels = self.pooled_totals = None
 
-    def setup_eval(self, eval_data):
-        rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
-        self.prepare, self.id_ = ev.get_probability_preparation(eval_data.confidence_entry, eval_data.id_,
-                                                                self.rescale_confidence, self.rescale_sigma, mm)
-        self.load_params = Loader.Params(eval_data.confidence_entry, need_t2_mask=self.need_mask)
-        self.eval_cases = [EvalCase(None, WriteCsvHook(os.path.join(self.out_dir, CALIB_CURVES_PLACEHOLDER.format(self.id_)), entries=self.keys))]
+    def fused_arguments(self):
+        return {'levels': self.levels, 'mask': self.need_mask}
+
+    def record_fused(self, res, slot, subject, n_dim):
+        self.record_levels(res['calib_levels'][slot], res['calib_totals'][slot], subject)
+
+    def setup_run(self):
+        self.subject_rows(CALIB_CURVES_PLACEHOLDER, self.keys)
         # Python integers: the pooled sum of Q(p) of a few hundred BraTS subjects can pass 2^63
         self.pooled_levels = np.zeros((3, self.levels), dtype=object)
         self.pooled_totals = np.zeros((2, 4), dtype=object)
@@ -830,30 +905,22 @@ class CalibCurvesAction(EvalAction):
         self.pooled_totals += np.asarray(totals).astype(object)
 
     def eval_subject(self, sf, loader):
-        to_eval = loader.get_data(sf, self.load_params)
-        if self.prepare:
-            to_eval = self.prepare(to_eval)
+        to_eval = self.prepared(sf, loader)
         levels, totals = ev.calibration_levels(to_eval['probabilities'], to_eval['target'], self.levels,
                                                mask=to_eval['mask'] if self.need_mask else None)
         self.record_levels(levels[0], totals[0], sf.subject)
 
     def finish_eval(self):
         super().finish_eval()
-        row = self.metrics(self.pooled_levels, self.pooled_totals)
-        with open(os.path.join(self.out_dir, CALIB_CURVES_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id'] + list(self.keys))
-            writer.writerow([self.id_] + [row[k] for k in self.keys])
+        self.write_pooled_row(self.path(CALIB_CURVES_POOLED_PLACEHOLDER), self.keys, self.metrics(self.pooled_levels, self.pooled_totals))
         thresholds = [0.0] + [float(t) for t in ev.calibration_thresholds(self.levels)]
         isotonic = ev.isotonic_levels(self.pooled_levels)
-        with open(os.path.join(self.out_dir, CALIB_LEVELS_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(CALIB_LEVELS_COLUMNS)
-            for level in range(self.levels):
-                n_neg, n_pos, conf = (int(v) for v in self.pooled_levels[:, level])
-                n = n_neg + n_pos
-                writer.writerow([level, thresholds[level], n_neg, n_pos, conf / (n << 32) if n else '', n_pos / n if n else '',
-                                 float(isotonic[level])])
+        rows = []
+        for level in range(self.levels):
+            n_neg, n_pos, conf = (int(v) for v in self.pooled_levels[:, level])
+            n = n_neg + n_pos
+            rows.append([level, thresholds[level], n_neg, n_pos, conf / (n << 32) if n else '', n_pos / n if n else '', float(isotonic[level])])
+        write_table(self.path(CALIB_LEVELS_PLACEHOLDER), CALIB_LEVELS_COLUMNS, rows)
 
 
 def read_agreement_csv(path):
@@ -885,6 +952,8 @@ class AgreementAction(EvalAction):
       eval_agreement_pooled_<id>.csv   one row per score: Pearson and Spearman correlation with Dice over the subjects, AUROC of detecting
                                        dice < ``dice_fail`` by the score (low agreement / high volume spread = failure; ties count half)"""
 
+    scans = ('ue',)           # (its Dice comes from the confusion counts)
+
     def __init__(self, base_dir, dice_fail=0.8):
         super().__init__()
         self.dice_fail = float(dice_fail)
@@ -898,8 +967,7 @@ class AgreementAction(EvalAction):
         self.load_params = Loader.Params(eval_data.confidence_entry)
         self.table = read_agreement_csv(os.path.join(eval_data.eval_path, AGREEMENT_FILE))
         self.dice, self.scores = [], {k: [] for k in AGREEMENT_SCORES}
-        hook = WriteCsvHook(os.path.join(self.out_dir, AGREEMENT_PLACEHOLDER.format(self.id_)), entries=('dice',) + tuple(AGREEMENT_SCORES))
-        self.eval_cases = [EvalCase(None, hook)]
+        self.eval_cases = [EvalCase(None, WriteCsvHook(self.path(AGREEMENT_PLACEHOLDER), entries=('dice',) + tuple(AGREEMENT_SCORES)))]
 
     def record_dice(self, dice, subject_name):
         row = self.table.get(str(subject_name))
@@ -917,16 +985,15 @@ class AgreementAction(EvalAction):
         tp, _, fp, fn, _ = ev.confusion_matrx(to_eval['prediction'], to_eval['target'])
         self.record_dice(ev._dice(tp, fp, fn), sf.subject)
 
+    def record_fused(self, res, slot, subject, n_dim):
+        tp, _, fp, fn = _confusion(res, slot)
+        self.record_dice(ev._dice(tp, fp, fn), subject)
+
     def finish_eval(self):
         super().finish_eval()
-        with open(os.path.join(self.out_dir, AGREEMENT_POOLED_PLACEHOLDER.format(self.id_)), 'w', newline='') as f:
-            writer = csv.writer(f)
-            writer.writerow(['test_id', 'score', 'pearson', 'spearman', 'auroc_dice_below_{}'.format(self.dice_fail), 'subjects', 'failed'])
-            for row in agreement_pooled_rows(self.dice, self.scores, self.dice_fail):
-                writer.writerow([self.id_] + row)
-
-
-ECE_TYPES = {EceAction, EceCalibrationAction}
+        write_table(self.path(AGREEMENT_POOLED_PLACEHOLDER),
+                    ['test_id', 'score', 'pearson', 'spearman', 'auroc_dice_below_{}'.format(self.dice_fail), 'subjects', 'failed'],
+                    ([self.id_] + row for row in agreement_pooled_rows(self.dice, self.scores, self.dice_fail)))
 
 
 def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8, calib_bins=10,
@@ -940,31 +1007,19 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
     the IoU above which a component and a lesion match, in [0.5, 1)) and 'patches' (``patch``: the (depth, height, width) extents of its
     windows, each in 1..16; ``patch_accuracy``: a patch is accurate when more than this many per mille of its voxels are; ``levels``: of its
     patch histogram)."""
-    actions = []
-    for name in action_names:
-        if name == 'minmax':
-            actions.append(SaveMinMaxAction(min_max_dir))
-        elif name == 'ece_dice':
-            actions.append(EceAction(base_dir, ece_details, 'subject', 'global', min_max_dir))
-        elif name == 'calib':
-            actions.append(EceCalibrationAction(base_dir, ece_details, 'subject', 'global', min_max_dir))
-        elif name == 'bnf_ue':
-            actions.append(CorrectionAction(ev.UE_THRESHOLDS, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'ue_curves':
-            actions.append(UeCurvesAction(levels, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'patches':
-            actions.append(PatchesAction(levels, patch, patch_accuracy, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'components':
-            actions.append(ComponentsAction(levels, connectivity, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'lesions':
-            actions.append(LesionsAction(levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'boundary':
-            actions.append(BoundaryAction(levels, bands, base_dir, 'subject', 'global', min_max_dir))
-        elif name == 'agreement':      # (``dice_fail``: the Dice below which a segmentation counts as failed)
-            actions.append(AgreementAction(base_dir, dice_fail))
-        elif name == 'calib_curves':
-            actions.append(CalibCurvesAction(levels, base_dir, ece_details, calib_bins, mass_bins, recalibrate_from, 'subject', 'global', min_max_dir))
-    return actions
+    rescale = ('subject', 'global', min_max_dir)
+    table = {'minmax': lambda: SaveMinMaxAction(min_max_dir),
+             'ece_dice': lambda: EceAction(base_dir, ece_details, *rescale),
+             'calib': lambda: EceCalibrationAction(base_dir, ece_details, *rescale),
+             'bnf_ue': lambda: CorrectionAction(ev.UE_THRESHOLDS, base_dir, *rescale),
+             'ue_curves': lambda: UeCurvesAction(levels, base_dir, *rescale),
+             'patches': lambda: PatchesAction(levels, patch, patch_accuracy, base_dir, *rescale),
+             'components': lambda: ComponentsAction(levels, connectivity, base_dir, *rescale),
+             'lesions': lambda: LesionsAction(levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, *rescale),
+             'boundary': lambda: BoundaryAction(levels, bands, base_dir, *rescale),
+             'agreement': lambda: AgreementAction(base_dir, dice_fail),      # (``dice_fail``: the Dice below which a segmentation counts as failed)
+             'calib_curves': lambda: CalibCurvesAction(levels, base_dir, ece_details, calib_bins, mass_bins, recalibrate_from, *rescale)}
+    return [table[name]() for name in action_names if name in table]
 
 
 # ------------------------------------------------------------------------ the fused subject loop
@@ -1049,36 +1104,37 @@ class _LoaderAhead:
         self.reader.close()
 
 
+SCANS = ('ece', 'minmax', 'ue', 'ue_hist', 'components', 'boundary', 'calib_levels', 'lesions', 'patches')      # the order of ``want``
+
+
+def metrics_call(actions):
+    """The one `evaluation.SubjectBatch.metrics` call that serves a list of actions on a probability-map run -> (its keyword arguments:
+    ``want`` = the actions' scans and 'minmax', ``thresholds`` = (0.5,) unless an action fixes them, and whatever else the actions fix;
+    whether the batch holds the brain mask; the arguments two actions fix differently -- with any, one call cannot serve them all)."""
+    fixed, clashes = {}, set()
+    for action in actions:
+        for key, value in action.fused_arguments().items():
+            if fixed.setdefault(key, value) != value:
+                clashes.add(key)
+    scans = {'minmax'}.union(*(action.scans or () for action in actions))
+    fixed.pop('mask', None)       # (an argument of the batch, not of the call)
+    fixed.setdefault('thresholds', (0.5,))
+    return dict(fixed, want=[scan for scan in SCANS if scan in scans]), any(action.need_mask for action in actions), clashes
+
+
 def _fusable(entry, actions):
     """The fused loop covers the runs whose confidence entry IS the probability map (baseline, baseline_mc, center, center_mc, ensemble:
-    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion --, the four actions of the script and the extension actions; the
-    actions that use the brain mask ('ece_dice', 'calib', 'calib_curves') must agree on it: the batch holds one mask."""
-    masks = {bool(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False)) for a in actions if type(a) in ECE_TYPES | {CalibCurvesAction}}
-    return (entry.confidence_entry == 'probabilities' and len(masks) <= 1 and
-            all(type(a) in (SaveMinMaxAction, EceAction, EceCalibrationAction, CorrectionAction, UeCurvesAction, ComponentsAction, BoundaryAction,
-                            AgreementAction, CalibCurvesAction, LesionsAction, PatchesAction)
-                for a in actions) and
-            all(ev.from_p_supported(a.thresholds) for a in actions if isinstance(a, CorrectionAction)))
+    evaldata.py:21-47) -- no rescaling, no uncertainty-to-probability conversion -- when every action can be recorded from the scans of
+    `SubjectBatch.metrics` and no two actions fix different values for one of its arguments: the batch holds one mask ('ece_dice', 'calib'
+    and 'calib_curves' must agree on it), the level histograms of one call have one number of levels."""
+    return entry.confidence_entry == 'probabilities' and all(a.scans is not None for a in actions) and not metrics_call(actions)[2]
 
 
 def metrics_wanted(actions):
-    """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the ECE actions use a mask) for a
-    list of actions on a probability-map run ('ue_hist' is wanted by a UeCurvesAction, which also holds the `levels` to ask for, 'components'
-    by a ComponentsAction, which holds the `connectivity`, 'boundary' by a BoundaryAction, which holds the `bands`, 'calib_levels' by a
-    CalibCurvesAction, which holds `levels` as well, 'lesions' by a LesionsAction, which holds `connectivity` and `merge_radius`, 'patches' by
-    a PatchesAction, which holds `levels`, `patch` and `accuracy_per_mille`)."""
-    by_type = {type(a): a for a in actions}
-    want = (['ece'] if (ECE_TYPES & set(by_type)) else []) + ['minmax'] + \
-           (['ue'] if (CorrectionAction in by_type or AgreementAction in by_type or (ECE_TYPES & set(by_type))) else []) + \
-           (['ue_hist'] if UeCurvesAction in by_type else []) + \
-           (['components'] if ComponentsAction in by_type else []) + \
-           (['boundary'] if BoundaryAction in by_type else []) + \
-           (['calib_levels'] if CalibCurvesAction in by_type else []) + \
-           (['lesions'] if LesionsAction in by_type else []) + \
-           (['patches'] if PatchesAction in by_type else [])
-    ue = by_type.get(CorrectionAction)
-    want_mask = any(getattr(a, 'need_t2_mask', False) or getattr(a, 'need_mask', False) for a in actions)
-    return want, (tuple(ue.thresholds) if ue is not None else (0.5,)), want_mask
+    """(`want` of evaluation.SubjectBatch.metrics, thresholds of the uncertainty-error counts, whether the batch holds a mask) for a list of
+    actions on a probability-map run."""
+    call, with_mask, _ = metrics_call(actions)
+    return call['want'], call['thresholds'], with_mask
 
 
 def record_subject(actions, subject, res, slot, n_dim):
@@ -1086,46 +1142,13 @@ def record_subject(actions, subject, res, slot, n_dim):
     value types) the per-action strategies of the reference-ordered loop produce."""
     mn, mx = res['min'][slot], res['max'][slot]
     # helper.add_background_probability's range check (rechun/eval/helper.py:8-12, 31-47), on the device's min / max
-    if any(not isinstance(a, SaveMinMaxAction) for a in actions):
+    if any(a.checks_range for a in actions):
         if mx > 1:
             raise ValueError('Found value larger than 1: "{}"'.format(mx))
         if mn < 0:
             raise ValueError('Found value smaller than 0: "{}"'.format(mn))
-    counts = res['counts'][slot] if 'counts' in res else None
     for action in actions:
-        if isinstance(action, SaveMinMaxAction):
-            action.eval_cases[0].record({'min': mn, 'max': mx}, subject, action.id_)
-        elif isinstance(action, (EceAction, EceCalibrationAction)):
-            hist = [h[slot] for h in res['hist']]
-            tp, tn, fp, fn = (int(v) for v in counts[0][:4])
-            results = {}
-            if isinstance(action, EceCalibrationAction):      # key order of EceBinaryNumpy(return_bins=True) + DiceNumpy
-                ece = ev.ece_from_histogram(*hist, n_dim=n_dim, out_bins=results)
-                results['ece'] = ece
-                results['dice'] = ev._dice(tp, fp, fn)
-            else:
-                results['ece'] = ev.ece_from_histogram(*hist, n_dim=n_dim)
-                results['dice'] = ev._dice(tp, fp, fn)
-                results.update(tp=tp, tn=tn, fp=fp, fn=fn, n=tp + tn + fp + fn)
-            action.eval_cases[0].record(results, subject, action.id_)
-        elif isinstance(action, CorrectionAction):
-            for t, case in enumerate(action.eval_cases):
-                case.record(ev.correction_results(counts[t]), subject, action.id_)
-        elif isinstance(action, UeCurvesAction):
-            action.record_histogram(res['ue_hist'][slot], subject)
-        elif isinstance(action, PatchesAction):
-            action.record_histogram(res['patch_hist'][slot], subject)
-        elif isinstance(action, ComponentsAction):
-            action.record_tables(res['components'][slot][0], res['components'][slot][1], subject)
-        elif isinstance(action, LesionsAction):
-            action.record_tables(res['lesions'][slot], subject)
-        elif isinstance(action, BoundaryAction):
-            action.record_boundary(*res['boundary'][slot], subject)
-        elif isinstance(action, AgreementAction):      # (the counts are there whenever the action is: metrics_wanted)
-            tp, _, fp, fn = (int(v) for v in counts[0][:4])
-            action.record_dice(ev._dice(tp, fp, fn), subject)
-        elif isinstance(action, CalibCurvesAction):
-            action.record_levels(res['calib_levels'][slot], res['calib_totals'][slot], subject)
+        action.record_fused(res, slot, subject, n_dim)
 
 
 def _evaluate_fused(entry, actions, batch_subjects, timing):
@@ -1134,12 +1157,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
     the mask (ece_dice and calib share it), the uncertainty-error counts of all thresholds from the probability map (their tp / tn / fp /
     fn are ece_dice's confusion matrix), min / max -- and the results fanned out to the actions' CSV hooks in subject order.  The rows are
     those of the per-action loop, byte for byte (tests/test_gpu_parity.py)."""
-    want, thresholds, want_mask = metrics_wanted(actions)
-    levels = next((a.levels for a in actions if isinstance(a, (UeCurvesAction, BoundaryAction, CalibCurvesAction, PatchesAction))), ev.UE_LEVELS)
-    patch, patch_accuracy = next(((a.patch, a.accuracy_per_mille) for a in actions if isinstance(a, PatchesAction)), (ev.PATCH_DEFAULT, 500))
-    bands = next((a.bands for a in actions if isinstance(a, BoundaryAction)), 10)
-    connectivity = next((a.connectivity for a in actions if isinstance(a, (ComponentsAction, LesionsAction))), 26)
-    merge_radius = next((a.merge_radius for a in actions if isinstance(a, LesionsAction)), 0)
+    call, want_mask, _ = metrics_call(actions)
     params = Loader.Params('probabilities', need_target=True, need_prediction=True, need_t2_mask=want_mask)
     files = entry.subject_files
     reader = _ReadAhead(files, params, depth=2 * batch_subjects)
@@ -1166,8 +1184,7 @@ def _evaluate_fused(entry, actions, batch_subjects, timing):
                 batch.put(slot, d['probabilities'], d['prediction'], d['target'], d.get('mask'))
             t_stage = time.perf_counter()
             batch.upload()
-            res = batch.metrics(thresholds=thresholds, want=want, levels=levels, connectivity=connectivity, bands=bands, merge_radius=merge_radius,
-                                patch=patch, accuracy_per_mille=patch_accuracy)
+            res = batch.metrics(**call)
             t_gpu = time.perf_counter()
             for slot, (k, d) in enumerate(group):
                 record_subject(actions, files[k].subject, res, slot, n_dim)

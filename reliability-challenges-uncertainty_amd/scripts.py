@@ -296,7 +296,7 @@ class DeviceMetricsHook(loops.TestLoopHook):
             raise ValueError('others.device_metrics: unsupported actions {}'.format(self.action_names))
         for action in self.actions:
             action.start_eval()
-        self.want, self.thresholds, self.want_mask = evalrun.metrics_wanted(self.actions)
+        self.call, self.want_mask, _ = evalrun.metrics_call(self.actions)
         if self.gt_dir:
             gts = (evalrun.collect_brats_ground_truth if self.dataset == 'brats' else evalrun.collect_isic_ground_truth)(self.gt_dir)
             self.gts = {sf.subject: sf for sf in gts}
@@ -321,7 +321,7 @@ class DeviceMetricsHook(loops.TestLoopHook):
         self.batch.used = 0
         self.batch.put(0, vol['p'], vol['prediction'], target, mask)
         self.batch.upload()
-        self.rows[name] = (self.batch.metrics(thresholds=self.thresholds, want=self.want), target.ndim)
+        self.rows[name] = (self.batch.metrics(**self.call), target.ndim)
 
     def on_test_end(self, task_context, context):
         for name in sorted(self.rows):       # the evaluation script's subject order (rechun/eval/evaldata.py: sorted by subject)
