@@ -23,7 +23,9 @@ def _int_in(lo, hi):
 def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--ds', type=str, nargs='?', help='the dataset to evaluate the runs on')
-    parser.add_argument('--ids', type=str, nargs='*', help='the ids of the runs to be evaluated')
+    parser.add_argument('--ids', type=str, nargs='*', help='the ids of the runs to be evaluated (default: the reference\'s eight; rcu_amd only, when '
+                        'named: density -- a default run under others.density, whose <subject>_density.nii.gz is rescaled like the aleatoric sigma, '
+                        'run minmax first)')
     parser.add_argument('--act', type=str, nargs='*', help='the names of the evaluation configuration: minmax, ece_dice, calib, bnf_ue (the default: '
                         'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) components '
                         '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice) and '

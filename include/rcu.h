@@ -823,6 +823,44 @@ int rcu_mc_merge_slices(const void* src_stats_dev, size_t m, void* dst_stats_dev
 int rcu_mc_finalize_counts(const void* stats_dev, size_t n, size_t hw, int nb_classes, const int32_t* counts_dev, int flags, float* mean_dev,
                            float* entropy_dev, float* mutual_info_dev, float* variance_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Feature-space density (EXTENSION: the reference has no single-pass epistemic uncertainty; rcu_amd.density, rcu_amd.steps.DensityPredictStep, the
+ * fit_density scripts and the `others.density` key of the two default test scripts -- Mukhoti et al. 2021, Deep Deterministic Uncertainty; Lee et
+ * al. 2018 for the shared covariance)
+ *   Features.  phi(v) in R^F is rcu_unet_features of an eval-mode forward: F real channels at channel_pitch floats per voxel.  1 <= F <=
+ *   RCU_DENSITY_MAX_FEATURES, channel_pitch >= F and a multiple of 4.  Channels F .. pitch - 1 are ignored: they may hold any finite value.
+ *   Classes.  y(v) in {0 .. K - 1}, K <= 8, one uint8 per voxel.
+ *   Moments, per slice s and class c:  n[s][c] = #{v : y(v) = c} (int64),  S[s][c][:] = sum phi (float64 [F]),  G[s][c][:][:] = sum phi phi^T
+ *   (float64 [F][F], BOTH triangles filled, bitwise symmetric).  A float32 accumulator covers one chunk of RCU_DENSITY_CHUNK consecutive voxels of
+ *   the slice (chunk q = voxels [q m, (q + 1) m) of the slice, m = RCU_DENSITY_CHUNK; G: the fp32 MFMA's k-ordered fmaf chain over the chunk's
+ *   voxels; S: the voxels of even and of odd index summed separately); the chunk sums are promoted and added in float64 in chunk order.  The rows of
+ *   slice s are bit for bit a function of that slice's features, labels, hw, F and K: not of n, the slice's position in the batch, the alignment of
+ *   the pointers, the launch geometry or the stream.  Error: |G_ij - exact| <= (m + 1) 2^-24 sum_v |phi_i phi_j|, |S_i - exact| <= (m + 1) 2^-24
+ *   sum_v |phi_i|.
+ *   A label >= K is refused: RCU_ERR_INVALID after the kernels have run (such voxels are left out of every sum); the call reads one word back, so it
+ *   returns with the stream drained.  Classes beyond four (two above 32 channels) cost one more pass over the features each four (two).
+ *   Fit (host, float64; rcu_amd.density.fit_from_moments, tests/density_reference.py).  Per class every entry of n, S and G is summed over all slices
+ *   with an exactly rounded sum (math.fsum; integers for n): the fit does not depend on batching or slice order.  mu_c = S_c / n_c,
+ *   Sigma_c = G_c / n_c - mu_c mu_c^T + ridge (tr Sigma_c / F) I (ridge 1e-6 by default; shared_covariance: the pooled sum_c n_c Sigma_c / sum n
+ *   before the ridge, for every class), L_c = chol(Sigma_c), A_c = L_c^-1 (lower triangular), b_c = A_c mu_c,
+ *   k_c = log(n_c / sum n) - sum log diag L_c - (F / 2) log 2 pi.  A class with n_c <= F is refused.
+ *   Energy.  e(v) = -log sum_c exp(k_c - d2_c(v) / 2), d2_c(v) = |A_c phi(v) - b_c|^2: the negative log density, float32, from A, b, k rounded once
+ *   to float32.  Per class the rows y_i = fma chain over j = 0 .. F - 1 (in the MFMA's order) from -b_i, then d2 = sum y_i^2 in float32, t_c =
+ *   fmaf(-0.5, d2, k_c), and a running logsumexp that subtracts the maximum so far.  A voxel's energy is a function of its F feature values and the
+ *   parameters alone, whatever n_voxels, its position or the presence of d2_dev.  With s_i = sum_j |A_ij phi_j| + |b_i|:
+ *   |d2_c - exact| <= (3 F + 8) 2^-24 sum_i s_i^2.  features_dev must be 16-byte aligned.
+ *   Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it).
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_DENSITY_MAX_FEATURES 64
+#define RCU_DENSITY_CHUNK 1024
+size_t rcu_density_moments_workspace_bytes(size_t n, size_t hw, int F, int K);
+int rcu_density_moments(const float* features_dev, int channel_pitch, int F, const uint8_t* labels_dev /* [n][hw] */, size_t n, size_t hw, int K,
+                        int64_t* n_out_dev /* [n][K] */, double* S_out_dev /* [n][K][F] */, double* G_out_dev /* [n][K][F][F] */, void* workspace_dev,
+                        void* stream);
+int rcu_density_energy(const float* features_dev, int channel_pitch, int F, size_t n_voxels, int K, const float* A_dev /* [K][F][F] */,
+                       const float* b_dev /* [K][F] */, const float* k_dev /* [K] */, float* energy_dev /* [n_voxels] */,
+                       float* d2_dev /* [n_voxels][K] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

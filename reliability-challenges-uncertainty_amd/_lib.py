@@ -183,6 +183,9 @@ SIGNATURES = {
     'rcu_dropout_masks_indexed': (c_int, [POINTER(c_uint64), c_int, c_int, c_void_p, POINTER(c_int32), POINTER(c_float), c_int, c_void_p, c_void_p]),
     'rcu_mc_merge_slices': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     'rcu_mc_finalize_counts': (c_int, [c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_density_moments_workspace_bytes': (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
+    'rcu_density_moments': (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_density_energy': (c_int, [c_void_p, c_int, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

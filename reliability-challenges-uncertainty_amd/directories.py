@@ -21,6 +21,9 @@ ISIC_ORIG_DATA_DIR = _setting('ISIC_ORIG_DATA_DIR')
 RUN_IDS = ('baseline', 'baseline_mc', 'center', 'center_mc', 'ensemble', 'auxiliary_feat', 'auxiliary_segm', 'aleatoric')
 _SETTING_OF_RUN = {'baseline': 'BASELINE', 'baseline_mc': 'BASELINE_MC', 'center': 'CENTER', 'center_mc': 'CENTER_MC',
                    'ensemble': 'ENSEMBLE', 'auxiliary_feat': 'AUX_FEAT', 'auxiliary_segm': 'AUX_SEGM', 'aleatoric': 'ALEATORIC'}
+# rcu_amd extension: run types the reference does not have.  They are evaluated when named (--ids density), never by default (RUN_IDS)
+EXTENSION_RUN_IDS = ('density',)
+_SETTING_OF_RUN['density'] = 'DENSITY'
 for _ds in ('ISIC', 'BRATS'):
     for _run, _key in _SETTING_OF_RUN.items():
         # e.g. BRATS_BASELINE_MC_PREDICT = '<timestamp>_brats_baseline_mc'; unset: the run id itself (out/predictions/brats/baseline_mc)

@@ -69,6 +69,9 @@ AGREEMENT_SCORES = {'mean_pairwise_dice': False, 'min_pairwise_dice': False, 'po
 CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities', 'center': 'probabilities',
                     'center_mc': 'probabilities', 'ensemble': 'probabilities', 'auxiliary_feat': 'confidence',
                     'auxiliary_segm': 'confidence', 'aleatoric': 'sigma'}   # evaldata.py:21-47
+# rcu_amd extension: a default run under others.density -- its {subject}_density.nii.gz (the feature-space energy, rcu_amd.density) is unbounded
+# like sigma and takes sigma's path through every action: the rescale_sigma rescale (global min-max through the minmax action), then an uncertainty
+CONFIDENCE_ENTRY['density'] = 'density'
 
 
 # ------------------------------------------------------------------------------------- CSV hooks
@@ -1227,32 +1230,45 @@ def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=
     actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail, calib_bins,
                           mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou, patch, patch_accuracy)
     for entry in eval_data_list:
-        for action in actions:
-            action.setup_eval(entry)
-        for action in actions:
-            action.start_eval()
-        if fused and entry.subject_files and _fusable(entry, actions):
-            if timing is not None:
-                for key in ('subjects', 'batches', 'wait_for_files_s', 'read_thread_s', 'stage_s', 'upload_and_kernels_s', 'csv_rows_s'):
-                    timing.setdefault(key, 0)
-            _evaluate_fused(entry, actions, max(1, int(batch_subjects)), timing)
-            for action in actions:
-                action.finish_eval()
-            continue
-        # the reference's subject-by-subject, action-by-action order (eval_uncertainty.py:36-46); the files of the coming subjects are read by
-        # the threads of _ReadAhead meanwhile, into the caches of the subjects' Loaders (what an action asks for first is there already)
-        wanted = [a.load_params for a in actions if a.load_params is not None]
-        ahead = _LoaderAhead(entry.subject_files, wanted, depth=4) if (wanted and len(entry.subject_files) > 1) else None
-        try:
-            for i, sf in enumerate(entry.subject_files):
-                print('[{}/{}] {}'.format(i + 1, len(entry.subject_files), sf.subject), end=' ', flush=True)
-                loader = ahead.get(i) if ahead is not None else Loader()
-                start = time.time()
-                for action in actions:
-                    action.eval_subject(sf, loader)
-                print('({}s)'.format(time.time() - start))
-        finally:
-            if ahead is not None:
-                ahead.close()
+        first = [a for a in actions if isinstance(a, SaveMinMaxAction)]
+        rest = [a for a in actions if not isinstance(a, SaveMinMaxAction)]
+        if entry.confidence_entry != 'probabilities' and first and rest:
+            # the global rescale of a confidence / sigma / density entry reads the file the minmax action writes for this run, at set-up time:
+            # `--act minmax ue_curves` in ONE call runs the minmax action over the run first (a call without minmax reads an earlier call's file)
+            _evaluate_entry(entry, first, fused, batch_subjects, timing)
+            _evaluate_entry(entry, rest, fused, batch_subjects, timing)
+        else:
+            _evaluate_entry(entry, actions, fused, batch_subjects, timing)
+
+
+def _evaluate_entry(entry, actions, fused, batch_subjects, timing):
+    """One run through ``actions`` (evaluate_runs)."""
+    for action in actions:
+        action.setup_eval(entry)
+    for action in actions:
+        action.start_eval()
+    if fused and entry.subject_files and _fusable(entry, actions):
+        if timing is not None:
+            for key in ('subjects', 'batches', 'wait_for_files_s', 'read_thread_s', 'stage_s', 'upload_and_kernels_s', 'csv_rows_s'):
+                timing.setdefault(key, 0)
+        _evaluate_fused(entry, actions, max(1, int(batch_subjects)), timing)
         for action in actions:
             action.finish_eval()
+        return
+    # the reference's subject-by-subject, action-by-action order (eval_uncertainty.py:36-46); the files of the coming subjects are read by
+    # the threads of _ReadAhead meanwhile, into the caches of the subjects' Loaders (what an action asks for first is there already)
+    wanted = [a.load_params for a in actions if a.load_params is not None]
+    ahead = _LoaderAhead(entry.subject_files, wanted, depth=4) if (wanted and len(entry.subject_files) > 1) else None
+    try:
+        for i, sf in enumerate(entry.subject_files):
+            print('[{}/{}] {}'.format(i + 1, len(entry.subject_files), sf.subject), end=' ', flush=True)
+            loader = ahead.get(i) if ahead is not None else Loader()
+            start = time.time()
+            for action in actions:
+                action.eval_subject(sf, loader)
+            print('({}s)'.format(time.time() - start))
+    finally:
+        if ahead is not None:
+            ahead.close()
+    for action in actions:
+        action.finish_eval()

@@ -9,6 +9,7 @@ Each function is the ``main`` of the same-named reference script (flags unchange
     bin-dl/{brats,isic}_test_auxiliary_segm.py -config_file       (bin-dl/brats_test_auxiliary_segm.py:23-47)
     bin-eval/eval_uncertainty.py   --ds --ids --act               (bin-eval/eval_uncertainty.py:13-50, 248-288)
     bin-dl/{brats,isic}_fit_temperature.py -config_file           (EXTENSION: temperature scaling, fit_temperature)
+    bin-dl/{brats,isic}_fit_density.py -config_file               (EXTENSION: feature-space density, fit_density)
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
 """
@@ -24,6 +25,7 @@ from . import _lib
 from . import calibration
 from . import corruption as corruption_mod
 from . import data as data_mod
+from . import density as density_mod
 from . import distributed as rdist
 from . import evalrun
 from . import evaluation as ev
@@ -633,6 +635,53 @@ def _refuse_corruption(context, script):
                          'fitted on clean validation data'.format(script))
 
 
+def _refuse_density(context, script):
+    if hasattr(context.config.others, 'density'):
+        raise ValueError('others.density (feature-space density uncertainty) applies to the default test scripts only; the {} script does not take '
+                         'it'.format(script))
+
+
+def _density(context):
+    """``others.density: <path to density.npz>`` (an rcu_amd extension, include/rcu.h "Feature-space density"; the fit_density scripts write the
+    file): the deterministic default run with the energy of the fitted class Gaussians as one more map per subject -> the DensityFit, or None
+    without the key.  One eval-mode pass per batch: a ValueError that names both keys beside the keys that sample (mc, tta, agreement, mc_adaptive,
+    logit_samples).  Composes with others.corruption and others.temperature (which rescales conv_cls.1 alone: the features do not move)."""
+    if not hasattr(context.config.others, 'density'):
+        return None
+    for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples'):
+        if hasattr(context.config.others, key) and not (key == 'agreement' and getattr(context.config.others, key) is False):
+            raise ValueError('others.density does not compose with others.{}: the density map belongs to the one deterministic pass'.format(key))
+    value = context.config.others.density
+    if not isinstance(value, (str, os.PathLike)):
+        raise ValueError('others.density must be the path of a density.npz (bin-dl/*_fit_density.py), got {!r}'.format(value))
+    try:
+        return density_mod.load_density(value)
+    except ValueError as e:
+        raise ValueError('others.density: {}'.format(e)) from None
+
+
+class DensityWriteHook(loops.TestLoopHook):
+    """``others.density``: ``{subject}_density.nii.gz``, the float32 energy of the subject's voxels (``output['density']``, assembled like the
+    probabilities), written beside the files of the run -- whose names and bytes it leaves alone."""
+
+    def __init__(self, in_background=True):
+        self.in_background = in_background
+
+    def on_test_subject_end(self, subject_context, task_context, context):
+        data = subject_context.subject_data
+        energy = data.get('density')
+        if energy is None:
+            raise ValueError('others.density: subject {} came without its density map'.format(subject_context.subject_index))
+        subject = data.get('subject', subject_context.subject_index)
+        energy = np.asarray(energy)
+        energy = np.ascontiguousarray(energy[..., 0] if energy.shape[-1] == 1 else energy, dtype=np.float32)
+        properties, path = data.get('properties'), os.path.join(context.test_dir, '{}_density.nii.gz'.format(subject))
+        nifti.do_work(lambda: nifti.write(path, energy, properties), in_background=self.in_background)
+
+    def on_termination(self, context):
+        nifti.join_all()
+
+
 def _default_steps(context, world):
     adaptive = _adaptive(context, world)      # (refuses others.mc_adaptive beside tta, agreement, exact: false, several ranks, or without mc)
     if hasattr(context.config.others, 'tta'):
@@ -788,11 +837,17 @@ def _abandon_process_group(timeout_s=10.0):
 
 def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
+    density_fit = _density(context)      # (refuses others.density beside the keys that sample)
     _refuse_logit_samples(context, 'default')
     entries = ('probabilities',) if dataset == 'brats' else None
     corrupt_steps, corrupt_hooks = _corruption(context)
-    test_steps = corrupt_steps + _default_steps(context, world)
     extra = []
+    if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
+        test_steps = corrupt_steps + [steps.DensityPredictStep(density_fit)]
+        entries = None if entries is None else entries + ('density',)
+        extra.append(DensityWriteHook())
+    else:
+        test_steps = corrupt_steps + _default_steps(context, world)
     if any(isinstance(s_, steps.SampleAgreementStep) for s_ in test_steps):
         entries = None if entries is None else entries + ('agreement',)
         extra.append(AgreementCsvHook(context.config.others.mc))
@@ -811,6 +866,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
     _refuse_agreement(context, 'ensemble')
     _refuse_adaptive(context, 'ensemble')
     _refuse_logit_samples(context, 'ensemble')
+    _refuse_density(context, 'ensemble')
     corrupt_steps, corrupt_hooks = _corruption(context)
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
@@ -827,6 +883,7 @@ def test_aleatoric(dataset, config_file=None, device='cuda'):
     _refuse_temperature(context, 'aleatoric')
     _refuse_agreement(context, 'aleatoric')
     _refuse_adaptive(context, 'aleatoric')
+    _refuse_density(context, 'aleatoric')
     corrupt_steps, corrupt_hooks = _corruption(context)
     return _run(context, dataset, corrupt_steps + _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world, startup_hooks=corrupt_hooks)
@@ -973,6 +1030,7 @@ def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
     _refuse_agreement(context, 'auxiliary_feat')
     _refuse_adaptive(context, 'auxiliary_feat')
     _refuse_logit_samples(context, 'auxiliary_feat')
+    _refuse_density(context, 'auxiliary_feat')
     corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
         return context
@@ -999,6 +1057,7 @@ def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
     _refuse_agreement(context, 'auxiliary_segm')
     _refuse_adaptive(context, 'auxiliary_segm')
     _refuse_logit_samples(context, 'auxiliary_segm')
+    _refuse_density(context, 'auxiliary_segm')
     corrupt_steps, corrupt_hooks = _corruption(context)
     if not _single_rank_only(world):
         return context
@@ -1065,6 +1124,7 @@ def fit_temperature(dataset, config_file, device='cuda'):
     _refuse_agreement(context, 'fit_temperature')
     _refuse_adaptive(context, 'fit_temperature')
     _refuse_corruption(context, 'fit_temperature')
+    _refuse_density(context, 'fit_temperature')
     mc = int(getattr(others, 'mc', 0) or 0)
     seed = 0 if context.config.seed is None else int(context.config.seed)
     context.load_from_checkpoint(context.get_test_at())
@@ -1094,7 +1154,49 @@ def fit_temperature(dataset, config_file, device='cuda'):
     return fit
 
 
-for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature):
+def fit_density(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_density.py (EXTENSION): fit the class Gaussians of the feature-space density (rcu_amd.density) on the volumes a test
+    configuration's ``test_data`` names -- the VALIDATION volumes, read as ``fit_temperature`` reads them -- with one eval-mode pass per batch,
+    target labels > 0 (K = 2).  ``others.density_ridge`` (1e-6) and ``others.density_shared_covariance`` (false) are the fit's options.  Writes
+    ``density.npz`` and a readable ``density.json`` into the run directory and returns the fit; ``others.density: <that .npz>`` applies it in the
+    default test scripts."""
+    if dataset not in ('brats', 'isic'):
+        raise ValueError('chose "brats" or "isic" as dataset')
+    context, world = _context(device, config_file)
+    if world.world > 1:
+        raise ValueError('the density fit runs in one process; launch it without torch.distributed.run')
+    others = context.config.others
+    for key in ('tta', 'mc'):
+        if hasattr(others, key):
+            raise ValueError('others.{}: the density fit is one eval-mode pass per batch and does not take it'.format(key))
+    _refuse_temperature(context, 'fit_density')
+    _refuse_logit_samples(context, 'fit_density')
+    _refuse_agreement(context, 'fit_density')
+    _refuse_adaptive(context, 'fit_density')
+    _refuse_corruption(context, 'fit_density')
+    _refuse_density(context, 'fit_density')
+    context.load_from_checkpoint(context.get_test_at())
+    model = context.model
+    density_mod._feature_channels(model)      # (refuses a model that is no U-Net)
+    context.setup_directory()
+    context.setup_logging()
+    context.do_seed(0 if context.config.seed is None else int(context.config.seed))
+    build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
+    context.load_test_data(build)
+    fit = density_mod.fit_density(model, _validation_batches(context, dataset, context.device), ridge=float(_other(context, 'density_ridge', 1e-6)),
+                                  shared_covariance=bool(_other(context, 'density_shared_covariance', False)), nb_classes=2)
+    path = os.path.join(context.test_dir, 'density.npz')
+    density_mod.save_density(fit, path)
+    record = dict(fit.as_dict(), model_dir=context.config.model_dir, test_at=context.config.test_at, dataset=context.config.test_data.dataset)
+    with open(os.path.join(context.test_dir, 'density.json'), 'w') as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write('\n')
+    logging.info('density fit: F = %d, K = %d, counts %s, %d voxels -> %s', fit.F, fit.K, [int(v) for v in fit.n], fit.voxels, path)
+    print('density: {}'.format(path))
+    return fit
+
+
+for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density):
     _fn.__test__ = False   # not pytest tests
 
 

@@ -881,6 +881,34 @@ class SegmentationPredictStep(BatchStep):
             batch_context.output['probabilities'] = softmax(logits)
 
 
+class DensityPredictStep(BatchStep):
+    """EXTENSION -- feature-space density uncertainty (rcu_amd.density, include/rcu.h "Feature-space density") in place of the default predict step:
+    one eval-mode forward with the feature tap, ``output['logits']`` and ``output['probabilities']`` as SegmentationPredictStep(do_probs=True) gives
+    them, and ``output['density']``, the float32 energy ``[N, 1, H, W]`` of ``fit`` (a density.DensityFit), computed from the feature view while
+    it is valid -- before any other forward on that plan."""
+
+    def __init__(self, fit) -> None:
+        super().__init__()
+        from . import density
+        if not isinstance(fit, density.DensityFit):
+            raise ValueError('DensityPredictStep needs a density.DensityFit, got {}'.format(type(fit).__name__))
+        self.fit = fit
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        from . import density
+        _check_context(context)
+        model = context.model
+        channels = density._feature_channels(model)
+        if channels != self.fit.F:
+            raise ValueError('the density fit has F = {} feature channels, the model has {}'.format(self.fit.F, channels))
+        images = _images_to_device(batch_context, context)
+        with density.eval_features(model):
+            logits = model(images)
+            batch_context.output['density'] = density.energy(self.fit, model.features)
+        batch_context.output['logits'] = logits
+        batch_context.output['probabilities'] = softmax(logits)
+
+
 class SampleAgreementStep(BatchStep):
     """Behind the summary: pops ``sample_votes`` (McPredictStep with ``agreement=True``) and writes ``output['agreement']``, one int64 row
     ``[(T + 1) + T (T + 1) / 2]`` per slice -- ``hist`` then the upper triangle ``pairs`` of include/rcu.h's rcu_agreement_tables, one image per
