@@ -33,7 +33,8 @@ def make_parser():
                         '(the run\'s agreement.csv -- written under others.agreement: true -- against each subject\'s Dice: correlations, failure detection) and lesions '
                         '(lesion-wise Dice, lesion F1, panoptic quality and the filtering of predicted lesions by uncertainty, from the joint table of '
                         'predicted components and target lesions) and patches (patch accuracy vs. patch uncertainty of Mukhoti & Gal 2018 -- p(accurate | certain), '
-                        'p(uncertain | inaccurate), PAvPU -- over a grid of non-overlapping windows, from a patch table made on the GPU)')
+                        'p(uncertain | inaccurate), PAvPU -- over a grid of non-overlapping windows, from a patch table made on the GPU) and quantiles '
+                        '(the sibling of minmax for --rescale quantile: the exact quantile table of a sigma / density run, by radix selection on the GPU)')
     parser.add_argument('--pred_dir', type=str, default=None, help='root with one sub-directory per dataset and run id '
                         '(default: directories.PREDICT_DIR and the per-run *_PREDICT names)')
     parser.add_argument('--gt_dir', type=str, default=None, help='BraTS training tree / ISIC dataset prefix '
@@ -62,6 +63,16 @@ def make_parser():
                         'default 1 gives windows on the slices a 2-D network saw, --patch_depth 4 with --patch 4 gives cubes')
     parser.add_argument('--patch_accuracy', type=_int_in(0, 999), default=500, help='rcu_amd: the patches action counts a window as accurate when more '
                         'than this many per mille of its voxels are predicted correctly (0..999)')
+    parser.add_argument('--rescale', type=str, default='minmax', choices=('minmax', 'quantile'), help='rcu_amd: how the unbounded entries (the sigma of '
+                        'an aleatoric run, the energy of a density run) reach [0, 1] in bnf_ue, ue_curves, patches, components, lesions and boundary. '
+                        'minmax (the default): the reference\'s global min-max from the file of --act minmax, files *_globalrescale. quantile: the '
+                        'rank transform of the run from the table of --act quantiles (run it first, or name it in the same call), files '
+                        '*_quantilerescale: every level holds an equal share of the voxels, whatever the outliers. ece_dice, calib and calib_curves keep '
+                        'min-max under either value (a rank-transformed uncertainty is uniform by construction and says nothing about calibration); '
+                        'probability-map runs and confidence entries are untouched')
+    parser.add_argument('--quantiles', type=_int_in(2, 4096), default=1000, help='rcu_amd: the Q boundaries of the table --act quantiles writes '
+                        '(<out>/quantiles/eval_quantiles_<id>.csv: the exact k/Q quantiles of the run inside the T2 brain mask for BraTS, over all pixels '
+                        'for ISIC) and --rescale quantile expects (2..4096); choose --levels equal to it and every level gets its share')
     parser.add_argument('--plain', action='store_true', help='rcu_amd: the reference\'s subject-by-subject, action-by-action loop for every run')
     return parser
 
@@ -90,4 +101,5 @@ if __name__ == '__main__':
                              levels=args.levels, connectivity=args.connectivity, bands=args.bands, dice_fail=args.dice_fail,
                              calib_bins=args.calib_bins, mass_bins=args.mass_bins, recalibrate_from=args.recalibrate_from,
                              merge_radius=args.merge_radius, min_lesion_voxels=args.min_lesion_voxels, match_iou=args.match_iou,
-                             patch=(args.patch_depth, args.patch, args.patch), patch_accuracy=args.patch_accuracy)
+                             patch=(args.patch_depth, args.patch, args.patch), patch_accuracy=args.patch_accuracy,
+                             rescale=args.rescale, quantiles=args.quantiles)

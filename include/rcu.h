@@ -861,6 +861,51 @@ int rcu_density_energy(const float* features_dev, int channel_pitch, int F, size
                        const float* b_dev /* [K][F] */, const float* k_dev /* [K] */, float* energy_dev /* [n_voxels] */,
                        float* d2_dev /* [n_voxels][K] or NULL */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Quantile rescale (EXTENSION: the reference brings an unbounded uncertainty map -- the aleatoric sigma, the density energy -- into [0, 1] with the
+ * run's global min / max, so one outlier voxel fixes the scale; this is the rank transform of the run instead.  rcu_amd.evaluation.quantile_table /
+ * quantile_rescale / RescaleQuantile, the `quantiles` action and `--rescale quantile` of the evaluation script; tests/quantile_reference.py)
+ *   Key.  key(u) is the order-preserving uint32 of the float32 value u: -0.0 is taken as +0.0 first; with b the bit pattern, key = ~b if the sign bit
+ *   is set, else b | 0x80000000.  key is non-decreasing in u over all of float32, the infinities included.  A map stored in another dtype is cast to
+ *   float32 first (round to nearest: monotone, so the result is still a rank transform).  NaN has no key: NaNs are counted, and a run with any NaN
+ *   is refused by the host (ValueError naming the subject).
+ *   Population.  The voxels inside the T2 brain mask where the dataset evaluates inside one (ece_details == 'foreground': BraTS), every voxel
+ *   otherwise (ISIC) -- the rule `calib` follows.  N = the population size over all subjects of the run (a BraTS volume is about 85 % constant
+ *   background: over all voxels about 850 of 1000 boundaries would coincide on that one value).
+ *   Table.  Q boundaries, 2 <= Q <= RCU_UNC_HIST_MAX_LEVELS.  For k = 1 .. Q-1: the rank r_k = ceil(k N / Q) in integers, b_k = the key of the
+ *   r_k-th smallest population value (1-based).  Coinciding boundaries (ties) are kept as they are.  This is
+ *   numpy.quantile(x, k / Q, method='inverted_cdf').
+ *   Level.  l(u) = #{k in 1..Q-1 : key(u) > b_k}, in 0 .. Q-1, for every voxel, inside the population or not.  For distinct values level l holds
+ *   exactly r_{l+1} - r_l population voxels (r_0 = 0, r_Q = N).
+ *   Rescaled value.  (l + 0.5) / Q in float64, stored as float32: it lies in (0, 1), and under level(u) = #{k in 1..B-1 : u > k / B} (rcu_unc_hist)
+ *   with B = Q it gives back l for every l -- the float32 rounding error stays below 2^-24, against 0.5 / Q to the nearest threshold.
+ *   Selection.  Exact, by radix passes over the keys from the top: a pass counts, for every selected prefix, the population voxels per next digit
+ *   (rcu_key_hist); the host finds each boundary's digit and its rank inside that digit from the integer table (evaluation.quantile_refine) and
+ *   selects the distinct prefixes of the next pass.  The digit widths of the passes (the plan) add up to 32.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_KEY_HIST_MAX_PREFIXES 4095
+/* One radix pass over n_volumes float32 volumes of n_per_volume voxels (volume v at maps_dev + v * n_per_volume; mask_dev: uint8 in the same layout,
+ * not 0 = in the population, or NULL = every voxel).  For every population voxel that is not NaN: hi = key >> (shift + bits) (0 where shift + bits =
+ * 32), slot = the index of hi in prefixes_host -- n_prefixes strictly increasing values below 2^(32 - shift - bits), a HOST array; n_prefixes == 0:
+ * every voxel is slot 0 -- voxels whose hi is not listed are skipped; digit = (key >> shift) & (2^bits - 1); hist_dev[slot][digit] += 1.
+ * hist_dev: int64 [max(n_prefixes, 1)][2^bits], ADDED to (the caller zeroes it once: one resident table collects a whole run).  counts_dev: uint64
+ * [2], added to as well: [0] += the NaNs among the population voxels, [1] += the population voxels (NaNs included).  All integers: the same bits
+ * whatever the launch geometry, the batching, the alignment of the pointers or the order of the volumes.  workspace_dev: at least
+ * rcu_key_hist_workspace_bytes(n_prefixes) bytes (the prefix table on the device).  1 <= bits <= 16, shift >= 0, shift + bits <= 32, n_per_volume in
+ * 1..2^31-2, n_volumes in 1..65535; every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it). */
+size_t rcu_key_hist_workspace_bytes(int n_prefixes);
+/* Testing aid: blocks of 16,384 (32,768 in the packed LDS form) voxels one workgroup of rcu_key_hist takes (1..8; larger values count as 8; 0 = the
+ * launcher's own rule).  The counts do not depend on it. */
+int rcu_key_hist_set_blocks_per_workgroup(int blocks);
+int rcu_key_hist(const float* maps_dev, const uint8_t* mask_dev, size_t n_per_volume, int n_volumes, const uint32_t* prefixes_host, int n_prefixes,
+                 int shift, int bits, int64_t* hist_dev, uint64_t* counts_dev, void* workspace_dev, void* stream);
+/* The rank transform of n float32 values under the quantiles - 1 non-decreasing boundary keys bounds_host (HOST array): out_dev[i] =
+ * (float)((l + 0.5) / quantiles) with l = l(map_dev[i]) as above, and levels_dev[i] = l (uint16, or NULL).  NaN -> level 0.  A voxel's output is a
+ * function of its value and the table alone.  workspace_dev: at least rcu_quantile_apply_workspace_bytes(quantiles) bytes.  out_dev must not overlap map_dev. */
+size_t rcu_quantile_apply_workspace_bytes(int quantiles);
+int rcu_quantile_apply(const float* map_dev, size_t n, const uint32_t* bounds_host, int quantiles, float* out_dev, uint16_t* levels_dev,
+                       void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ RCU_MAX_BINS = 32
 RCU_MAX_THRESHOLDS = 16
 RCU_UNC_HIST_MAX_LEVELS = 4096
 RCU_CALIB_CURVE_MAX_LEVELS = 4096
+# quantile rescale (include/rcu.h): selected prefixes per radix pass of rcu_key_hist
+RCU_KEY_HIST_MAX_PREFIXES = 4095
 # connected components (include/rcu.h): the uncertainty source of rcu_cc_table
 RCU_CC_UNC_NONE, RCU_CC_UNC_F32, RCU_CC_UNC_F64, RCU_CC_UNC_P = 0, 1, 2, 3
 # distance transform (include/rcu.h): the squared distance of a volume without a feature voxel; the most bands of rcu_boundary_table
@@ -186,6 +188,11 @@ SIGNATURES = {
     'rcu_density_moments_workspace_bytes': (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
     'rcu_density_moments': (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rcu_density_energy': (c_int, [c_void_p, c_int, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_key_hist_workspace_bytes': (c_size_t, [c_int]),
+    'rcu_key_hist_set_blocks_per_workgroup': (c_int, [c_int]),
+    'rcu_key_hist': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_quantile_apply_workspace_bytes': (c_size_t, [c_int]),
+    'rcu_quantile_apply': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

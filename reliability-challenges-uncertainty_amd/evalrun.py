@@ -31,6 +31,10 @@ CALIBRATION_PLACEHOLDER = 'eval_calibration_{}.csv'
 UNCERTAINTY_PLACEHOLDER = 'eval_uncertainty_{}_th{}.csv'
 ECE_PLACEHOLDER = 'eval_ece_{}.csv'
 MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
+# rcu_amd extension (the 'quantiles' action, the sibling of 'minmax'): the run's quantile table, in its own directory
+QUANTILES_NAME = 'quantiles'
+QUANTILES_PLACEHOLDER = 'eval_quantiles_{}.csv'
+RESCALES = ('minmax', 'quantile')
 # rcu_amd extension (the 'ue_curves' action), next to the per-threshold files in UNCERTAINTY_NAME
 UE_CURVES_PLACEHOLDER = 'eval_ue_curves_{}.csv'
 UE_CURVES_POOLED_PLACEHOLDER = 'eval_ue_curves_pooled_{}.csv'
@@ -359,6 +363,8 @@ class EvalAction(abc.ABC):
     ``scans``, ``fused_arguments`` and ``record_fused``."""
 
     scans = None              # the scans (names of ``want``) of `SubjectBatch.metrics` the action is recorded from; None: it cannot run fused
+    runs_first = False        # whether it writes a file of the run that other actions of the same call read at set-up time ('minmax', 'quantiles')
+    whole_run = False         # whether it walks the run itself (``eval_run``) instead of being handed one subject at a time
     need_mask = False         # whether it evaluates inside the T2 brain mask
     checks_range = True       # whether its preparation refuses maps outside [0, 1] (helper.add_background_probability)
 
@@ -395,6 +401,10 @@ class EvalAction(abc.ABC):
         for case in self.eval_cases:
             case.do_eval(to_eval, sf.subject, self.id_)
 
+    def eval_run(self, eval_data: EvalData):
+        """The whole run at once, for an action that declares ``whole_run`` (between ``start_eval`` and ``finish_eval``)."""
+        raise NotImplementedError
+
     def finish_eval(self):
         for case in self.eval_cases:
             case.hook.on_run_end(case.result_history, self.id_)
@@ -406,8 +416,75 @@ def _minmax_for(min_max_dir, run_id, rescale):
     return read_min_max(os.path.join(min_max_dir, MINMAX_PLACEHOLDER.format(run_id)))
 
 
+def quantiles_file(quantile_dir, run_id):
+    return os.path.join(quantile_dir, QUANTILES_PLACEHOLDER.format(run_id))
+
+
+def read_quantiles_for(quantile_dir, run_id, quantiles):
+    """The table the 'quantiles' action wrote for this run, with the Q the call asks for; anything else is a ValueError naming file and flag."""
+    path = quantiles_file(quantile_dir, run_id)
+    if not os.path.exists(path):
+        raise ValueError('--rescale quantile: {} is missing; run `--act quantiles` over run {} first (in this call or an earlier one)'.format(path, run_id))
+    table = ev.load_quantiles(path)
+    if table.Q != int(quantiles):
+        raise ValueError('--rescale quantile: {} holds Q = {} boundaries, --quantiles asks for {}; run `--act quantiles --quantiles {}` again'
+                         .format(path, table.Q, quantiles, quantiles))
+    return table
+
+
+class SaveQuantilesAction(EvalAction):
+    """EXTENSION (the sibling of ``SaveMinMaxAction``): the exact quantile table of a 'sigma' / 'density' run (evaluation.quantile_table) over the
+    voxels inside the T2 brain mask where the dataset evaluates inside one, over every voxel otherwise, written to
+    ``<base_dir>/quantiles/eval_quantiles_<id>.csv``.  It reads the run once per radix pass (twice by default) and therefore walks the run itself;
+    it never joins the fused probability loop.  On a probability-map or 'confidence' run it writes nothing and says so."""
+
+    scans = None
+    runs_first = True
+    whole_run = True
+    checks_range = False
+    ENTRIES = ('sigma', 'density')
+
+    def __init__(self, quantile_dir, quantiles, need_mask):
+        super().__init__()
+        self.quantile_dir, self.quantiles, self.need_mask = quantile_dir, ev._check_quantiles(quantiles), bool(need_mask)
+        self.entry = None
+
+    def setup_eval(self, eval_data):
+        self.id_ = eval_data.id_
+        self.entry = eval_data.confidence_entry
+        self.load_params = None       # (it reads its files itself, once per pass)
+
+    def eval_subject(self, sf, loader):
+        pass
+
+    def eval_run(self, eval_data):
+        if self.entry not in self.ENTRIES:
+            print('quantiles: run {} holds a {} map in [0, 1], which is not rescaled: nothing written'.format(self.id_, self.entry))
+            return
+        if not eval_data.subject_files:
+            raise ValueError('quantiles: run {} has no subjects'.format(self.id_))
+        params = Loader.Params(self.entry, need_target=False, need_prediction=False, need_t2_mask=self.need_mask)
+        files = eval_data.subject_files
+
+        def volumes():
+            reader = _ReadAhead(files, params, depth=4)
+            try:
+                for i, sf in enumerate(files):
+                    data = reader.get(i)
+                    yield sf.subject, data[self.entry], data.get('mask')
+            finally:
+                reader.close()
+
+        start = time.time()
+        table = ev.quantile_table(volumes, self.quantiles, population='mask' if self.need_mask else 'all')
+        os.makedirs(self.quantile_dir, exist_ok=True)
+        ev.save_quantiles(table, quantiles_file(self.quantile_dir, self.id_))
+        print('quantiles: {} subjects, N = {}, Q = {} ({}s)'.format(len(files), table.N, table.Q, time.time() - start))
+
+
 class SaveMinMaxAction(EvalAction):
     scans = ('minmax',)
+    runs_first = True
     checks_range = False      # (it moves the confidence entry as it is)
 
     def __init__(self, min_max_dir: str) -> None:
@@ -445,11 +522,17 @@ class PreparedAction(EvalAction):
         self.preparation, self.need_mask = preparation, need_mask
         self.rescale_confidence, self.rescale_sigma, self.min_max_dir = rescale_confidence, rescale_sigma, min_max_dir
         self.out_dir = os.path.join(base_dir, out_name)
+        self.quantile_dir, self.quantiles = None, ev.QUANTILES      # (of rescale_sigma == 'quantile': get_actions sets them)
         os.makedirs(self.out_dir, exist_ok=True)
 
     def setup_eval(self, eval_data):
         rescale = self.rescale_confidence if eval_data.confidence_entry == 'confidence' else self.rescale_sigma
-        mm = None if eval_data.confidence_entry == 'probabilities' else _minmax_for(self.min_max_dir, eval_data.id_, rescale)
+        if eval_data.confidence_entry == 'probabilities':
+            mm = None
+        elif rescale == 'quantile':      # the table takes the place of the (min, max) pair
+            mm = read_quantiles_for(self.quantile_dir, eval_data.id_, self.quantiles)
+        else:
+            mm = _minmax_for(self.min_max_dir, eval_data.id_, rescale)
         self.prepare, self.id_ = self.preparation(eval_data.confidence_entry, eval_data.id_, self.rescale_confidence, self.rescale_sigma, mm)
         self.load_params = Loader.Params(eval_data.confidence_entry, need_t2_mask=self.need_mask)
         self.setup_run()
@@ -1000,7 +1083,8 @@ class AgreementAction(EvalAction):
 
 
 def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_LEVELS, connectivity=26, bands=10, dice_fail=0.8, calib_bins=10,
-                mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500):
+                mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500,
+                rescale='minmax', quantiles=ev.QUANTILES):
     """bin-eval/eval_uncertainty.py:226-244, plus the extensions 'ue_curves' (``levels``: its number of uncertainty levels), 'components'
     (``connectivity`` 6 or 26; ``levels``: the threshold grid of its filtered Dice), 'boundary' (``bands``: its distance bands, 1..64;
     ``levels``: of its off-border level histogram) and 'calib_curves' (``levels``: of its calibration level histogram; ``calib_bins``: the
@@ -1009,20 +1093,33 @@ def get_actions(action_names, min_max_dir, base_dir, ece_details, levels=ev.UE_L
     lesions closer than this Euclidean dilation are one lesion; ``min_lesion_voxels``: smaller lesions count as background; ``match_iou``:
     the IoU above which a component and a lesion match, in [0.5, 1)) and 'patches' (``patch``: the (depth, height, width) extents of its
     windows, each in 1..16; ``patch_accuracy``: a patch is accurate when more than this many per mille of its voxels are; ``levels``: of its
-    patch histogram)."""
+    patch histogram) and 'quantiles' (``quantiles``: the Q boundaries of the run's quantile table, written to ``<base_dir>/quantiles``).
+    ``rescale`` = 'quantile': the actions on the prepared uncertainty -- 'bnf_ue', 'ue_curves', 'patches', 'components', 'lesions', 'boundary' --
+    take the quantile rescale (evaluation.RescaleQuantile, files ``*_quantilerescale``) where they take the global min-max today ('sigma' and
+    'density' entries); 'ece_dice', 'calib' and 'calib_curves' keep min-max (a rank-transformed uncertainty is uniform by construction and says
+    nothing about calibration), probability-map runs and 'confidence' entries are untouched."""
+    if rescale not in RESCALES:
+        raise ValueError('rescale must be one of {}, got {!r}'.format(RESCALES, rescale))
+    quantile_dir = os.path.join(base_dir, QUANTILES_NAME)
+    uncertainty_rescale = ('subject', 'quantile' if rescale == 'quantile' else 'global', min_max_dir)
     rescale = ('subject', 'global', min_max_dir)
     table = {'minmax': lambda: SaveMinMaxAction(min_max_dir),
              'ece_dice': lambda: EceAction(base_dir, ece_details, *rescale),
              'calib': lambda: EceCalibrationAction(base_dir, ece_details, *rescale),
-             'bnf_ue': lambda: CorrectionAction(ev.UE_THRESHOLDS, base_dir, *rescale),
-             'ue_curves': lambda: UeCurvesAction(levels, base_dir, *rescale),
-             'patches': lambda: PatchesAction(levels, patch, patch_accuracy, base_dir, *rescale),
-             'components': lambda: ComponentsAction(levels, connectivity, base_dir, *rescale),
-             'lesions': lambda: LesionsAction(levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, *rescale),
-             'boundary': lambda: BoundaryAction(levels, bands, base_dir, *rescale),
+             'quantiles': lambda: SaveQuantilesAction(quantile_dir, quantiles, ece_details == 'foreground'),
+             'bnf_ue': lambda: CorrectionAction(ev.UE_THRESHOLDS, base_dir, *uncertainty_rescale),
+             'ue_curves': lambda: UeCurvesAction(levels, base_dir, *uncertainty_rescale),
+             'patches': lambda: PatchesAction(levels, patch, patch_accuracy, base_dir, *uncertainty_rescale),
+             'components': lambda: ComponentsAction(levels, connectivity, base_dir, *uncertainty_rescale),
+             'lesions': lambda: LesionsAction(levels, connectivity, merge_radius, min_lesion_voxels, match_iou, base_dir, *uncertainty_rescale),
+             'boundary': lambda: BoundaryAction(levels, bands, base_dir, *uncertainty_rescale),
              'agreement': lambda: AgreementAction(base_dir, dice_fail),      # (``dice_fail``: the Dice below which a segmentation counts as failed)
              'calib_curves': lambda: CalibCurvesAction(levels, base_dir, ece_details, calib_bins, mass_bins, recalibrate_from, *rescale)}
-    return [table[name]() for name in action_names if name in table]
+    actions = [table[name]() for name in action_names if name in table]
+    for action in actions:
+        if isinstance(action, PreparedAction):
+            action.quantile_dir, action.quantiles = quantile_dir, ev._check_quantiles(quantiles)
+    return actions
 
 
 # ------------------------------------------------------------------------ the fused subject loop
@@ -1218,7 +1315,7 @@ class _Done:
 
 def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=True, batch_subjects=8, timing=None, levels=ev.UE_LEVELS,
                   connectivity=26, bands=10, dice_fail=0.8, calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0,
-                  match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500):
+                  match_iou=0.5, patch=ev.PATCH_DEFAULT, patch_accuracy=500, rescale='minmax', quantiles=ev.QUANTILES):
     """The subject loop of bin-eval/eval_uncertainty.py:13-50 for already collected runs.
     ``fused`` (default): runs whose confidence entry is the probability map go through ``_evaluate_fused`` -- one upload per subject shared by
     all actions, ``batch_subjects`` subjects per launch, files read ahead; the other runs (confidence / sigma entries: host-side
@@ -1226,15 +1323,17 @@ def evaluate_runs(eval_data_list, action_names, base_dir, ece_details='', fused=
     ``timing``: a dict that receives where the fused loop's time went (tools/eval_throughput.py); ``levels``: of the 'ue_curves' and
     'components' actions; ``connectivity``: of the 'components' action; ``bands``: of the 'boundary' action; ``calib_bins``, ``mass_bins``,
     ``recalibrate_from``: of the 'calib_curves' action; ``merge_radius``, ``min_lesion_voxels``, ``match_iou``: of the 'lesions' action, which
-    shares ``levels`` and ``connectivity`` with 'components'; ``patch``, ``patch_accuracy``: of the 'patches' action (``get_actions``)."""
+    shares ``levels`` and ``connectivity`` with 'components'; ``patch``, ``patch_accuracy``: of the 'patches' action; ``rescale``, ``quantiles``:
+    the rescale of 'sigma' / 'density' entries in the actions on the prepared uncertainty and the Q of the 'quantiles' action (``get_actions``)."""
     actions = get_actions(action_names, os.path.join(base_dir, MINMAX_NAME), base_dir, ece_details, levels, connectivity, bands, dice_fail, calib_bins,
-                          mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou, patch, patch_accuracy)
+                          mass_bins, recalibrate_from, merge_radius, min_lesion_voxels, match_iou, patch, patch_accuracy, rescale, quantiles)
     for entry in eval_data_list:
-        first = [a for a in actions if isinstance(a, SaveMinMaxAction)]
-        rest = [a for a in actions if not isinstance(a, SaveMinMaxAction)]
+        first = [a for a in actions if a.runs_first]
+        rest = [a for a in actions if not a.runs_first]
         if entry.confidence_entry != 'probabilities' and first and rest:
-            # the global rescale of a confidence / sigma / density entry reads the file the minmax action writes for this run, at set-up time:
-            # `--act minmax ue_curves` in ONE call runs the minmax action over the run first (a call without minmax reads an earlier call's file)
+            # the global and the quantile rescale of a confidence / sigma / density entry read the file the minmax / quantiles action writes for
+            # this run, at set-up time: `--act minmax ue_curves` (`--act quantiles ue_curves --rescale quantile`) in ONE call runs the actions
+            # that write such a file over the run first (a call without them reads an earlier call's file)
             _evaluate_entry(entry, first, fused, batch_subjects, timing)
             _evaluate_entry(entry, rest, fused, batch_subjects, timing)
         else:
@@ -1247,6 +1346,14 @@ def _evaluate_entry(entry, actions, fused, batch_subjects, timing):
         action.setup_eval(entry)
     for action in actions:
         action.start_eval()
+    whole = [a for a in actions if a.whole_run]
+    if whole:       # actions that walk the run themselves ('quantiles': once per radix pass); the others go on as if these were not named
+        for action in whole:
+            action.eval_run(entry)
+            action.finish_eval()
+        actions = [a for a in actions if not a.whole_run]
+        if not actions:
+            return
     if fused and entry.subject_files and _fusable(entry, actions):
         if timing is not None:
             for key in ('subjects', 'batches', 'wait_for_files_s', 'read_thread_s', 'stage_s', 'upload_and_kernels_s', 'csv_rows_s'):

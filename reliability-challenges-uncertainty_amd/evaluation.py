@@ -430,8 +430,222 @@ class EntropyOfProbability:
         return self.materialise().max()
 
 
+# ------------------------------------------------ quantile rescale of unbounded uncertainty maps (EXTENSION; include/rcu.h "Quantile rescale")
+QUANTILES = 1000                     # default number of boundaries Q (= the default number of levels of the level histograms)
+QUANTILE_PLAN = (16, 16)             # digit widths of the radix passes, from the top of the key: the run is read twice
+QUANTILE_PLAN_NARROW = (16, 8, 8)    # ... where the second pass's table of the default plan would not fit QUANTILE_TABLE_BYTES
+QUANTILE_TABLE_BYTES = 1 << 30
+QUANTILE_POPULATIONS = ('all', 'mask')
+
+
+def float_key(values):
+    """The order-preserving uint32 of float32 values (include/rcu.h: -0.0 as +0.0; ``~b`` below zero, ``b | 0x80000000`` else).  NaN has no key."""
+    b = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32)
+    b = np.where(b == np.uint32(0x80000000), np.uint32(0), b)
+    return np.where(b >> np.uint32(31) != 0, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def key_float(keys):
+    """The float32 value of a key (the inverse of ``float_key`` up to the sign of zero)."""
+    k = np.ascontiguousarray(keys, dtype=np.uint32)
+    return np.where(k >> np.uint32(31) != 0, k & np.uint32(0x7fffffff), ~k).astype(np.uint32).view(np.float32)
+
+
+def quantile_ranks(n, quantiles):
+    """r_k = ceil(k n / Q) for k = 1 .. Q-1, in Python integers."""
+    n, q = int(n), int(quantiles)
+    return [(k * n + q - 1) // q for k in range(1, q)]
+
+
+def _check_quantiles(quantiles):
+    if not 2 <= int(quantiles) <= _lib.RCU_UNC_HIST_MAX_LEVELS:
+        raise ValueError('quantiles must be in 2..{}, got {}'.format(_lib.RCU_UNC_HIST_MAX_LEVELS, quantiles))
+    return int(quantiles)
+
+
+def _check_plan(plan):
+    plan = tuple(int(b) for b in plan)
+    if not plan or sum(plan) != 32 or any(not 1 <= b <= 16 for b in plan):
+        raise ValueError('the digit widths of a quantile plan must lie in 1..16 and add up to 32, got {}'.format(plan))
+    return plan
+
+
+class QuantileTable:
+    """Q, the population size N, the Q-1 boundary keys (uint32) and their ranks r_k (int64, 1-based), and which population they are of."""
+
+    def __init__(self, quantiles, n, keys, ranks, population='all'):
+        self.Q, self.N = int(quantiles), int(n)
+        self.keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        self.ranks = np.ascontiguousarray(ranks, dtype=np.int64)
+        self.population = population
+        if self.keys.shape != (self.Q - 1,) or self.ranks.shape != (self.Q - 1,):
+            raise ValueError('a quantile table of Q = {} has {} boundaries'.format(self.Q, self.Q - 1))
+
+    values = property(lambda self: key_float(self.keys))
+
+    def __eq__(self, other):
+        return (isinstance(other, QuantileTable) and (self.Q, self.N, self.population) == (other.Q, other.N, other.population)
+                and np.array_equal(self.keys, other.keys) and np.array_equal(self.ranks, other.ranks))
+
+
+def quantile_refine(hist, ranks, slots=None, prefixes=None):
+    """One step of the selection, on the host in integers: ``hist`` is the pass's ``[slots, 2^bits]`` table, ``ranks[k]`` boundary k's residual
+    rank (1-based) inside row ``slots[k]`` (default: row 0), ``prefixes[s]`` the key prefix row s stands for (default: the one empty prefix 0).
+    -> (digits, ranks inside those digits, the distinct prefixes ``prefix << bits | digit`` of the next pass in increasing order, each boundary's
+    row among them).  No device."""
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or hist.shape[1] < 2 or hist.shape[1] & (hist.shape[1] - 1):
+        raise ValueError('hist must be [slots, 2^bits], got {}'.format(hist.shape))
+    bits = hist.shape[1].bit_length() - 1
+    ranks = [int(r) for r in ranks]
+    slots = [0] * len(ranks) if slots is None else [int(s) for s in slots]
+    prefixes = [0] * hist.shape[0] if prefixes is None else [int(p) for p in prefixes]
+    if len(prefixes) != hist.shape[0] or len(slots) != len(ranks):
+        raise ValueError('one prefix per row of hist and one slot per rank')
+    digits, inside, grown = [], [], []
+    cumulative = {}
+    for rank, slot in zip(ranks, slots):
+        if slot not in cumulative:
+            cumulative[slot] = np.cumsum(hist[slot].astype(np.int64))        # (a run has fewer than 2^63 voxels)
+        c = cumulative[slot]
+        if not 1 <= rank <= int(c[-1]):
+            raise ValueError('rank {} outside row {} of {} voxels'.format(rank, slot, int(c[-1])))
+        d = int(np.searchsorted(c, rank, side='left'))                       # the first digit whose cumulative count reaches the rank
+        digits.append(d)
+        inside.append(rank - (int(c[d - 1]) if d else 0))
+        grown.append((prefixes[slot] << bits) | d)
+    next_prefixes = sorted(set(grown))
+    index = {p: i for i, p in enumerate(next_prefixes)}
+    return digits, inside, next_prefixes, [index[p] for p in grown]
+
+
+def _key_hist_launch(maps, mask, prefixes, shift, bits, hist, counts):
+    """rcu_key_hist over device ``[v, n]`` float32 maps (and uint8 mask or None): adds to the device int64 ``hist`` and ``counts`` [2]."""
+    v, n = maps.shape
+    lib = _lib.load()
+    table = (ctypes.c_uint32 * max(len(prefixes), 1))(*prefixes)
+    ws = torch.empty(max(lib.rcu_key_hist_workspace_bytes(len(prefixes)), 8), device=maps.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_key_hist(_lib.ptr(maps), _lib.ptr(mask), n, v, table, len(prefixes), int(shift), int(bits), _lib.ptr(hist), _lib.ptr(counts),
+                                _lib.ptr(ws), _lib.current_stream()))
+
+
+def key_histogram(maps, mask=None, prefixes=(), shift=16, bits=16, n_volumes=1, out=None):
+    """One radix pass (include/rcu.h, rcu_key_hist) over ``n_volumes`` float32 volumes -> (int64 ``[max(len(prefixes), 1), 2^bits]`` counts,
+    NaNs among the population voxels, population voxels).  ``out``: a device (hist, counts) pair of an earlier call that is added to and
+    returned as it is (nothing waits)."""
+    maps = _flat(maps, torch.float32, n_volumes)
+    mask = _flat(mask, torch.uint8, n_volumes, maps, 'map and mask')
+    prefixes = [int(p) for p in prefixes]
+    if out is None:
+        hist = torch.zeros((max(len(prefixes), 1), 1 << int(bits) if 1 <= int(bits) <= 16 else 1), device=maps.device, dtype=torch.int64)
+        counts = torch.zeros(2, device=maps.device, dtype=torch.int64)
+    else:
+        hist, counts = out
+    _key_hist_launch(maps, mask, prefixes, shift, bits, hist, counts)
+    if out is not None:
+        return out
+    counts = counts.cpu().numpy()
+    return hist.cpu().numpy(), int(counts[0]), int(counts[1])
+
+
+def _volumes(volumes_iter):
+    """``volumes_iter``: a callable that returns a fresh iterator, or something that can be iterated again -> (subject, map, mask or None)."""
+    for item in (volumes_iter() if callable(volumes_iter) else volumes_iter):
+        subject, map_, mask = item if len(item) == 3 else (item[0], item[1], None)
+        yield subject, map_, mask
+
+
+def quantile_table(volumes_iter, quantiles=QUANTILES, plan=None, population=None):
+    """The exact quantile table of a run (include/rcu.h, "Quantile rescale"): ``volumes_iter`` yields ``(subject, map, mask or None)`` per
+    subject and is walked once per radix pass -- the default plan ``(16, 16)`` reads the run twice; where the D prefixes that survive the
+    first pass would need more than 1 GiB for its second table (D * 2^16 * 8 bytes) the plan is ``(16, 8, 8)``.  ``plan``: forced digit
+    widths (they add up to 32).  One resident int64 table per pass collects the whole run; the host refines it in integers
+    (``quantile_refine``).  A NaN inside the population is refused with a ValueError that names the subject.  -> QuantileTable."""
+    q = _check_quantiles(quantiles)
+    forced = plan is not None
+    plan = _check_plan(plan if forced else QUANTILE_PLAN)
+    dev = _device()
+    ranks = slots = None
+    prefixes, n_total, shift, done = [], None, 32, 0
+    masked = False
+    while done < len(plan):
+        bits = plan[done]
+        shift -= bits
+        hist = torch.zeros((max(len(prefixes), 1), 1 << bits), device=dev, dtype=torch.int64)
+        per_subject = []
+        for subject, map_, mask in _volumes(volumes_iter):
+            counts = torch.zeros(2, device=dev, dtype=torch.int64)
+            maps = _flat(map_, torch.float32, 1)
+            _key_hist_launch(maps, _flat(mask, torch.uint8, 1, maps, 'map and mask of subject {}'.format(subject)), prefixes, shift, bits, hist, counts)
+            per_subject.append((subject, counts))
+            masked = masked or mask is not None
+        if not per_subject:
+            raise ValueError('quantile_table: no volumes')
+        totals = torch.stack([c for _, c in per_subject]).cpu().numpy()
+        for (subject, _), (nans, _) in zip(per_subject, totals):
+            if nans:
+                raise ValueError('quantile_table: subject {} holds {} NaN value(s) inside the population; a NaN has no rank'.format(subject, int(nans)))
+        n_pass = int(totals[:, 1].sum())
+        if n_total is None:
+            n_total = n_pass
+            if n_total == 0:
+                raise ValueError('quantile_table: the population is empty')
+            ranks, slots = quantile_ranks(n_total, q), [0] * (q - 1)
+        elif n_pass != n_total:
+            raise ValueError('quantile_table: the run changed between two passes ({} population voxels, then {})'.format(n_total, n_pass))
+        _, ranks, prefixes, slots = quantile_refine(hist.cpu().numpy(), ranks, slots, prefixes or None)
+        done += 1
+        if done == 1 and not forced and len(prefixes) * (1 << plan[1]) * 8 > QUANTILE_TABLE_BYTES:
+            plan = QUANTILE_PLAN_NARROW
+    keys = np.array([prefixes[s] for s in slots], dtype=np.uint32)
+    return QuantileTable(q, n_total, keys, quantile_ranks(n_total, q), population or ('mask' if masked else 'all'))
+
+
+QUANTILE_COLUMNS = ('k', 'rank', 'key', 'value')
+
+
+def save_quantiles(table, path):
+    """``k, rank, key, value`` per boundary; ``key`` (the uint32 in decimal) is authoritative, ``value`` the float32's shortest round-trip text.
+    The first data row is ``0, N, Q, population kind``."""
+    import csv
+    with open(path, 'w', newline='') as f:
+        writer = csv.writer(f)
+        writer.writerow(QUANTILE_COLUMNS)
+        writer.writerow([0, table.N, table.Q, table.population])
+        for k, (rank, key, value) in enumerate(zip(table.ranks, table.keys, table.values), start=1):
+            writer.writerow([k, int(rank), int(key), str(value)])
+
+
+def load_quantiles(path):
+    import csv
+    with open(path, newline='') as f:
+        rows = list(csv.reader(f))
+    if len(rows) < 2 or tuple(rows[0]) != QUANTILE_COLUMNS or rows[1][0] != '0' or rows[1][3] not in QUANTILE_POPULATIONS:
+        raise ValueError('{} is not a quantile table'.format(path))
+    n, q = int(rows[1][1]), int(rows[1][2])
+    body = rows[2:]
+    if len(body) != q - 1 or [int(r[0]) for r in body] != list(range(1, q)):
+        raise ValueError('{}: {} boundaries for Q = {}'.format(path, len(body), q))
+    return QuantileTable(q, n, [int(r[2]) for r in body], [int(r[1]) for r in body], rows[1][3])
+
+
+def quantile_rescale(table, map_, return_levels=False):
+    """The rank transform of a map under a QuantileTable (include/rcu.h, rcu_quantile_apply): a device float32 tensor of ``(l + 0.5) / Q`` in the
+    map's shape, l = #{k : key(u) > b_k}; with ``return_levels`` also the levels themselves (an int16 tensor: Q <= 4096)."""
+    shape = tuple(map_.shape)
+    src = _to_dev(map_, torch.float32).reshape(-1)
+    lib = _lib.load()
+    out = torch.empty_like(src)
+    levels = torch.empty(src.shape, device=src.device, dtype=torch.int16) if return_levels else None
+    bounds = (ctypes.c_uint32 * (table.Q - 1))(*[int(k) for k in table.keys])
+    ws = torch.empty(max(lib.rcu_quantile_apply_workspace_bytes(table.Q), 8), device=src.device, dtype=torch.uint8)
+    _lib.check(lib.rcu_quantile_apply(_lib.ptr(src), src.numel(), bounds, table.Q, _lib.ptr(out), _lib.ptr(levels), _lib.ptr(ws), _lib.current_stream()))
+    out = out.reshape(shape)
+    return (out, levels.reshape(shape)) if return_levels else out
+
+
 # ------------------------------------------------ threshold-free uncertainty-error metrics from a level histogram (EXTENSION)
-UE_LEVELS = 1000        # default number of levels: every threshold of UE_THRESHOLDS is then a level boundary k / 1000
+UE_LEVELS = 1000       # default number of levels: every threshold of UE_THRESHOLDS is then a level boundary k / 1000
 UE_CURVE_KEYS = ('n', 'n_errors', 'auroc', 'auprc', 'aurc', 'eaurc', 'ue_dice_max', 'ue_dice_max_threshold')
 
 
@@ -1884,8 +2098,23 @@ class MoveEntry(PrepareData):
         return to_eval
 
 
+class RescaleQuantile(PrepareData):
+    """EXTENSION: the entry's rank transform under the run's QuantileTable (``quantile_rescale``), handed on as ``RescaleLinear`` hands its map
+    on -- a host array, float32 here.  (The consumers take device tensors as well, but the preparations behind this one -- ``MoveEntry``, and the
+    range check of ``check_min_max`` -- and the loaders' caches are written for host arrays: the map comes back once, 4 bytes per voxel.)"""
+
+    def __init__(self, entry: str, table) -> None:
+        self.entry, self.table = entry, table
+
+    def __call__(self, to_eval: dict) -> dict:
+        to_eval[self.entry] = quantile_rescale(self.table, to_eval[self.entry]).cpu().numpy()
+        return to_eval
+
+
 def _rescale_prep_and_idstr(confidence_entry, rescale_type, min_max=None):
     # analysis.py:277-285 ('global' reads the min/max CSV; here the pair is passed in)
+    if rescale_type == 'quantile':       # rcu_amd extension: ``min_max`` is the run's QuantileTable; its files never collide with the _globalrescale ones
+        return RescaleQuantile(confidence_entry, min_max), '_quantilerescale'
     if rescale_type == 'global':
         return RescaleLinear(confidence_entry, min_max[0], min_max[1]), '_globalrescale'
     if rescale_type == 'subject':

@@ -282,7 +282,10 @@ class DeviceMetricsHook(loops.TestLoopHook):
         spec = dict(spec or {}) if not isinstance(spec, (list, tuple)) else {'actions': list(spec)}
         self.dataset = dataset
         self.action_names = list(spec.get('actions') or ['minmax', 'ece_dice', 'calib', 'bnf_ue'])
-        self.run_id, self.gt_dir, self.out_dir = spec.get('run_id'), spec.get('gt_dir'), spec.get('out_dir')
+        if 'quantiles' in self.action_names:       # (the hook sees probability maps only: there is nothing to rescale, and the action reads a run twice)
+            raise ValueError('others.device_metrics: the action "quantiles" works on the files of a sigma / density run (bin-eval/eval_uncertainty.py '
+                             '--act quantiles); the hook sees probability maps only')
+        self.run_id,self.gt_dir, self.out_dir = spec.get('run_id'), spec.get('gt_dir'), spec.get('out_dir')
         self.store = store
         self.actions, self.rows, self.gts = [], {}, None
         self.batch = None
@@ -1203,7 +1206,7 @@ for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, te
 def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, actions=('minmax', 'ece_dice', 'calib', 'bnf_ue'),
                      expected_subjects=None, fused=True, batch_subjects=8, timing=None, levels=1000, connectivity=26, bands=10, dice_fail=0.8,
                      calib_bins=10, mass_bins=10, recalibrate_from=None, merge_radius=0, min_lesion_voxels=0, match_iou=0.5, patch=(1, 4, 4),
-                     patch_accuracy=500):
+                     patch_accuracy=500, rescale='minmax', quantiles=1000):
     """``run_dirs``: run id (baseline, baseline_mc, ..., aleatoric) -> prediction directory.  BraTS evaluates
     inside the T2 brain mask (``ece_details='foreground'``), ISIC on all pixels (eval_uncertainty.py:19-26).
     ``ground_truth_dir``: the BraTS tree of ``<subject>/<subject>_{t2,seg,...}.nii.gz`` or, for ISIC, the dataset
@@ -1221,5 +1224,5 @@ def eval_uncertainty(dataset, run_dirs: dict, ground_truth_dir, base_dir, action
     evalrun.evaluate_runs(entries, list(actions), base_dir, details, fused=fused, batch_subjects=batch_subjects, timing=timing, levels=levels,
                           connectivity=connectivity, bands=bands, dice_fail=dice_fail, calib_bins=calib_bins, mass_bins=mass_bins,
                           recalibrate_from=recalibrate_from, merge_radius=merge_radius, min_lesion_voxels=min_lesion_voxels, match_iou=match_iou,
-                          patch=patch, patch_accuracy=patch_accuracy)
+                          patch=patch, patch_accuracy=patch_accuracy, rescale=rescale, quantiles=quantiles)      # (rescale / quantiles: the rescale of sigma / density entries in the actions on the prepared uncertainty and the Q of the 'quantiles' action)
     return entries
