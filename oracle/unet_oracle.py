@@ -189,16 +189,19 @@ def _centre_pad(up, skip):
     return up
 
 
-def postnet_forward(state, x, nb_convs=3, masks=None):
+def postnet_forward(state, x, nb_convs=3, masks=None, dtype=torch.float32):
     """common/model/postnet.py:6-18: nb_convs x [Conv2d 1x1 C->C, Dropout2d, BatchNorm2d (eval), ReLU] + Conv2d 1x1.  ``masks``:
-    None (dropout None as in every shipped config, or Dropout2d in eval mode) or one [N, C] factor array per conv (MC-dropout)."""
+    None (dropout None as in every shipped config, or Dropout2d in eval mode) or one [N, C] factor array per conv (MC-dropout).
+    ``dtype``: torch.float64 promotes state, input and masks, as in unet_forward."""
     state = {k: torch.as_tensor(v) for k, v in strip_module_prefix(state).items()}
-    x = torch.as_tensor(x, dtype=torch.float32)
+    if dtype != torch.float32:
+        state = {k: (v.to(dtype) if torch.is_floating_point(v) else v) for k, v in state.items()}
+    x = torch.as_tensor(x, dtype=torch.float32).to(dtype)
     for i in range(nb_convs):
         k = 'convs.{}.conv2d_batch_relu'.format(i)
         x = F.conv2d(x, state[k + '.conv.weight'], state[k + '.conv.bias'])
         if masks is not None:
-            x = x * torch.as_tensor(masks[i], dtype=torch.float32)[:, :, None, None]
+            x = x * torch.as_tensor(masks[i], dtype=torch.float32).to(dtype)[:, :, None, None]
         x = F.batch_norm(x, state[k + '.bn.running_mean'], state[k + '.bn.running_var'], state[k + '.bn.weight'],
                          state[k + '.bn.bias'], False, 0.0, BN_EPS)
         x = F.relu(x)

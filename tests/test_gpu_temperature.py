@@ -132,6 +132,38 @@ def test_invalid_targets_are_counted_and_refused(dev):
         sweep.sums()
 
 
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('masked', [False, True], ids=['all', 'mask'])
+@pytest.mark.parametrize('p, c', [(37, 8), (257, 2)])
+def test_unstaged_form_against_the_float64_oracle(dev, p, c, masked):
+    """P x (C - 1) = 259 floats per voxel do not fit the LDS stage (TN_STAGE_MAX = 256): temperature_nll_kernel<false, ...> reads the
+    differences from global memory per candidate.  MC T >= 257 on a binary model, or 37 passes on an 8-class model, take it."""
+    from rcu_amd import calibration as cal
+    assert p * (c - 1) > 256 >= 36 * 7
+    z, y = _case(p, c, n=2)
+    mask = (np.random.RandomState(5).rand(*y.shape) < 0.6) if masked else None
+    keep = np.ones(y.shape, bool) if mask is None else mask
+    sweep = _sweep(z, y, mask, dev)
+    sums = sweep.sums()
+    assert sweep.voxels == int(keep.sum())
+    for k in (0, 48, 96):
+        beta = np.float32(1.0 / cal.CANDIDATES[k])
+        terms = _terms(z, y, beta, mask, dev)
+        ref = oracle_terms(z, y, float(beta))
+        err = np.abs(terms.astype(np.float64) - ref)
+        ok = (err <= 1e-5 * np.abs(ref)) | (err <= 2.0 ** -20)
+        assert ok[keep].all(), (k, float(err[keep].max()), ref[keep][~ok[keep]][:4], terms[keep][~ok[keep]][:4])
+        assert not terms[~keep].any()
+        expect = int(np.rint(np.clip(terms[keep].astype(np.float64), 0, 4096) * SCALE).astype(np.int64).sum())
+        assert sums[k] == expect, k
+    # the same voxels added as two calls
+    halves = cal.NllSweep(dev)
+    for i in range(2):
+        halves.add(torch.from_numpy(np.ascontiguousarray(z[:, i:i + 1]).reshape(p, c, 24, 24)).to(dev), torch.from_numpy(y[i:i + 1]).to(dev),
+                   None if mask is None else torch.from_numpy(mask[i:i + 1]).to(dev), passes=p)
+    assert halves.sums() == sums and halves.voxels == sweep.voxels
+
+
 def ctypes_float1():
     import ctypes
     return ctypes.c_float * 1
