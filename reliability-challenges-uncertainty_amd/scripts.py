@@ -13,6 +13,7 @@ Each function is the ``main`` of the same-named reference script (flags unchange
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
 """
+import collections
 import csv
 import json
 import logging
@@ -343,9 +344,84 @@ class PrepareSubjectStep(steps.BatchStep):
 
 
 def _other(context, key, default=None):
-    """A key of the YAML file's free-form ``others`` (rcu_amd extensions, absent from the reference's configs: coalesce_pixels, pipelined,
-    max_inflight, stream_lanes, device_metrics, tta, corruption)."""
+    """A key of the YAML file's free-form ``others`` (rcu_amd extensions, absent from the reference's configs): the options coalesce_pixels,
+    pipelined, max_inflight, loader_timing, stream_lanes, group_pixels, exact, device_metrics, device_confusion, and the keys of ``_OTHERS``,
+    which only some scripts take."""
     return getattr(context.config.others, key, default)
+
+
+_TEST_SCRIPTS = frozenset(('default', 'ensemble', 'aleatoric', 'auxiliary_feat', 'auxiliary_segm'))
+_DEFAULT = frozenset(('default',))
+_ONE_PASS_FIT = 'others.{}: the density fit is one eval-mode pass per batch and does not take it'
+_OtherKey = collections.namedtuple('_OtherKey', 'name description home scripts tail overrides', defaults=('', {}))
+# The extension keys of ``others`` that not every script takes, in the order they are checked: name, the description and the home its refusal
+# names, the scripts that take it, a tail to the refusal, the scripts that refuse it in words of their own.  A new key is a row here and its builder.
+_OTHERS = (
+    _OtherKey('tta', 'test-time augmentation', 'the default test scripts only', _DEFAULT,
+              overrides={'fit_temperature': 'others.tta: the temperature fit does not run under test-time augmentation',
+                         'fit_density': _ONE_PASS_FIT.format('tta')}),
+    _OtherKey('mc', None, None, _TEST_SCRIPTS | {'fit_temperature'}, overrides={'fit_density': _ONE_PASS_FIT.format('mc')}),
+    _OtherKey('temperature', 'temperature scaling', 'the default test scripts only', _DEFAULT),
+    _OtherKey('agreement', 'MC sample agreement', 'the default test scripts with others.mc only', _DEFAULT),
+    _OtherKey('mc_adaptive', 'adaptive MC dropout', 'the default test scripts with others.mc only', _DEFAULT),
+    _OtherKey('logit_samples', 'test-time logit sampling', 'the aleatoric test scripts only', frozenset(('aleatoric',))),
+    _OtherKey('corruption', 'input corruptions', 'the test scripts only', _TEST_SCRIPTS, tail=': calibration is fitted on clean validation data'),
+    _OtherKey('density', 'feature-space density uncertainty', 'the default test scripts only', _DEFAULT),
+)
+
+
+def _lacks_mc(others, world):
+    return not hasattr(others, 'mc')
+
+
+def _sharded(others, world):
+    return world.world > 1
+
+
+# What a key of the default script does not compose with: (key, the other key -- set in the YAML file -- or a condition (others, world), message),
+# in the order the rules of a key are checked.  ``agreement: false`` is the key switched off.
+_RULES = tuple(('density', key, 'others.density does not compose with others.{}: the density map belongs to the one deterministic pass'.format(key))
+               for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples')) + (
+    ('mc_adaptive', 'tta', 'others.mc_adaptive does not compose with others.tta (test-time augmentation): the transforms of a slice share its statistics'),
+    ('mc_adaptive', _lacks_mc, 'others.mc_adaptive needs others.mc: there are no passes to save without MC dropout'),
+    ('mc_adaptive', lambda others, world: getattr(others, 'agreement', False),
+     'others.mc_adaptive does not compose with others.agreement: the vote planes assume every slice sees every pass'),
+    ('mc_adaptive', lambda others, world: not bool(getattr(others, 'exact', True)),
+     'others.mc_adaptive needs exact statistics (others.exact: false is refused): the decision is made on exact integer sums'),
+    ('mc_adaptive', _sharded, 'others.mc_adaptive is not sharded: run the script in one process'),
+    ('agreement', 'tta', 'others.agreement does not compose with others.tta (test-time augmentation): the vote plane holds the passes of MC dropout alone'),
+    ('agreement', _lacks_mc, 'others.agreement needs others.mc: there are no samples to compare without MC dropout passes'),
+    ('agreement', _sharded, 'others.agreement is not sharded: run the script in one process (a vote plane lives where all passes of a batch run)'),
+)
+
+
+_TAKEN_BY = {row.name: row.scripts for row in _OTHERS}
+
+
+def _is_set(others, key):
+    return hasattr(others, key) and not (key == 'agreement' and others.agreement is False)
+
+
+def _check_rules(others, world, key):
+    """Raises the first rule of ``_RULES`` that the YAML file's ``key`` breaks."""
+    for owner, other, message in _RULES:
+        if owner == key and (other(others, world) if callable(other) else _is_set(others, other)):
+            raise ValueError(message)
+
+
+def _check_others(context, script, world):
+    """Every script's first look at ``others``: the first key of ``_OTHERS`` that ``script`` does not take is refused by name.  (A key the script
+    takes that names the refused one in ``_RULES`` speaks first: it says what the two have to do with each other.)"""
+    others = context.config.others
+    for row in _OTHERS:
+        if not hasattr(others, row.name) or script in row.scripts:
+            continue
+        if script in row.overrides:
+            raise ValueError(row.overrides[script])
+        for owner, other, _ in _RULES:
+            if other == row.name and hasattr(others, owner) and script in _TAKEN_BY[owner]:
+                _check_rules(others, world, owner)
+        raise ValueError('others.{} ({}) applies to {}; the {} script does not take it{}'.format(row.name, row.description, row.home, script, row.tail))
 
 
 def _mask_seed(context, world):
@@ -383,41 +459,16 @@ def _tta_steps(context, world):
     return [step, steps.MultiPredictionSummary()]
 
 
-def _refuse_tta(context, script):
-    if hasattr(context.config.others, 'tta'):
-        raise ValueError('others.tta (test-time augmentation) applies to the default test scripts only; the {} script does not take it'.format(script))
-
-
-def _refuse_logit_samples(context, script):
-    if hasattr(context.config.others, 'logit_samples'):
-        raise ValueError('others.logit_samples (test-time logit sampling) applies to the aleatoric test scripts only; the {} script does not take it'
-                         .format(script))
-
-
-def _refuse_agreement(context, script):
-    if hasattr(context.config.others, 'agreement'):
-        raise ValueError('others.agreement (MC sample agreement) applies to the default test scripts with others.mc only; the {} script does not '
-                         'take it'.format(script))
-
-
 def _agreement(context, world):
     """``others.agreement: true`` (an rcu_amd extension, include/rcu.h "Sample agreement"): the T = ``others.mc`` samples of a subject compared as
-    whole segmentations -> ``<test_dir>/agreement.csv``.  One process, MC dropout alone: a ValueError that names the key otherwise."""
-    if not hasattr(context.config.others, 'agreement'):
-        return False
-    value = context.config.others.agreement
+    whole segmentations -> ``<test_dir>/agreement.csv``.  One process, MC dropout alone (``_RULES``): a ValueError that names the key otherwise."""
+    value = _other(context, 'agreement', False)
     if not isinstance(value, bool):
         raise ValueError('others.agreement must be true or false, got {!r}'.format(value))
-    if not value:
-        return False
-    if hasattr(context.config.others, 'tta'):
-        raise ValueError('others.agreement does not compose with others.tta (test-time augmentation): the vote plane holds the passes of MC dropout alone')
-    if not hasattr(context.config.others, 'mc'):
-        raise ValueError('others.agreement needs others.mc: there are no samples to compare without MC dropout passes')
-    if world.world > 1:
-        raise ValueError('others.agreement is not sharded: run the script in one process (a vote plane lives where all passes of a batch run)')
-    steps.check_agreement_passes(context.config.others.mc)
-    return True
+    if value:
+        _check_rules(context.config.others, world, 'agreement')
+        steps.check_agreement_passes(context.config.others.mc)
+    return value
 
 
 class AgreementCsvHook(loops.TestLoopHook):
@@ -450,32 +501,17 @@ class AgreementCsvHook(loops.TestLoopHook):
             writer.writerows(self.rows)
 
 
-def _refuse_adaptive(context, script):
-    if hasattr(context.config.others, 'mc_adaptive'):
-        raise ValueError('others.mc_adaptive (adaptive MC dropout) applies to the default test scripts with others.mc only; the {} script does not '
-                         'take it'.format(script))
-
-
 def _adaptive(context, world):
     """``others.mc_adaptive: {check_at: [5, 10], tolerance: 0.01, max_unsettled: 0}`` (an rcu_amd extension, include/rcu.h "Adaptive MC") next to
     ``others.mc``: slices settled at a pass checkpoint are retired and finalised from the passes they have seen -> the checked schedule, or None
-    without the key.  One process, MC dropout alone, exact statistics: a ValueError that names the key otherwise."""
+    without the key.  One process, MC dropout alone, exact statistics (``_RULES``): a ValueError that names the key otherwise."""
     if not hasattr(context.config.others, 'mc_adaptive'):
         return None
     others = context.config.others
+    _check_rules(others, world, 'mc_adaptive')
     value = others.mc_adaptive
     if not isinstance(value, dict):
         value = dict(vars(value)) if hasattr(value, '__dict__') else value
-    if hasattr(others, 'tta'):
-        raise ValueError('others.mc_adaptive does not compose with others.tta (test-time augmentation): the transforms of a slice share its statistics')
-    if not hasattr(others, 'mc'):
-        raise ValueError('others.mc_adaptive needs others.mc: there are no passes to save without MC dropout')
-    if getattr(others, 'agreement', False):
-        raise ValueError('others.mc_adaptive does not compose with others.agreement: the vote planes assume every slice sees every pass')
-    if not bool(getattr(others, 'exact', True)):
-        raise ValueError('others.mc_adaptive needs exact statistics (others.exact: false is refused): the decision is made on exact integer sums')
-    if world.world > 1:
-        raise ValueError('others.mc_adaptive is not sharded: run the script in one process')
     try:
         return steps.check_adaptive(value, others.mc)
     except ValueError as e:
@@ -576,12 +612,6 @@ def _aleatoric_steps(context, world):
     return [steps.AleatoricPredictStep(is_log_sigma, samples, seed)]
 
 
-def _refuse_temperature(context, script):
-    if hasattr(context.config.others, 'temperature'):
-        raise ValueError('others.temperature (temperature scaling) applies to the default test scripts only; the {} script does not take it'
-                         .format(script))
-
-
 class ApplyTemperatureHook(loops.TestLoopHook):
     """``others.temperature`` (an rcu_amd extension): the model loaded by the test loop is scaled by T (UNet.set_temperature) before the first
     batch -- on every rank of a sharded run."""
@@ -632,28 +662,14 @@ def _corruption(context):
     return [steps.CorruptInputStep(stages, seed)], [CorruptionRecordHook(corruption_mod.describe(stages, seed))]
 
 
-def _refuse_corruption(context, script):
-    if hasattr(context.config.others, 'corruption'):
-        raise ValueError('others.corruption (input corruptions) applies to the test scripts only; the {} script does not take it: calibration is '
-                         'fitted on clean validation data'.format(script))
-
-
-def _refuse_density(context, script):
-    if hasattr(context.config.others, 'density'):
-        raise ValueError('others.density (feature-space density uncertainty) applies to the default test scripts only; the {} script does not take '
-                         'it'.format(script))
-
-
 def _density(context):
     """``others.density: <path to density.npz>`` (an rcu_amd extension, include/rcu.h "Feature-space density"; the fit_density scripts write the
     file): the deterministic default run with the energy of the fitted class Gaussians as one more map per subject -> the DensityFit, or None
     without the key.  One eval-mode pass per batch: a ValueError that names both keys beside the keys that sample (mc, tta, agreement, mc_adaptive,
-    logit_samples).  Composes with others.corruption and others.temperature (which rescales conv_cls.1 alone: the features do not move)."""
+    logit_samples: ``_RULES``).  Composes with others.corruption and others.temperature (which rescales conv_cls.1 alone: the features do not move)."""
     if not hasattr(context.config.others, 'density'):
         return None
-    for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples'):
-        if hasattr(context.config.others, key) and not (key == 'agreement' and getattr(context.config.others, key) is False):
-            raise ValueError('others.density does not compose with others.{}: the density map belongs to the one deterministic pass'.format(key))
+    _check_rules(context.config.others, None, 'density')      # (its rules name keys alone: no world to ask)
     value = context.config.others.density
     if not isinstance(value, (str, os.PathLike)):
         raise ValueError('others.density must be the path of a density.npz (bin-dl/*_fit_density.py), got {!r}'.format(value))
@@ -685,35 +701,37 @@ class DensityWriteHook(loops.TestLoopHook):
         nifti.join_all()
 
 
+def _default_plan(context, world, density_fit=None):
+    """The one decision of the default script: density, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the entries they add
+    to the assembled subject, the per-subject hooks that write them)."""
+    if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
+        return [steps.DensityPredictStep(density_fit)], ('density',), [DensityWriteHook()]
+    others = context.config.others
+    adaptive = _adaptive(context, world)
+    agreement = adaptive is None and _agreement(context, world)      # (beside a schedule the key is off: _RULES)
+    if hasattr(others, 'tta'):
+        return _tta_steps(context, world), (), []
+    if not hasattr(others, 'mc'):
+        return [steps.SegmentationPredictStep(do_probs=True)], (), []
+    # ``others.group_pixels`` / ``others.exact`` (rcu_amd extensions): the memory / reproducibility trade of the MC step.  Every stream lane of every
+    # rank sizes its plan for n x min(group_pixels // (n H W), T) samples (canonical plans: 24 GB per lane for four passes of a 160-slice BraTS
+    # batch) and ``exact`` keeps the statistics as exact float64 sums; a smaller ``group_pixels`` (or ``stream_lanes: 1``) shrinks the workspace,
+    # ``exact: false`` halves the statistics and the reduce at the price of byte-identity across lanes, groups and world sizes (INTEGRATION.md).
+    mc, options = others.mc, dict(lanes=_other(context, 'stream_lanes'), group_pixels=_other(context, 'group_pixels'))
+    if adaptive is not None:      # (the written map files keep their names: the slice rows only feed adaptive.csv)
+        return ([steps.McPredictStep(mc, seed=_adaptive_seed(context), adaptive=adaptive, **options), steps.MultiPredictionSummary(),
+                 AdaptiveRowsStep(adaptive['check_at'])], ('adaptive',), [AdaptiveCsvHook(adaptive['check_at'], mc)])
+    options.update(seed=_mask_seed(context, world), exact=bool(_other(context, 'exact', True)))
+    if agreement:
+        return ([steps.McPredictStep(mc, agreement=True, **options), steps.MultiPredictionSummary(), steps.SampleAgreementStep()], ('agreement',),
+                [AgreementCsvHook(mc)])
+    if world.world > 1:     # the T + 1 passes of every batch sharded over the ranks, one sum-reduce per batch (rcu_amd.distributed)
+        return [rdist.ShardedMcPredictStep(mc, world, **options), steps.MultiPredictionSummary()], (), []
+    return [steps.McPredictStep(mc, **options), steps.MultiPredictionSummary()], (), []
+
+
 def _default_steps(context, world):
-    adaptive = _adaptive(context, world)      # (refuses others.mc_adaptive beside tta, agreement, exact: false, several ranks, or without mc)
-    if hasattr(context.config.others, 'tta'):
-        _agreement(context, world)      # (refuses others.agreement: true)
-        return _tta_steps(context, world)
-    if not hasattr(context.config.others, 'mc'):
-        _agreement(context, world)
-    if adaptive is not None:
-        return [steps.McPredictStep(context.config.others.mc, seed=_adaptive_seed(context), lanes=_other(context, 'stream_lanes'),
-                                    group_pixels=_other(context, 'group_pixels'), adaptive=adaptive),
-                steps.MultiPredictionSummary(), AdaptiveRowsStep(adaptive['check_at'])]
-    if hasattr(context.config.others, 'mc'):
-        lanes = _other(context, 'stream_lanes')
-        # ``others.group_pixels`` / ``others.exact`` (rcu_amd extensions): the memory / reproducibility trade of the MC step.  Every stream lane of every
-        # rank sizes its plan for n x min(group_pixels // (n H W), T) samples (canonical plans: 24 GB per lane for four passes of a 160-slice BraTS
-        # batch) and ``exact`` keeps the statistics as exact float64 sums; a smaller ``group_pixels`` (or ``stream_lanes: 1``) shrinks the workspace,
-        # ``exact: false`` halves the statistics and the reduce at the price of byte-identity across lanes, groups and world sizes.
-        group_pixels, exact = _other(context, 'group_pixels'), bool(_other(context, 'exact', True))
-        if _agreement(context, world):      # (one process: refused above otherwise)
-            return [steps.McPredictStep(context.config.others.mc, seed=_mask_seed(context, world), lanes=lanes, group_pixels=group_pixels, exact=exact,
-                                        agreement=True),
-                    steps.MultiPredictionSummary(), steps.SampleAgreementStep()]
-        if world.world > 1:     # the T + 1 passes of every batch sharded over the ranks, one sum-reduce per batch (rcu_amd.distributed)
-            return [rdist.ShardedMcPredictStep(context.config.others.mc, world, seed=_mask_seed(context, world), lanes=lanes,
-                                               group_pixels=group_pixels, exact=exact),
-                    steps.MultiPredictionSummary()]
-        return [steps.McPredictStep(context.config.others.mc, seed=_mask_seed(context, world), lanes=lanes, group_pixels=group_pixels, exact=exact),
-                steps.MultiPredictionSummary()]
-    return [steps.SegmentationPredictStep(do_probs=True)]
+    return _default_plan(context, world)[0]
 
 
 def _hooks(write_hook, extra=()):
@@ -721,20 +739,38 @@ def _hooks(write_hook, extra=()):
     return loops.ReducedComposeTestLoopHook(hooks)
 
 
-def _load_additional_models(context):
-    """others.model_dir (list) + others.test_at -> extra ensemble members (brats_test_ensemble.py:37-57)."""
+def _other_model_dir(context):
     others = context.config.others
     if not hasattr(others, 'model_dir') or not hasattr(others, 'test_at'):
         raise ValueError('missing "model_dir" or "test_at" entry in the configuration (others)')
-    model_dirs = [others.model_dir] if isinstance(others.model_dir, str) else list(others.model_dir)
+    return others.model_dir
+
+
+def _load_model_at(context, model_dir, provide_features=False):
+    """The trained model of ``model_dir`` at ``others.test_at``, on the context's device, in eval mode."""
+    mf = mgt.ModelFiles.from_model_dir(model_dir)
+    model = mgt.load_model_from_parameters(mf.model_path())
+    if provide_features:
+        model.provide_features = True
+    mgt.load_checkpoint(mgt.find_checkpoint_file(mf.weight_checkpoint_dir, context.config.others.test_at), model)
+    return model.to(context.device).eval()
+
+
+def _load_additional_models(context):
+    """others.model_dir (list) + others.test_at -> extra ensemble members (brats_test_ensemble.py:37-57)."""
+    model_dirs = _other_model_dir(context)
+    model_dirs = [model_dirs] if isinstance(model_dirs, str) else list(model_dirs)
     models = []
     for i, model_dir in enumerate(model_dirs):
         logging.info('load additional model [{}/{}] {}'.format(i + 1, len(model_dirs), os.path.basename(model_dir)))
-        mf = mgt.ModelFiles.from_model_dir(model_dir)
-        model = mgt.load_model_from_parameters(mf.model_path())
-        mgt.load_checkpoint(mgt.find_checkpoint_file(mf.weight_checkpoint_dir, others.test_at), model)
-        models.append(model.to(context.device).eval())
+        models.append(_load_model_at(context, model_dir))
     return models
+
+
+def _load_segmentation_model(context):
+    """others.model_dir + others.test_at -> the trained segmentation U-Net with provide_features set
+    (brats_test_auxiliary_feat.py:35-46)."""
+    return _load_model_at(context, _other_model_dir(context), provide_features=True)
 
 
 def _loop_options(context):
@@ -759,15 +795,21 @@ def _context(device, config_file):
     return context, world
 
 
+def _nothing_to_shard(world):
+    """A run of one deterministic forward pass per batch has nothing to shard over samples: under a multi-process launch it is rank 0's alone
+    -> whether this rank leaves at once."""
+    if world.world > 1 and not world.is_root:
+        logging.info('rank {}: this configuration has one forward pass per batch, nothing to shard; rank 0 runs it'.format(world.rank))
+        return True
+    return False
+
+
 def _run(context, dataset, test_steps, write_hook, entries, world=None, startup_hooks=(), subject_hooks=()):
     """``startup_hooks`` run on every rank; ``subject_hooks`` (per-subject writers such as AgreementCsvHook) on the root alone, behind the write hook."""
     world = world if world is not None else rdist.World()
     sharded = [s_ for s_ in test_steps if isinstance(s_, rdist._ShardedStepBase)]
-    if world.world > 1 and not sharded:
-        # one deterministic forward pass per batch: nothing to shard over samples -- the run is rank 0's, the other ranks leave at once
-        if not world.is_root:
-            logging.info('rank {}: this configuration has one forward pass per batch, nothing to shard; rank 0 runs it'.format(world.rank))
-            return context
+    if not sharded and _nothing_to_shard(world):
+        return context
     build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
     options = _loop_options(context)
     extra_hooks = list(startup_hooks) + list(subject_hooks)
@@ -840,36 +882,18 @@ def _abandon_process_group(timeout_s=10.0):
 
 def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
+    _check_others(context, 'default', world)
     density_fit = _density(context)      # (refuses others.density beside the keys that sample)
-    _refuse_logit_samples(context, 'default')
-    entries = ('probabilities',) if dataset == 'brats' else None
     corrupt_steps, corrupt_hooks = _corruption(context)
-    extra = []
-    if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
-        test_steps = corrupt_steps + [steps.DensityPredictStep(density_fit)]
-        entries = None if entries is None else entries + ('density',)
-        extra.append(DensityWriteHook())
-    else:
-        test_steps = corrupt_steps + _default_steps(context, world)
-    if any(isinstance(s_, steps.SampleAgreementStep) for s_ in test_steps):
-        entries = None if entries is None else entries + ('agreement',)
-        extra.append(AgreementCsvHook(context.config.others.mc))
-    rows_step = next((s_ for s_ in test_steps if isinstance(s_, AdaptiveRowsStep)), None)
-    if rows_step is not None:      # (the written map files keep their names: the slice rows only feed adaptive.csv)
-        entries = None if entries is None else entries + ('adaptive',)
-        extra.append(AdaptiveCsvHook(rows_step.check_at, context.config.others.mc))
-    return _run(context, dataset, test_steps, WriteHook(link_inputs=dataset == 'isic'), entries, world,
-                startup_hooks=_temperature_hooks(context) + corrupt_hooks, subject_hooks=extra)
+    test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit)
+    return _run(context, dataset, corrupt_steps + test_steps, WriteHook(link_inputs=dataset == 'isic'),
+                ('probabilities',) + more_entries if dataset == 'brats' else None, world,
+                startup_hooks=_temperature_hooks(context) + corrupt_hooks, subject_hooks=subject_hooks)
 
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_ensemble.yaml'.format(dataset)))
-    _refuse_tta(context, 'ensemble')
-    _refuse_temperature(context, 'ensemble')
-    _refuse_agreement(context, 'ensemble')
-    _refuse_adaptive(context, 'ensemble')
-    _refuse_logit_samples(context, 'ensemble')
-    _refuse_density(context, 'ensemble')
+    _check_others(context, 'ensemble', world)
     corrupt_steps, corrupt_hooks = _corruption(context)
     members = _load_additional_models(context)
     lanes = _other(context, 'stream_lanes')
@@ -882,11 +906,7 @@ def test_ensemble(dataset, config_file=None, device='cuda'):
 
 def test_aleatoric(dataset, config_file=None, device='cuda'):
     context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_aleatoric.yaml'.format(dataset)))
-    _refuse_tta(context, 'aleatoric')
-    _refuse_temperature(context, 'aleatoric')
-    _refuse_agreement(context, 'aleatoric')
-    _refuse_adaptive(context, 'aleatoric')
-    _refuse_density(context, 'aleatoric')
+    _check_others(context, 'aleatoric', world)
     corrupt_steps, corrupt_hooks = _corruption(context)
     return _run(context, dataset, corrupt_steps + _aleatoric_steps(context, world), WriteHook(with_sigma=True, link_inputs=dataset == 'isic'),
                 None, world, startup_hooks=corrupt_hooks)
@@ -1005,80 +1025,45 @@ class WriteConfidenceHook(loops.TestLoopHook):
         nifti.join_all()
 
 
-def _load_segmentation_model(context):
-    """others.model_dir + others.test_at -> the trained segmentation U-Net with provide_features set
-    (brats_test_auxiliary_feat.py:35-46)."""
-    others = context.config.others
-    if not hasattr(others, 'model_dir') or not hasattr(others, 'test_at'):
-        raise ValueError('missing "model_dir" or "test_at" entry in the configuration (others)')
-    mf = mgt.ModelFiles.from_model_dir(others.model_dir)
-    model = mgt.load_model_from_parameters(mf.model_path())
-    model.provide_features = True
-    mgt.load_checkpoint(mgt.find_checkpoint_file(mf.weight_checkpoint_dir, others.test_at), model)
-    return model.to(context.device).eval()
-
-
-def _single_rank_only(world):
-    """The auxiliary-network runs are one deterministic forward pass per batch: under a multi-process launch they are rank 0's alone."""
-    if world.world > 1 and not world.is_root:
-        logging.info('rank {}: this configuration has one forward pass per batch, nothing to shard; rank 0 runs it'.format(world.rank))
-        return False
-    return True
+def _auxiliary(script, dataset, config_file, device, loop_of):
+    """What the two auxiliary scripts share.  ``loop_of(context)`` -> (batch steps, subject steps, assembler, entries, write hook, further
+    BuildData arguments) of the dataset: one deterministic forward pass per batch, so under a multi-process launch the run is rank 0's alone."""
+    context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_{}.yaml'.format(dataset, script)))
+    _check_others(context, script, world)
+    corrupt_steps, corrupt_hooks = _corruption(context)
+    if _nothing_to_shard(world):
+        return context
+    batch_steps, subject_steps, assembler, entries, hook, build_options = loop_of(context)
+    build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset(), **build_options)
+    test = loops.Test(corrupt_steps + batch_steps, subject_steps, assembler, entries=entries)
+    test(context, build, hook=_hooks(hook, corrupt_hooks))
+    return context
 
 
 def test_auxiliary_feat(dataset, config_file=None, device='cuda'):
-    context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_feat.yaml'.format(dataset)))
-    _refuse_tta(context, 'auxiliary_feat')
-    _refuse_temperature(context, 'auxiliary_feat')
-    _refuse_agreement(context, 'auxiliary_feat')
-    _refuse_adaptive(context, 'auxiliary_feat')
-    _refuse_logit_samples(context, 'auxiliary_feat')
-    _refuse_density(context, 'auxiliary_feat')
-    corrupt_steps, corrupt_hooks = _corruption(context)
-    if not _single_rank_only(world):
-        return context
-    test_model = _load_segmentation_model(context)
-    if dataset == 'brats':
-        build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset())
-        test = loops.Test(corrupt_steps + [AuxiliaryFeatPredictStep(test_model)], [loops.ExtractSubjectInfoStep(), EvalAuxiliaryFeatStep()],
-                          loops.SubjectAssembler(), entries=('probabilities', 'segm_probabilities'))
-        hook = WriteConfidenceHook('segm_probabilities')
-    else:
-        build = data_mod.BuildData(build_dataset=data_mod.BuildIsicDataset())
-        test = loops.Test(corrupt_steps + [AuxiliaryFeatPredictStep(test_model), PrepareSubjectStep()],
-                          [EvalAuxiliaryFeatStep(squeeze_labels=True)], loops.Subject2dAssembler(),
-                          entries=('probabilities', 'segm_probabilities', 'labels'))
-        hook = WriteConfidenceHook('segm_probabilities', link=('label_paths',))
-    test(context, build, hook=_hooks(hook, corrupt_hooks))
-    return context
+    def loop_of(context):
+        predict = AuxiliaryFeatPredictStep(_load_segmentation_model(context))
+        if dataset == 'brats':
+            return ([predict], [loops.ExtractSubjectInfoStep(), EvalAuxiliaryFeatStep()], loops.SubjectAssembler(),
+                    ('probabilities', 'segm_probabilities'), WriteConfidenceHook('segm_probabilities'), {})
+        return ([predict, PrepareSubjectStep()], [EvalAuxiliaryFeatStep(squeeze_labels=True)], loops.Subject2dAssembler(),
+                ('probabilities', 'segm_probabilities', 'labels'), WriteConfidenceHook('segm_probabilities', link=('label_paths',)), {})
+
+    return _auxiliary('auxiliary_feat', dataset, config_file, device, loop_of)
 
 
 def test_auxiliary_segm(dataset, config_file=None, device='cuda'):
-    context, world = _context(device, config_file or os.path.join(CONFIG_DIR, 'test_{}_auxiliary_segm.yaml'.format(dataset)))
-    _refuse_tta(context, 'auxiliary_segm')
-    _refuse_temperature(context, 'auxiliary_segm')
-    _refuse_agreement(context, 'auxiliary_segm')
-    _refuse_adaptive(context, 'auxiliary_segm')
-    _refuse_logit_samples(context, 'auxiliary_segm')
-    _refuse_density(context, 'auxiliary_segm')
-    corrupt_steps, corrupt_hooks = _corruption(context)
-    if not _single_rank_only(world):
-        return context
-    if dataset == 'brats':
-        build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset())
-        test = loops.Test(corrupt_steps + [AuxiliarySegmPredictStep()], [loops.ExtractSubjectInfoStep(), EvalAuxiliarySegmStep()],
-                          loops.SubjectAssembler(), entries=('probabilities', 'orig_prediction'))
-        hook = WriteConfidenceHook('orig_prediction')
-    else:
+    def loop_of(context):
+        if dataset == 'brats':
+            return ([AuxiliarySegmPredictStep()], [loops.ExtractSubjectInfoStep(), EvalAuxiliarySegmStep()], loops.SubjectAssembler(),
+                    ('probabilities', 'orig_prediction'), WriteConfidenceHook('orig_prediction'), {})
         if not hasattr(context.config.others, 'prediction_dir'):
             raise ValueError('"others.prediction_dir" is required in the config')
-        build = data_mod.BuildData(build_dataset=data_mod.BuildIsicDataset(),
-                                   prediction_dir=context.config.others.prediction_dir)
-        test = loops.Test(corrupt_steps + [AuxiliarySegmPredictStep(keep_labels=True)], [EvalAuxiliarySegmStep(set_score=True)],
-                          loops.Subject2dAssembler(), entries=('probabilities', 'labels', 'orig_prediction'))
-        hook = WriteConfidenceHook('orig_prediction', link=('label_paths', 'image_paths'))
-    test(context, build, hook=_hooks(hook, corrupt_hooks))
-    return context
+        return ([AuxiliarySegmPredictStep(keep_labels=True)], [EvalAuxiliarySegmStep(set_score=True)], loops.Subject2dAssembler(),
+                ('probabilities', 'labels', 'orig_prediction'), WriteConfidenceHook('orig_prediction', link=('label_paths', 'image_paths')),
+                dict(prediction_dir=context.config.others.prediction_dir))
+
+    return _auxiliary('auxiliary_segm', dataset, config_file, device, loop_of)
 
 
 # ------------------------------------------------------------------------------- temperature scaling (EXTENSION)
@@ -1109,41 +1094,42 @@ def _validation_batches(context, dataset, device):
         yield images, target
 
 
-def fit_temperature(dataset, config_file, device='cuda'):
-    """bin-dl/{brats,isic}_fit_temperature.py (EXTENSION): fit the temperature of a test configuration's model on the volumes its ``test_data``
-    names -- the VALIDATION volumes -- by the NLL of the pass-averaged prediction (``others.mc`` passes with the YAML ``seed``, 0 without one,
-    else one eval-mode pass), on all voxels, target labels > 0.  Writes ``temperature.json`` into the run directory and returns the fit;
-    ``others.temperature: <that file>`` applies it in the default test scripts."""
+def _fit_context(script, dataset, config_file, device, check_model):
+    """What the fit scripts share up to the fit itself -> (context, seed) with the model loaded and checked (``check_model(model)`` raises), the run
+    directory and its log set up, the generators seeded with the YAML ``seed`` (0 without one) and ``test_data`` built: one process, one loader."""
     if dataset not in ('brats', 'isic'):
         raise ValueError('chose "brats" or "isic" as dataset')
     context, world = _context(device, config_file)
     if world.world > 1:
-        raise ValueError('the temperature fit runs in one process; launch it without torch.distributed.run')
-    others = context.config.others
-    if hasattr(others, 'tta'):
-        raise ValueError('others.tta: the temperature fit does not run under test-time augmentation')
-    _refuse_temperature(context, 'fit_temperature')
-    _refuse_logit_samples(context, 'fit_temperature')
-    _refuse_agreement(context, 'fit_temperature')
-    _refuse_adaptive(context, 'fit_temperature')
-    _refuse_corruption(context, 'fit_temperature')
-    _refuse_density(context, 'fit_temperature')
-    mc = int(getattr(others, 'mc', 0) or 0)
+        raise ValueError('the {} fit runs in one process; launch it without torch.distributed.run'.format(script[len('fit_'):]))
+    _check_others(context, script, world)
     seed = 0 if context.config.seed is None else int(context.config.seed)
     context.load_from_checkpoint(context.get_test_at())
-    model = context.model
+    check_model(context.model)
+    context.setup_directory()
+    context.setup_logging()
+    context.do_seed(seed)
+    context.load_test_data(data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset()))
+    return context, seed
+
+
+def _check_temperature_model(model):
     if not hasattr(model, 'set_temperature'):
         raise ValueError('the temperature fit needs a U-Net segmentation model')
     if model.sigma_out:
         raise ValueError('the temperature fit is not defined for a sigma_out model (its sigma is in logit units)')
     if model.nb_classes != 2:
         raise ValueError('the temperature fit scripts take binary models (nb_classes = 2), got {}'.format(model.nb_classes))
-    context.setup_directory()
-    context.setup_logging()
-    context.do_seed(seed)
-    build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
-    context.load_test_data(build)
-    fit = calibration.fit_temperature(model, _validation_batches(context, dataset, context.device), mc_steps=mc, seed=seed,
+
+
+def fit_temperature(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_temperature.py (EXTENSION): fit the temperature of a test configuration's model on the volumes its ``test_data``
+    names -- the VALIDATION volumes -- by the NLL of the pass-averaged prediction (``others.mc`` passes with the YAML ``seed``, 0 without one,
+    else one eval-mode pass), on all voxels, target labels > 0.  Writes ``temperature.json`` into the run directory and returns the fit;
+    ``others.temperature: <that file>`` applies it in the default test scripts."""
+    context, seed = _fit_context('fit_temperature', dataset, config_file, device, _check_temperature_model)
+    mc = int(_other(context, 'mc', 0) or 0)
+    fit = calibration.fit_temperature(context.model, _validation_batches(context, dataset, context.device), mc_steps=mc, seed=seed,
                                       group_pixels=_other(context, 'group_pixels'))
     record = dict(fit.as_dict(), model_dir=context.config.model_dir, test_at=context.config.test_at,
                   dataset=context.config.test_data.dataset, mc=mc)
@@ -1163,30 +1149,9 @@ def fit_density(dataset, config_file, device='cuda'):
     target labels > 0 (K = 2).  ``others.density_ridge`` (1e-6) and ``others.density_shared_covariance`` (false) are the fit's options.  Writes
     ``density.npz`` and a readable ``density.json`` into the run directory and returns the fit; ``others.density: <that .npz>`` applies it in the
     default test scripts."""
-    if dataset not in ('brats', 'isic'):
-        raise ValueError('chose "brats" or "isic" as dataset')
-    context, world = _context(device, config_file)
-    if world.world > 1:
-        raise ValueError('the density fit runs in one process; launch it without torch.distributed.run')
-    others = context.config.others
-    for key in ('tta', 'mc'):
-        if hasattr(others, key):
-            raise ValueError('others.{}: the density fit is one eval-mode pass per batch and does not take it'.format(key))
-    _refuse_temperature(context, 'fit_density')
-    _refuse_logit_samples(context, 'fit_density')
-    _refuse_agreement(context, 'fit_density')
-    _refuse_adaptive(context, 'fit_density')
-    _refuse_corruption(context, 'fit_density')
-    _refuse_density(context, 'fit_density')
-    context.load_from_checkpoint(context.get_test_at())
-    model = context.model
-    density_mod._feature_channels(model)      # (refuses a model that is no U-Net)
-    context.setup_directory()
-    context.setup_logging()
-    context.do_seed(0 if context.config.seed is None else int(context.config.seed))
-    build = data_mod.BuildData(build_dataset=data_mod.BuildVolumeDataset() if dataset == 'brats' else data_mod.BuildIsicDataset())
-    context.load_test_data(build)
-    fit = density_mod.fit_density(model, _validation_batches(context, dataset, context.device), ridge=float(_other(context, 'density_ridge', 1e-6)),
+    context, _ = _fit_context('fit_density', dataset, config_file, device, density_mod._feature_channels)      # (refuses a model that is no U-Net)
+    fit = density_mod.fit_density(context.model, _validation_batches(context, dataset, context.device),
+                                  ridge=float(_other(context, 'density_ridge', 1e-6)),
                                   shared_covariance=bool(_other(context, 'density_shared_covariance', False)), nb_classes=2)
     path = os.path.join(context.test_dir, 'density.npz')
     density_mod.save_density(fit, path)
