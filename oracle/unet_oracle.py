@@ -85,7 +85,7 @@ def unet_plan(nb_classes, in_channels, depth=4, start_filters=16, dropout=0.2, d
 
 def _number_layers(plan):
     """op['index'] of every conv unit, up-convolution and residual 1x1 conv: the layer's position in the GPU plan (rcu_unet_layer_info order,
-    csrc/rcu_api.hip build_plan_for).  That order is the execution order, except that a residual block's 1x1 conv runs between the block's two
+    csrc/rcu_plan.hip build_plan_for).  That order is the execution order, except that a residual block's 1x1 conv runs between the block's two
     units (the second unit adds into its output), and conv_sigma.0 shares the row of conv_cls.0 (one kernel computes the twin)."""
     index = 0
     first_of_residual_block = False

@@ -119,8 +119,9 @@ __global__ __launch_bounds__(AD_THREADS) void mc_slice_scores_kernel(const doubl
         default: return hipErrorInvalidValue;                        \
     }
 
-hipError_t launch_mc_slice_scores(const void* stats, int C, size_t N, size_t HW, long long thr_q, uint32_t* unsettled, long long* margin_q,
-                                  hipStream_t stream)
+// float64 statistics only (MC_EXACT): unsettled[i] = #{v in slice i : (int64)(max_c S_c(v) * 2^40) < thr_q}, margin_q[i] = the smallest such integer
+static hipError_t launch_mc_slice_scores(const void* stats, int C, size_t N, size_t HW, long long thr_q, uint32_t* unsettled, long long* margin_q,
+                                         hipStream_t stream)
 {
     hipLaunchKernelGGL(mc_scores_init_kernel, dim3((unsigned)((N + AD_THREADS - 1) / AD_THREADS)), dim3(AD_THREADS), 0, stream, unsettled, margin_q,
                        (int)N);
@@ -207,7 +208,8 @@ static hipError_t launch_merge_as(const void* src, void* dst, size_t units, size
     return hipGetLastError();
 }
 
-hipError_t launch_mc_merge_slices(const void* src, size_t M, void* dst, size_t N, size_t HW, int C, int flags, const int32_t* index, hipStream_t stream)
+// every plane: dst[plane][index[i]] += src[plane][i], i < M; entries outside [0, N) are skipped; the others must be distinct
+static hipError_t launch_mc_merge_slices(const void* src, size_t M, void* dst, size_t N, size_t HW, int C, int flags, const int32_t* index, hipStream_t stream)
 {
     const size_t planes = (size_t)C + ((flags & MC_VAR) ? (size_t)C : 0) + ((flags & MC_MI) ? 1 : 0);
     const size_t rows = planes * M;
@@ -327,8 +329,9 @@ __global__ __launch_bounds__(AD_THREADS) void mc_finalize_counts4_kernel(const v
     if (var != nullptr && (flags & MC_VAR)) var[i] = float4{vr[0], vr[1], vr[2], vr[3]};
 }
 
-hipError_t launch_mc_finalize_counts(const void* stats, int C, size_t N, size_t HW, const int32_t* counts, int flags, float* mean, float* entropy,
-                                     float* mi, float* var, hipStream_t stream)
+// launch_mc_finalize (rcu_pointwise.hip) with T = counts[slice] (device array of N entries >= 1)
+static hipError_t launch_mc_finalize_counts(const void* stats, int C, size_t N, size_t HW, const int32_t* counts, int flags, float* mean, float* entropy,
+                                            float* mi, float* var, hipStream_t stream)
 {
     const size_t V = N * HW;
     // the condition of launch_mc_finalize's four-voxel form (rcu_pointwise.hip, vec4_ok)
@@ -344,3 +347,65 @@ hipError_t launch_mc_finalize_counts(const void* stats, int C, size_t N, size_t 
 }
 
 }  // namespace rcu
+
+// ------------------------------------------------------------------------------------------------
+// entry points (include/rcu.h "Adaptive MC").  A HIP error is reported under the text of the call that returned it.
+// ------------------------------------------------------------------------------------------------
+using namespace rcu;
+
+// slices of hw voxels whose rows, row blocks and voxel quads stay inside the kernels' 32-bit indices
+static int check_adaptive_shape(const char* fn, size_t n, size_t hw, int C)
+{
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n < 1 || hw < 1 || n > ((size_t)1 << 20) || hw > ((size_t)1 << 30))
+        return report_error(RCU_ERR_INVALID, std::string(fn) + ": n must be in 1..2^20 and hw in 1..2^30");
+    return RCU_OK;
+}
+
+extern "C" int rcu_mc_slice_scores(const void* stats_dev, size_t n, size_t hw, int C, int flags, int64_t thr_q, uint32_t* unsettled_dev,
+                                   int64_t* margin_q_dev, void* stream)
+{
+    if (!stats_dev || !unsettled_dev || !margin_q_dev) return report_error(RCU_ERR_INVALID, "rcu_mc_slice_scores: null argument");
+    if (check_adaptive_shape("rcu_mc_slice_scores", n, hw, C)) return RCU_ERR_INVALID;
+    if (!(flags & RCU_MC_EXACT) || (flags & ~(RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT)))
+        return report_error(RCU_ERR_INVALID, "rcu_mc_slice_scores: needs RCU_MC_EXACT statistics (the decision is made on exact integer sums), got flags " +
+                                                 std::to_string(flags));
+    if (thr_q < 0) return report_error(RCU_ERR_INVALID, "rcu_mc_slice_scores: thr_q must be >= 0");
+    if (reinterpret_cast<uintptr_t>(stats_dev) % 8 != 0) return report_error(RCU_ERR_INVALID, "rcu_mc_slice_scores: stats must be 8-byte aligned");
+    const hipError_t e = launch_mc_slice_scores(stats_dev, C, n, hw, (long long)thr_q, unsettled_dev, reinterpret_cast<long long*>(margin_q_dev),
+                                                static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_mc_slice_scores(stats_dev, C, n, hw, (long long)thr_q, unsettled_dev, reinterpret_cast<long long*>(margin_q_dev), "
+                                        "static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_mc_merge_slices(const void* src_stats_dev, size_t m, void* dst_stats_dev, size_t n, size_t hw, int C, int flags,
+                                   const int32_t* index_dev, void* stream)
+{
+    if (!src_stats_dev || !dst_stats_dev || !index_dev) return report_error(RCU_ERR_INVALID, "rcu_mc_merge_slices: null argument");
+    if (check_adaptive_shape("rcu_mc_merge_slices", n, hw, C) || check_adaptive_shape("rcu_mc_merge_slices", m, hw, C)) return RCU_ERR_INVALID;
+    if (flags & ~(RCU_MC_MI | RCU_MC_VAR | RCU_MC_EXACT))
+        return report_error(RCU_ERR_INVALID, "rcu_mc_merge_slices: flags must be a combination of RCU_MC_MI, RCU_MC_VAR and RCU_MC_EXACT, got " +
+                                                 std::to_string(flags));
+    const uintptr_t s = reinterpret_cast<uintptr_t>(src_stats_dev), d = reinterpret_cast<uintptr_t>(dst_stats_dev);
+    const size_t element = (flags & (RCU_MC_VAR | RCU_MC_EXACT)) ? 8 : 4;
+    if (s % element != 0 || d % element != 0) return report_error(RCU_ERR_INVALID, "rcu_mc_merge_slices: blobs must be aligned to their element");
+    if (s < d + rcu_mc_stats_bytes(n, hw, C, flags) && d < s + rcu_mc_stats_bytes(m, hw, C, flags))
+        return report_error(RCU_ERR_INVALID, "rcu_mc_merge_slices: src and dst must not overlap");
+    const hipError_t e = launch_mc_merge_slices(src_stats_dev, m, dst_stats_dev, n, hw, C, flags, index_dev, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_mc_merge_slices(src_stats_dev, m, dst_stats_dev, n, hw, C, flags, index_dev, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_mc_finalize_counts(const void* stats, size_t n, size_t hw, int C, const int32_t* counts_dev, int flags, float* mean,
+                                      float* entropy, float* mi, float* var, void* stream)
+{
+    if (!stats || !counts_dev) return report_error(RCU_ERR_INVALID, "rcu_mc_finalize_counts: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (mi && !(flags & RCU_MC_MI)) return report_error(RCU_ERR_INVALID, "mutual_info requested without RCU_MC_MI statistics");
+    if (var && !(flags & RCU_MC_VAR)) return report_error(RCU_ERR_INVALID, "variance requested without RCU_MC_VAR statistics");
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_mc_finalize_counts(stats, C, n, hw, counts_dev, flags, mean, entropy, mi, var, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_mc_finalize_counts(stats, C, n, hw, counts_dev, flags, mean, entropy, mi, var, static_cast<hipStream_t>(stream))", e);
+}

@@ -129,7 +129,7 @@ static inline unsigned blocks_per_volume(size_t n) { return (unsigned)((n + ELEM
 // per workgroup and with it the chip full: at least four rounds of workgroups stay.  `forced`: rcu_calib_set_blocks_per_workgroup
 // (test / tuning aid; 0 = this rule).
 static int g_forced_blocks[2] = {0, 0};   // [ece, unc]
-void calib_set_blocks_per_workgroup(int ece, int unc)
+static void calib_set_blocks_per_workgroup(int ece, int unc)
 {
     g_forced_blocks[0] = ece;
     g_forced_blocks[1] = unc;
@@ -148,7 +148,7 @@ static inline unsigned blocks_per_workgroup(unsigned blocks, int n_volumes, unsi
 struct EceAccum {
     unsigned long long count, sum_pos, sum_lo, sum_hi;
 };
-size_t ece_workspace_bytes(size_t n_per_volume, int n_volumes)
+static size_t ece_workspace_bytes(size_t n_per_volume, int n_volumes)
 {
     (void)n_per_volume;
     return (size_t)n_volumes * MAX_BINS * sizeof(EceAccum);
@@ -318,8 +318,8 @@ __global__ __launch_bounds__(RED_THREADS) void ece_reduce_kernel(const EceAccum*
     result[vol].sum_conf[b] = ((double)hi * 4294967296.0 + (double)lo) * (1.0 / (double)(1ull << ECE_FIX_BITS));
 }
 
-hipError_t launch_ece_hist(const float* p, const uint8_t* target, const uint8_t* mask, size_t n, int n_volumes,
-                           const float* thr_host, int n_bins, EceResult* result_dev, void* workspace, hipStream_t stream)
+static hipError_t launch_ece_hist(const float* p, const uint8_t* target, const uint8_t* mask, size_t n, int n_volumes,
+                                  const float* thr_host, int n_bins, EceResult* result_dev, void* workspace, hipStream_t stream)
 {
     if (n_bins < 1 || n_bins > MAX_BINS || n_volumes < 1) return hipErrorInvalidValue;
     BinThresholds th;
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(CB_THREADS) void bin_ids_kernel(const float* __rest
     if (i < n) ids[i] = (uint8_t)bin_of(p[i], th);
 }
 
-hipError_t launch_bin_ids(const float* p, size_t n, const float* thr_host, int n_bins, uint8_t* ids, hipStream_t stream)
+static hipError_t launch_bin_ids(const float* p, size_t n, const float* thr_host, int n_bins, uint8_t* ids, hipStream_t stream)
 {
     if (n_bins < 1 || n_bins > MAX_BINS) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
@@ -382,7 +382,7 @@ static constexpr int UNC_MAX_BLOCKS = 8;              // blocks per workgroup of
 
 // Workspace of the counts: one row of UNC_SLOTS accumulators per volume, added to with integer atomics by the workgroups (exact,
 // order-free) and turned into the output layout by a small second kernel; the launcher zeroes it.
-size_t unc_workspace_bytes(size_t n_per_volume, int n_volumes)
+static size_t unc_workspace_bytes(size_t n_per_volume, int n_volumes)
 {
     (void)n_per_volume;
     return (size_t)n_volumes * UNC_SLOTS * sizeof(unsigned long long);
@@ -636,9 +636,10 @@ __global__ __launch_bounds__(RED_THREADS) void unc_reduce_kernel(const unsigned 
     o[4 + cell] = row[t * 4 + cell];      // tpu, tnu, fpu, fnu
 }
 
-hipError_t launch_unc_counts(const void* unc, int unc_is_f64, const uint8_t* prediction, const uint8_t* target,
-                             const uint8_t* mask, size_t n, int n_volumes, const double* thr_host, int n_thr,
-                             unsigned long long* out_dev, void* workspace, hipStream_t stream)
+// out_dev: [n_volumes][n_thr][8] u64 = tp, tn, fp, fn, tpu, tnu, fpu, fnu
+static hipError_t launch_unc_counts(const void* unc, int unc_is_f64, const uint8_t* prediction, const uint8_t* target,
+                                    const uint8_t* mask, size_t n, int n_volumes, const double* thr_host, int n_thr,
+                                    unsigned long long* out_dev, void* workspace, hipStream_t stream)
 {
     if (n_thr < 1 || n_thr > MAX_THR || n_volumes < 1) return hipErrorInvalidValue;
     UncThresholds th;
@@ -775,9 +776,9 @@ static bool ue_p_build(const double* thr, int n_thr, UePCell* cells, unsigned lo
     return m == 0;
 }
 
-int unc_from_p_num_thresholds() { return UE_P_ROWS; }
-double unc_from_p_threshold(int i) { return (i >= 0 && i < UE_P_ROWS) ? UE_P_TABLE[i].thr : -1.0; }
-bool unc_from_p_supported(const double* thr, int n_thr)
+static int unc_from_p_num_thresholds() { return UE_P_ROWS; }
+static double unc_from_p_threshold(int i) { return (i >= 0 && i < UE_P_ROWS) ? UE_P_TABLE[i].thr : -1.0; }
+static bool unc_from_p_supported(const double* thr, int n_thr)
 {
     UePCell cells[UE_P_CELLS];
     unsigned long long masks[(2 * MAX_THR + 1) * UE_P_MASK_WORDS];
@@ -785,13 +786,13 @@ bool unc_from_p_supported(const double* thr, int n_thr)
 }
 
 static constexpr size_t UE_P_TABLE_BYTES = sizeof(UePCell) * UE_P_CELLS + sizeof(unsigned long long) * (2 * MAX_THR + 1) * UE_P_MASK_WORDS;
-size_t unc_from_p_workspace_bytes(size_t n_per_volume, int n_volumes)
+static size_t unc_from_p_workspace_bytes(size_t n_per_volume, int n_volumes)
 {
     return unc_workspace_bytes(n_per_volume, n_volumes) + UE_P_TABLE_BYTES;
 }
 
 // Reference-side evaluation of the table for one probability (test aid + the launcher's tiny-input path)
-int unc_from_p_exceeded_host(float p, const double* thr, int n_thr)
+static int unc_from_p_exceeded_host(float p, const double* thr, int n_thr)
 {
     unsigned b;
     std::memcpy(&b, &p, 4);
@@ -808,9 +809,9 @@ int unc_from_p_exceeded_host(float p, const double* thr, int n_thr)
     return m;
 }
 
-hipError_t launch_unc_counts_from_p(const float* p_fg, const uint8_t* prediction, const uint8_t* target, const uint8_t* mask, size_t n,
-                                    int n_volumes, const double* thr_host, int n_thr, unsigned long long* out_dev, void* workspace,
-                                    hipStream_t stream)
+static hipError_t launch_unc_counts_from_p(const float* p_fg, const uint8_t* prediction, const uint8_t* target, const uint8_t* mask, size_t n,
+                                           int n_volumes, const double* thr_host, int n_thr, unsigned long long* out_dev, void* workspace,
+                                           hipStream_t stream)
 {
     if (n_volumes < 1) return hipErrorInvalidValue;
     // the table travels with every call (4.4 KB, stream-ordered; pageable source: the runtime stages it before the call returns)
@@ -850,7 +851,7 @@ __global__ __launch_bounds__(CB_THREADS) void norm_entropy_kernel(const float* _
     if (out32) out32[i] = (float)h;
 }
 
-hipError_t launch_norm_entropy(const float* p_fg, size_t n, double* out_f64, float* out_f32, hipStream_t stream)
+static hipError_t launch_norm_entropy(const float* p_fg, size_t n, double* out_f64, float* out_f32, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(norm_entropy_kernel, dim3((unsigned)((n + CB_THREADS - 1) / CB_THREADS)), dim3(CB_THREADS), 0,
@@ -859,3 +860,104 @@ hipError_t launch_norm_entropy(const float* p_fg, size_t n, double* out_f64, flo
 }
 
 }  // namespace rcu
+
+// ------------------------------------------------------------------------------------------------
+// metric seam (include/rcu.h).  A HIP error is reported under the text of the call that returned it.
+// ------------------------------------------------------------------------------------------------
+using namespace rcu;
+
+static_assert(sizeof(rcu_ece_result) == sizeof(EceResult), "ABI struct mismatch");
+static_assert(RCU_MAX_BINS == MAX_BINS && RCU_MAX_THRESHOLDS == MAX_THR, "ABI constant mismatch");
+
+extern "C" int rcu_ece_thresholds(int n_bins, float* thr)
+{
+    if (n_bins < 1 || n_bins > MAX_BINS || !thr) return report_error(RCU_ERR_INVALID, "n_bins must be in 1..32");
+    // edges = np.linspace(0, 1 + 1e-8, n_bins + 1): start + k * step with step = (stop - start) / n_bins
+    const double stop = 1.0 + 1e-8, step = stop / n_bins;
+    for (int k = 1; k < n_bins; ++k) {
+        const double edge = k * step;
+        float t = (float)edge;
+        if ((double)t < edge) t = std::nextafterf(t, INFINITY);
+        thr[k - 1] = t;
+    }
+    return RCU_OK;
+}
+
+extern "C" size_t rcu_ece_workspace_bytes(size_t n, int nv) { return ece_workspace_bytes(n, nv < 1 ? 1 : nv); }
+
+extern "C" int rcu_ece_hist(const float* p, const uint8_t* target, const uint8_t* mask, size_t n, int n_volumes,
+                            const float* thr, int n_bins, rcu_ece_result* result, void* workspace, void* stream)
+{
+    if (!result || !thr || (n && (!p || !target || !workspace)))
+        return report_error(RCU_ERR_INVALID, "rcu_ece_hist: null argument");
+    if (n_bins < 1 || n_bins > MAX_BINS || n_volumes < 1) return report_error(RCU_ERR_INVALID, "rcu_ece_hist: bad n_bins / n_volumes");
+    const hipError_t e = launch_ece_hist(p, target, mask, n, n_volumes, thr, n_bins, reinterpret_cast<EceResult*>(result), workspace,
+                                         static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_ece_hist(p, target, mask, n, n_volumes, thr, n_bins, reinterpret_cast<EceResult*>(result), workspace, "
+                                        "static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_ece_bin_ids(const float* p, size_t n, const float* thr, int n_bins, uint8_t* ids, void* stream)
+{
+    if ((n && (!p || !ids)) || !thr) return report_error(RCU_ERR_INVALID, "rcu_ece_bin_ids: null argument");
+    if (n_bins < 1 || n_bins > MAX_BINS) return report_error(RCU_ERR_INVALID, "n_bins must be in 1..32");
+    const hipError_t e = launch_bin_ids(p, n, thr, n_bins, ids, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_bin_ids(p, n, thr, n_bins, ids, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_calib_set_blocks_per_workgroup(int ece_blocks, int unc_blocks)
+{
+    if (ece_blocks < 0 || unc_blocks < 0) return report_error(RCU_ERR_INVALID, "rcu_calib_set_blocks_per_workgroup: negative block count");
+    calib_set_blocks_per_workgroup(ece_blocks, unc_blocks);
+    return RCU_OK;
+}
+
+extern "C" size_t rcu_unc_workspace_bytes(size_t n, int nv) { return unc_workspace_bytes(n, nv < 1 ? 1 : nv); }
+
+extern "C" int rcu_unc_counts(const void* unc, int unc_is_f64, const uint8_t* prediction, const uint8_t* target,
+                              const uint8_t* mask, size_t n, int n_volumes, const double* thr, int n_thr, uint64_t* counts,
+                              void* workspace, void* stream)
+{
+    if (!counts || !thr || (n && (!unc || !prediction || !target || !workspace)))
+        return report_error(RCU_ERR_INVALID, "rcu_unc_counts: null argument");
+    if (n_thr < 1 || n_thr > MAX_THR || n_volumes < 1)
+        return report_error(RCU_ERR_INVALID, "rcu_unc_counts: n_thr must be in 1..16 and n_volumes >= 1");
+    const hipError_t e = launch_unc_counts(unc, unc_is_f64, prediction, target, mask, n, n_volumes, thr, n_thr,
+                                           reinterpret_cast<unsigned long long*>(counts), workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_unc_counts(unc, unc_is_f64, prediction, target, mask, n, n_volumes, thr, n_thr, "
+                                        "reinterpret_cast<unsigned long long*>(counts), workspace, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_unc_from_p_num_thresholds(void) { return unc_from_p_num_thresholds(); }
+extern "C" double rcu_unc_from_p_threshold(int i) { return unc_from_p_threshold(i); }
+extern "C" int rcu_unc_from_p_supported(const double* thr, int n_thr) { return (thr && unc_from_p_supported(thr, n_thr)) ? 1 : 0; }
+extern "C" int rcu_unc_from_p_exceeded(float p, const double* thr, int n_thr)
+{
+    if (!thr || n_thr < 1 || n_thr > MAX_THR) return -1;
+    return unc_from_p_exceeded_host(p, thr, n_thr);
+}
+extern "C" size_t rcu_unc_from_p_workspace_bytes(size_t n, int nv) { return unc_from_p_workspace_bytes(n, nv < 1 ? 1 : nv); }
+
+extern "C" int rcu_unc_counts_from_p(const float* p, const uint8_t* prediction, const uint8_t* target, const uint8_t* mask, size_t n,
+                                     int n_volumes, const double* thr, int n_thr, uint64_t* counts, void* workspace, void* stream)
+{
+    if (!thr || !counts || !workspace || (n && (!p || !prediction || !target)))
+        return report_error(RCU_ERR_INVALID, "rcu_unc_counts_from_p: null argument");
+    if (n_thr < 1 || n_thr > MAX_THR || n_volumes < 1) return report_error(RCU_ERR_INVALID, "rcu_unc_counts_from_p: bad n_thr / n_volumes");
+    if (!unc_from_p_supported(thr, n_thr))
+        return report_error(RCU_ERR_INVALID, "rcu_unc_counts_from_p: thresholds must be strictly ascending values of the built-in table (rcu_unc_from_p_threshold)");
+    const hipError_t e = launch_unc_counts_from_p(p, prediction, target, mask, n, n_volumes, thr, n_thr, reinterpret_cast<unsigned long long*>(counts),
+                                                  workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_unc_counts_from_p(p, prediction, target, mask, n, n_volumes, thr, n_thr, "
+                                        "reinterpret_cast<unsigned long long*>(counts), workspace, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_normalised_entropy(const float* p_fg, size_t n, double* out64, float* out32, void* stream)
+{
+    if (n && !p_fg) return report_error(RCU_ERR_INVALID, "rcu_normalised_entropy: null argument");
+    const hipError_t e = launch_norm_entropy(p_fg, n, out64, out32, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_norm_entropy(p_fg, n, out64, out32, static_cast<hipStream_t>(stream))", e);
+}

@@ -59,7 +59,7 @@ struct ConvTile {
     // rows of equal parity 8 slots apart: conflict-free with 2/3 of the LDS bytes and staging traffic of the padded
     // layout.  Weights: a group reads channels {0-3, 12-15, 20-27} (or the complement) of a 32-channel block; swapping
     // the halves for channels 16..31 (mod 32) separates them the same way.  The packed weight tiles carry that
-    // permutation (rcu_api.hip).
+    // permutation (rcu_wpack.h).
     static constexpr bool SWZ = SWZ_ != 0;
     static constexpr int TAPW = (TAPS == 9) ? 3 : 2;        // taps per window row
     static constexpr int THREADS = 256;
@@ -130,7 +130,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x16 (&
     const bool full_tile = (y0 + T::TH <= a.H) && (x0 + T::TW <= a.W) && (n0 + T::TS <= a.N);
     const size_t row_stride = (size_t)OW * a.CoutP * OS, col_stride = (size_t)a.CoutP * OS;
     const int Hp = a.H >> 1, Wp = a.W >> 1;
-    // the pooled tensor may belong to a padded level (ConvArgs::pool_H / pool_W, rcu_api.hip choose_level_extents): its own extents, our pixels
+    // the pooled tensor may belong to a padded level (ConvArgs::pool_H / pool_W, rcu_plan.hip plan_unet): its own extents, our pixels
     const int PHs = a.pool_H > 0 ? a.pool_H : Hp, PWs = a.pool_W > 0 ? a.pool_W : Wp;
 #pragma unroll
     for (int ni = 0; ni < NTW; ++ni) {

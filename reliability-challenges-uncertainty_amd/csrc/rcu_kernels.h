@@ -10,10 +10,10 @@
 
 namespace rcu {
 
-// rcu_last_error() of the calling thread := msg; returns code (the entry points of the other translation units report through it, rcu_api.hip)
+// rcu_last_error() of the calling thread := msg; returns code (defined in rcu_api.hip; every translation unit's entry points report through it)
 int report_error(int code, const std::string& msg);
 
-// host helpers of the evaluation extensions' entry points (rcu_unc_hist.hip, rcu_cc.hip, rcu_edt.hip)
+// host helpers of the entry points that live next to their kernels
 inline int hip_failed(const char* fn, hipError_t e) { return report_error(RCU_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e)); }
 inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int check_n_volumes(const std::string& f, int n_volumes, int max_volumes)
@@ -61,7 +61,7 @@ struct ConvArgs {
     int out_H, out_W;    // sub-pixel up-conv (direct kernels): extent of the output tensor when it is larger than 2H x 2W -- the
     int out_y0, out_x0;  //   reference's centre pad (common/model/unet.py:110-116) -- and where the 2H x 2W image sits in it; 0: 2H x 2W
     int N, H, W;         // input grid = pixel-tile grid
-    // Padded levels (`part` = 1; Winograd kernels + rcu_first.hip; rcu_api.hip, choose_level_extents): the tensors of a level are allocated with
+    // Padded levels (`part` = 1; Winograd kernels + rcu_first.hip; rcu_plan.hip, plan_unet): the tensors of a level are allocated with
     // extents rounded up to whole tiles, H x W above are those ALLOCATED extents of the source level, and the pixels beyond the real image hold
     // zeros that no kernel ever writes -- so a tile that hangs over the real border reads exactly the zero padding the reference's conv applies
     // (common/model/unet.py:13: padding=1) and the load side of the kernels is the whole-tile one.  What changes is the store side:
@@ -245,6 +245,11 @@ constexpr int MC_VAR = 2;
 constexpr int MC_INPUT_PROBS = 4;   // accumulate: input already holds probabilities (ensemble seam)
 constexpr int MC_EXACT = 8;
 constexpr int MAX_CLASSES = 8;
+inline int check_classes(int c)
+{
+    if (c < 1 || c > MAX_CLASSES) return report_error(RCU_ERR_INVALID, "nb_classes must be in 1..8");
+    return RCU_OK;
+}
 
 struct HeadArgs {
     const float* act;     // [V][CP] NHWC activations of the (fused) head conv unit
@@ -287,26 +292,12 @@ struct VoteArgs {
     unsigned char bit[SAMPLE_MAX_PASSES];         // bit of pass t of the launch inside that word
 };
 hipError_t launch_head_votes(const HeadArgs& a, uint32_t* votes, int n_words, const int32_t* bits_host, hipStream_t stream);
-// the standalone form over a materialised [n][C][hw] volume of logits or (MC_INPUT_PROBS) probabilities
-hipError_t launch_mc_votes(const float* in_nchw, int C, size_t N, size_t HW, int flags, uint32_t* votes, int bit, hipStream_t stream);
-// standalone forms over materialised [n][C][hw] logits and raw sigma (rcu_logit_sampling.hip)
-hipError_t launch_logit_normals(unsigned long long key, unsigned long long first_sample, size_t n, size_t hw, int C, int samples, float* out,
-                                hipStream_t stream);
-hipError_t launch_logit_sampling(const float* logits, const float* sigma_raw, size_t n, size_t hw, int C, int is_log_sigma, int samples,
-                                 unsigned long long key, unsigned long long first_sample, float* probs, void* stats, int flags, hipStream_t stream);
 // RCU_ERR_INVALID (with its message) unless 1 <= nb_classes <= 8, 1 <= samples <= LOGIT_MAX_SAMPLES, n, hw >= 1 and hw < 2^32
-int check_logit_sampling_shape(const char* fn, size_t n, size_t hw, int nb_classes, int samples);
+int check_logit_sampling_shape(const char* fn, size_t n, size_t hw, int nb_classes, int samples);   // (rcu_logit_sampling.hip)
+// a vote plane of n_words words / a bit index inside it, or RCU_ERR_INVALID with its message (rcu_pointwise.hip)
+int check_vote_plane(const std::string& fn, int n_words);
+int check_vote_bit(const std::string& fn, int bit, int n_words);
 
-hipError_t launch_mc_accumulate(const float* in_nchw, void* stats, int C, size_t N, size_t HW, int flags,
-                                hipStream_t stream);
-hipError_t launch_mc_finalize(const void* stats, int C, size_t N, size_t HW, int T, int flags, float* mean,
-                              float* entropy, float* mi, float* var, hipStream_t stream);
-hipError_t launch_softmax_nchw(const float* logits, float* probs, int C, size_t N, size_t HW, hipStream_t stream);
-hipError_t launch_aleatoric(const float* logits, const float* sigma_raw, int C, size_t N, size_t HW, int is_log_sigma,
-                            float* probs, float* sigma_out, uint8_t* prediction, float* sigma_pred,
-                            hipStream_t stream);
-hipError_t launch_argmax_fg(const float* probs_nchw, int C, size_t N, size_t HW, uint8_t* prediction, float* p_fg,
-                            hipStream_t stream);
 // Dropout2d factors of the passes of a pass group, drawn in one launch (include/rcu.h: rcu_dropout_masks)
 constexpr int MASK_MAX_PASSES = 32;      // seeds per launch (kernel arguments)
 constexpr int MASK_MAX_SITES = 40;       // 2 * (2 * 8 + 1) + the head units: depth <= 8
@@ -322,21 +313,12 @@ struct MaskArgs {
     int per_sample;
     unsigned long long first_sample;     // global index of the batch's sample 0 (include/rcu.h, rcu_dropout_masks)
 };
-hipError_t launch_dropout_masks(const MaskArgs& a, float* out, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // adaptive MC (rcu_adaptive.hip; include/rcu.h "Adaptive MC")
 // ---------------------------------------------------------------------------------------------
-// float64 statistics only (MC_EXACT): unsettled[i] = #{v in slice i : (int64)(max_c S_c(v) * 2^40) < thr_q}, margin_q[i] = the smallest such integer
-hipError_t launch_mc_slice_scores(const void* stats, int C, size_t N, size_t HW, long long thr_q, uint32_t* unsettled, long long* margin_q,
-                                  hipStream_t stream);
 // launch_dropout_masks with row i drawn at the global sample sample_index[i] (device array of a.site_end[0] / a.site_ch[0] entries); a.first_sample unused
 hipError_t launch_dropout_masks_indexed(const MaskArgs& a, const long long* sample_index, float* out, hipStream_t stream);
-// every plane: dst[plane][index[i]] += src[plane][i], i < M; entries outside [0, N) are skipped; the others must be distinct
-hipError_t launch_mc_merge_slices(const void* src, size_t M, void* dst, size_t N, size_t HW, int C, int flags, const int32_t* index, hipStream_t stream);
-// launch_mc_finalize with T = counts[slice] (device array of N entries >= 1)
-hipError_t launch_mc_finalize_counts(const void* stats, int C, size_t N, size_t HW, const int32_t* counts, int flags, float* mean, float* entropy,
-                                     float* mi, float* var, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // calibration kernels (rcu_calib.hip)
@@ -348,28 +330,6 @@ struct EceResult {           // one per volume
     double sum_conf[MAX_BINS];
     unsigned long long sum_pos[MAX_BINS];
 };
-void calib_set_blocks_per_workgroup(int ece, int unc);   // 0 = the launchers' own rule
-size_t ece_workspace_bytes(size_t n_per_volume, int n_volumes);
-hipError_t launch_ece_hist(const float* p, const uint8_t* target, const uint8_t* mask, size_t n_per_volume,
-                           int n_volumes, const float* thr_host, int n_bins, EceResult* result_dev, void* workspace,
-                           hipStream_t stream);
-hipError_t launch_bin_ids(const float* p, size_t n, const float* thr_host, int n_bins, uint8_t* ids,
-                          hipStream_t stream);
-size_t unc_workspace_bytes(size_t n_per_volume, int n_volumes);
-// out_dev: [n_volumes][n_thr][8] u64 = tp, tn, fp, fn, tpu, tnu, fpu, fnu
-hipError_t launch_unc_counts(const void* unc, int unc_is_f64, const uint8_t* prediction, const uint8_t* target,
-                             const uint8_t* mask, size_t n_per_volume, int n_volumes, const double* thr_host,
-                             int n_thr, unsigned long long* out_dev, void* workspace, hipStream_t stream);
-hipError_t launch_norm_entropy(const float* p_fg, size_t n, double* out_f64, float* out_f32, hipStream_t stream);
-// the same counts straight from the float32 foreground-probability map, "uncertain" decided by the table of the reference's own sets
-int unc_from_p_num_thresholds();
-double unc_from_p_threshold(int i);
-bool unc_from_p_supported(const double* thr, int n_thr);
-int unc_from_p_exceeded_host(float p, const double* thr, int n_thr);
-size_t unc_from_p_workspace_bytes(size_t n_per_volume, int n_volumes);
-hipError_t launch_unc_counts_from_p(const float* p_fg, const uint8_t* prediction, const uint8_t* target, const uint8_t* mask, size_t n_per_volume,
-                                    int n_volumes, const double* thr_host, int n_thr, unsigned long long* out_dev, void* workspace,
-                                    hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // temperature scaling: NLL sweep over candidate inverse temperatures (rcu_temperature.hip; entry points rcu_temperature_nll*)
@@ -385,8 +345,5 @@ size_t temperature_nll_workspace_bytes(size_t voxels, int n_candidates);
 constexpr int pn_layer_floats(int cb) { return cb * cb * 1024 + 2 * cb * 32; }
 constexpr int PN_MAX_LAYERS = 12;
 constexpr int PN_MAX_BLOCKS = 3;   // up to 96 feature channels (the packed layers live in LDS: n_layers * pn_layer_floats <= 160 KB)
-// masks: null, or Dropout2d factors [n_layers - 1][images][channels] of an MC pass
-hipError_t launch_postnet(const float* x_nhwc, int channel_pitch, size_t nvox, int hw, const float* packed, int n_layers,
-                          int nb_classes, int channels, const float* masks, float* logits_nchw, hipStream_t stream);
 
 }  // namespace rcu

@@ -76,16 +76,16 @@ __global__ __launch_bounds__(LS_THREADS) void logit_sampling_kernel(const float*
 
 }  // namespace
 
-hipError_t launch_logit_normals(unsigned long long key, unsigned long long first_sample, size_t n, size_t hw, int C, int samples, float* out,
-                                hipStream_t stream)
+static hipError_t launch_logit_normals(unsigned long long key, unsigned long long first_sample, size_t n, size_t hw, int C, int samples, float* out,
+                                       hipStream_t stream)
 {
     const size_t V = n * hw;
     hipLaunchKernelGGL(logit_normals_kernel, dim3(ls_grid(V)), dim3(LS_THREADS), 0, stream, key, first_sample, hw, V, C, samples, out);
     return hipGetLastError();
 }
 
-hipError_t launch_logit_sampling(const float* logits, const float* sigma_raw, size_t n, size_t hw, int C, int is_log_sigma, int samples,
-                                 unsigned long long key, unsigned long long first_sample, float* probs, void* stats, int flags, hipStream_t stream)
+static hipError_t launch_logit_sampling(const float* logits, const float* sigma_raw, size_t n, size_t hw, int C, int is_log_sigma, int samples,
+                                        unsigned long long key, unsigned long long first_sample, float* probs, void* stats, int flags, hipStream_t stream)
 {
     const size_t V = n * hw;
     RCU_LS_DISPATCH_C(C, hipLaunchKernelGGL(logit_sampling_kernel<C_>, dim3(ls_grid(V)), dim3(LS_THREADS), 0, stream, logits, sigma_raw, hw, V,

@@ -13,6 +13,7 @@
 // statistics planes (sum p, optionally sum p^2 in double, optionally sum H).
 #include "rcu_head_common.h"
 
+#include <algorithm>
 #include <initializer_list>
 
 namespace rcu {
@@ -23,7 +24,7 @@ static inline unsigned grid_for(size_t n) { return (unsigned)((n + PW_THREADS - 
 
 // ------------------------------------------------------------------------------- NCHW -> padded NHWC
 // `replicas` > 1: the N input images are written `replicas` times one after the other (pass groups).
-// The output image is allocated PH x PW >= H x W (a padded level 0, rcu_api.hip): only the real pixels are written.
+// The output image is allocated PH x PW >= H x W (a padded level 0, rcu_plan.hip): only the real pixels are written.
 __global__ __launch_bounds__(PW_THREADS) void pack_input_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                  int C, int CP, size_t HW, size_t V, size_t N, int W, int PH, int PW)
 {
@@ -522,7 +523,7 @@ __global__ __launch_bounds__(PW_THREADS) void mc_votes_kernel(const float* __res
     plane[v] = word | (head_vote<C>(l) << bit);
 }
 
-hipError_t launch_mc_votes(const float* in, int C, size_t N, size_t HW, int flags, uint32_t* votes, int bit, hipStream_t stream)
+static hipError_t launch_mc_votes(const float* in, int C, size_t N, size_t HW, int flags, uint32_t* votes, int bit, hipStream_t stream)
 {
     const size_t V = N * HW;
     RCU_DISPATCH_C(C, hipLaunchKernelGGL(mc_votes_kernel<C_>, dim3(grid_for(V)), dim3(PW_THREADS), 0, stream, in, HW, V, flags,
@@ -594,7 +595,7 @@ __global__ __launch_bounds__(PW_THREADS) void mc_accumulate4_kernel(const float4
     }
 }
 
-hipError_t launch_mc_accumulate(const float* in, void* stats, int C, size_t N, size_t HW, int flags, hipStream_t stream)
+static hipError_t launch_mc_accumulate(const float* in, void* stats, int C, size_t N, size_t HW, int flags, hipStream_t stream)
 {
     const size_t V = N * HW;
     // (float64 statistics -- 80 bytes of read-modify-write per voxel -- run as fast or faster one voxel per thread: measured 0.84 / 0.73 of
@@ -711,8 +712,8 @@ __global__ __launch_bounds__(PW_THREADS) void mc_finalize4_kernel(const void* st
     if (var != nullptr && (flags & MC_VAR)) var[i] = float4{vr[0], vr[1], vr[2], vr[3]};
 }
 
-hipError_t launch_mc_finalize(const void* stats, int C, size_t N, size_t HW, int T, int flags, float* mean,
-                              float* entropy, float* mi, float* var, hipStream_t stream)
+static hipError_t launch_mc_finalize(const void* stats, int C, size_t N, size_t HW, int T, int flags, float* mean,
+                                     float* entropy, float* mi, float* var, hipStream_t stream)
 {
     const size_t V = N * HW;
     if (vec4_ok(HW, V, {stats, mean, entropy, mi, var})) {
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(PW_THREADS) void softmax_kernel(const float* __rest
     for (int c = 0; c < C; ++c) out[(n * C + c) * HW + hw] = l[c];
 }
 
-hipError_t launch_softmax_nchw(const float* logits, float* probs, int C, size_t N, size_t HW, hipStream_t stream)
+static hipError_t launch_softmax_nchw(const float* logits, float* probs, int C, size_t N, size_t HW, hipStream_t stream)
 {
     const size_t V = N * HW;
     RCU_DISPATCH_C(C, hipLaunchKernelGGL(softmax_kernel<C_>, dim3(grid_for(V)), dim3(PW_THREADS), 0, stream, logits,
@@ -785,8 +786,8 @@ __global__ __launch_bounds__(PW_THREADS) void aleatoric_kernel(const float* __re
     if (sigma_pred != nullptr) sigma_pred[v] = sp;
 }
 
-hipError_t launch_aleatoric(const float* logits, const float* sigma_raw, int C, size_t N, size_t HW, int is_log_sigma,
-                            float* probs, float* sigma_out, uint8_t* prediction, float* sigma_pred, hipStream_t stream)
+static hipError_t launch_aleatoric(const float* logits, const float* sigma_raw, int C, size_t N, size_t HW, int is_log_sigma,
+                                   float* probs, float* sigma_out, uint8_t* prediction, float* sigma_pred, hipStream_t stream)
 {
     const size_t V = N * HW;
     RCU_DISPATCH_C(C, hipLaunchKernelGGL(aleatoric_kernel<C_>, dim3(grid_for(V)), dim3(PW_THREADS), 0, stream, logits,
@@ -812,8 +813,8 @@ __global__ __launch_bounds__(PW_THREADS) void argmax_fg_kernel(const float* __re
     if (p_fg != nullptr) p_fg[v] = p[C > 1 ? 1 : 0];   // foreground class (brats_test_default.py:99)
 }
 
-hipError_t launch_argmax_fg(const float* probs, int C, size_t N, size_t HW, uint8_t* prediction, float* p_fg,
-                            hipStream_t stream)
+static hipError_t launch_argmax_fg(const float* probs, int C, size_t N, size_t HW, uint8_t* prediction, float* p_fg,
+                                   hipStream_t stream)
 {
     const size_t V = N * HW;
     RCU_DISPATCH_C(C, hipLaunchKernelGGL(argmax_fg_kernel<C_>, dim3(grid_for(V)), dim3(PW_THREADS), 0, stream, probs, HW,
@@ -849,10 +850,162 @@ __global__ __launch_bounds__(PW_THREADS) void dropout_masks_kernel(const MaskArg
     out[(size_t)a.passes * begin + (size_t)(a.first + t) * len + (r - begin)] = factor;
 }
 
-hipError_t launch_dropout_masks(const MaskArgs& a, float* out, hipStream_t stream)
+static hipError_t launch_dropout_masks(const MaskArgs& a, float* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(dropout_masks_kernel, dim3((a.per_pass + PW_THREADS - 1) / PW_THREADS, a.count), dim3(PW_THREADS), 0, stream, a, out);
     return hipGetLastError();
 }
 
+int check_vote_plane(const std::string& fn, int n_words)
+{
+    if (n_words < 1 || n_words > RCU_VOTES_MAX_PASSES / 32) return report_error(RCU_ERR_INVALID, fn + ": n_words must be in 1..2, got " + std::to_string(n_words));
+    return RCU_OK;
+}
+int check_vote_bit(const std::string& fn, int bit, int n_words)
+{
+    if (bit < 0 || bit >= 32 * n_words)
+        return report_error(RCU_ERR_INVALID, fn + ": bit " + std::to_string(bit) + " outside [0, " + std::to_string(32 * n_words) + ")");
+    return RCU_OK;
+}
+
 }  // namespace rcu
+
+// ------------------------------------------------------------------------------------------------
+// step seam (include/rcu.h).  A HIP error is reported under the text of the call that returned it.
+// ------------------------------------------------------------------------------------------------
+using namespace rcu;
+
+extern "C" size_t rcu_mc_stats_bytes(size_t n, size_t hw, int C, int flags)
+{
+    const size_t V = n * hw;
+    const size_t mi = (flags & RCU_MC_MI) ? 1 : 0;
+    if (flags & (RCU_MC_VAR | RCU_MC_EXACT)) return V * ((size_t)C + ((flags & RCU_MC_VAR) ? (size_t)C : 0) + mi) * sizeof(double);
+    return V * ((size_t)C + mi) * sizeof(float);
+}
+
+extern "C" int rcu_mc_begin(void* stats, size_t n, size_t hw, int C, int flags, void* stream)
+{
+    if (!stats) return report_error(RCU_ERR_INVALID, "rcu_mc_begin: null stats");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    const hipError_t e = hipMemsetAsync(stats, 0, rcu_mc_stats_bytes(n, hw, C, flags), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("hipMemsetAsync(stats, 0, rcu_mc_stats_bytes(n, hw, C, flags), static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_mc_accumulate(const float* in, void* stats, size_t n, size_t hw, int C, int flags, void* stream)
+{
+    if (!in || !stats) return report_error(RCU_ERR_INVALID, "rcu_mc_accumulate: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_mc_accumulate(in, stats, C, n, hw, flags, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_mc_accumulate(in, stats, C, n, hw, flags, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_mc_finalize(const void* stats, size_t n, size_t hw, int C, int T, int flags, float* mean, float* entropy,
+                               float* mi, float* var, void* stream)
+{
+    if (!stats) return report_error(RCU_ERR_INVALID, "rcu_mc_finalize: null stats");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (T < 1) return report_error(RCU_ERR_INVALID, "rcu_mc_finalize: T must be >= 1");
+    if (mi && !(flags & RCU_MC_MI)) return report_error(RCU_ERR_INVALID, "mutual_info requested without RCU_MC_MI statistics");
+    if (var && !(flags & RCU_MC_VAR)) return report_error(RCU_ERR_INVALID, "variance requested without RCU_MC_VAR statistics");
+    if ((flags & RCU_MC_EXACT) && T > RCU_MC_EXACT_MAX_PASSES)
+        return report_error(RCU_ERR_INVALID, "RCU_MC_EXACT statistics hold at most 2048 passes (sums of multiples of 2^-40 below 2^13)");
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_mc_finalize(stats, C, n, hw, T, flags, mean, entropy, mi, var, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_mc_finalize(stats, C, n, hw, T, flags, mean, entropy, mi, var, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_softmax(const float* logits, float* probs, size_t n, size_t hw, int C, void* stream)
+{
+    if (!logits || !probs) return report_error(RCU_ERR_INVALID, "rcu_softmax: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_softmax_nchw(logits, probs, C, n, hw, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_softmax_nchw(logits, probs, C, n, hw, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_aleatoric(const float* logits, const float* sigma_raw, size_t n, size_t hw, int C, int is_log_sigma,
+                             float* probs, float* sigma, uint8_t* prediction, float* sigma_pred, void* stream)
+{
+    if (!logits || !sigma_raw) return report_error(RCU_ERR_INVALID, "rcu_aleatoric: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_aleatoric(logits, sigma_raw, C, n, hw, is_log_sigma, probs, sigma, prediction, sigma_pred, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_aleatoric(logits, sigma_raw, C, n, hw, is_log_sigma, probs, sigma, prediction, sigma_pred, "
+                                        "static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_prediction_and_foreground(const float* probs, size_t n, size_t hw, int C, uint8_t* prediction,
+                                             float* p_fg, void* stream)
+{
+    if (!probs) return report_error(RCU_ERR_INVALID, "rcu_prediction_and_foreground: null argument");
+    if (check_classes(C)) return RCU_ERR_INVALID;
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_argmax_fg(probs, C, n, hw, prediction, p_fg, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK : hip_failed("launch_argmax_fg(probs, C, n, hw, prediction, p_fg, static_cast<hipStream_t>(stream))", e);
+}
+
+extern "C" int rcu_mc_votes(const float* in_dev, size_t n, size_t hw, int nb_classes, int flags, uint32_t* votes_dev, int n_words, int bit, void* stream)
+{
+    const std::string fn = "rcu_mc_votes";
+    if (!in_dev || !votes_dev) return report_error(RCU_ERR_INVALID, fn + ": null in_dev / votes_dev");
+    if (int st = check_vote_plane(fn, n_words)) return st;
+    if (int st = check_vote_bit(fn, bit, n_words)) return st;
+    if (nb_classes < 1 || nb_classes > MAX_CLASSES) return report_error(RCU_ERR_INVALID, fn + ": nb_classes must be in 1..8");
+    if (n * hw == 0) return RCU_OK;
+    const hipError_t e = launch_mc_votes(in_dev, nb_classes, n, hw, flags & RCU_MC_INPUT_PROBS, votes_dev, bit, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_mc_votes(in_dev, nb_classes, n, hw, flags & RCU_MC_INPUT_PROBS, votes_dev, bit, static_cast<hipStream_t>(stream))", e);
+}
+
+// The two mask draws: the site table is checked and laid out once; sample_index_dev == nullptr draws at first_sample + i
+static int draw_dropout_masks(const std::string& fn, const uint64_t* seeds, int passes, int n, uint64_t first_sample, const int64_t* sample_index_dev,
+                              const int32_t* site_channels, const float* site_keep, int n_sites, float* out, void* stream)
+{
+    if (!seeds || !site_channels || !site_keep || !out) return report_error(RCU_ERR_INVALID, fn + ": null argument");
+    if (passes < 1 || n < 1 || n_sites < 1 || n_sites > MASK_MAX_SITES) return report_error(RCU_ERR_INVALID, fn + ": passes, n >= 1 and 1 <= n_sites <= 40");
+    MaskArgs a{};
+    long end = 0;
+    for (int s = 0; s < n_sites; ++s) {
+        if (site_channels[s] < 1 || !(site_keep[s] <= 1.f)) return report_error(RCU_ERR_INVALID, fn + ": site_channels >= 1, site_keep <= 1");
+        end += (long)n * site_channels[s];
+        if (end * (long)passes >= (1l << 31)) return report_error(RCU_ERR_INVALID, fn + ": more than 2^31 factors");
+        a.site_end[s] = (int)end;
+        a.site_keep[s] = site_keep[s];
+        a.site_ch[s] = site_channels[s];
+        a.site_off[s] = a.per_sample;
+        a.per_sample += site_channels[s];
+    }
+    a.first_sample = first_sample;
+    a.sites = n_sites;
+    a.per_pass = (int)end;
+    a.passes = passes;
+    // MASK_MAX_PASSES seeds travel as kernel arguments: a longer group takes several launches, each writing its passes' rows of `out`
+    for (a.first = 0; a.first < passes; a.first += MASK_MAX_PASSES) {
+        a.count = std::min(MASK_MAX_PASSES, passes - a.first);
+        for (int t = 0; t < a.count; ++t) a.seed[t] = seeds[a.first + t];
+        if (sample_index_dev) {
+            const hipError_t e = launch_dropout_masks_indexed(a, reinterpret_cast<const long long*>(sample_index_dev), out, static_cast<hipStream_t>(stream));
+            if (e != hipSuccess)
+                return hip_failed("launch_dropout_masks_indexed(a, reinterpret_cast<const long long*>(sample_index_dev), out, static_cast<hipStream_t>(stream))", e);
+        } else {
+            const hipError_t e = launch_dropout_masks(a, out, static_cast<hipStream_t>(stream));
+            if (e != hipSuccess) return hip_failed("launch_dropout_masks(a, out, static_cast<hipStream_t>(stream))", e);
+        }
+    }
+    return RCU_OK;
+}
+
+extern "C" int rcu_dropout_masks(const uint64_t* seeds, int passes, int n, uint64_t first_sample, const int32_t* site_channels,
+                                 const float* site_keep, int n_sites, float* out, void* stream)
+{
+    return draw_dropout_masks("rcu_dropout_masks", seeds, passes, n, first_sample, nullptr, site_channels, site_keep, n_sites, out, stream);
+}
+
+extern "C" int rcu_dropout_masks_indexed(const uint64_t* seeds, int passes, int n, const int64_t* sample_index_dev, const int32_t* site_channels,
+                                         const float* site_keep, int n_sites, float* out, void* stream)
+{
+    if (!sample_index_dev) return report_error(RCU_ERR_INVALID, "rcu_dropout_masks_indexed: null argument");
+    return draw_dropout_masks("rcu_dropout_masks_indexed", seeds, passes, n, 0, sample_index_dev, site_channels, site_keep, n_sites, out, stream);
+}

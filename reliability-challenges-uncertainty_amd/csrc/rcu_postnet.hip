@@ -16,12 +16,17 @@
 // HBM: 128 CB bytes read + 4 nb_classes bytes written per voxel; MFMA: (nb_convs CB^2 + CB) * 16 steps per 32 voxels.
 #include "rcu_kernels.h"
 
+#include <cmath>
+#include <map>
+#include <string>
+#include <vector>
+
 namespace rcu {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// LDS image per layer (postnet_pack_layer, rcu_api.hip): CB x CB weight tiles [cob][cib][j = 0..3][lane][4]
+// LDS image per layer (postnet_pack_layer below): CB x CB weight tiles [cob][cib][j = 0..3][lane][4]
 // (float4 = W[32 cob + lane % 32][32 cib + 8 j + 4 (lane / 32) .. + 3]), then the start values of the accumulators
 // [cob][j][h][4] (bias[32 cob + 8 j + 4 h .. + 3]) and the constants added behind the dropout factor, same layout.
 template <int CB>
@@ -141,8 +146,9 @@ static hipError_t launch_postnet_cb(const float* x, int channel_pitch, size_t nv
     return hipGetLastError();
 }
 
-hipError_t launch_postnet(const float* x, int channel_pitch, size_t nvox, int hw, const float* packed, int n_layers,
-                          int nb_classes, int channels, const float* masks, float* logits, hipStream_t stream)
+// masks: null, or Dropout2d factors [n_layers - 1][images][channels] of an MC pass
+static hipError_t launch_postnet(const float* x, int channel_pitch, size_t nvox, int hw, const float* packed, int n_layers,
+                                 int nb_classes, int channels, const float* masks, float* logits, hipStream_t stream)
 {
     if (nvox == 0) return hipSuccess;
     const int cb = (channels + 31) / 32;
@@ -158,3 +164,152 @@ hipError_t launch_postnet(const float* x, int channel_pitch, size_t nvox, int hw
 }
 
 }  // namespace rcu
+
+// ------------------------------------------------------------------------------------------------
+// the PostNet handle (include/rcu.h).  A HIP error is reported under the text of the call that returned it.
+// ------------------------------------------------------------------------------------------------
+using namespace rcu;
+
+struct rcu_postnet {
+    int in_channels = 0, nb_classes = 0, nb_convs = 0, bn = 1;
+    std::map<std::string, std::vector<float>> host_weights;
+    float* packed = nullptr;      // eval image of the layers
+    float* packed_mc = nullptr;   // MC-dropout image (see rcu_postnet_finalize_weights)
+    bool finalized = false;
+};
+
+extern "C" int rcu_postnet_create(int in_channels, int nb_classes, int nb_convs, int bn, rcu_postnet** out)
+{
+    if (!out) return report_error(RCU_ERR_INVALID, "rcu_postnet_create: null argument");
+    if (in_channels < 1 || in_channels > 32 * PN_MAX_BLOCKS)
+        return report_error(RCU_ERR_INVALID, "PostNet kernel handles 1.." + std::to_string(32 * PN_MAX_BLOCKS) + " feature channels");
+    if (nb_classes < 1 || nb_classes > 32) return report_error(RCU_ERR_INVALID, "PostNet kernel handles 1..32 classes");
+    if (nb_convs < 0 || nb_convs + 1 > PN_MAX_LAYERS)
+        return report_error(RCU_ERR_INVALID, "PostNet kernel handles at most " + std::to_string(PN_MAX_LAYERS - 1) + " hidden convs");
+    const int cb = (in_channels + 31) / 32;
+    if ((size_t)(nb_convs + 1) * pn_layer_floats(cb) * sizeof(float) > 160 * 1024)
+        return report_error(RCU_ERR_INVALID, "PostNet: the packed layers of " + std::to_string(nb_convs) + " hidden convs over " +
+                                                 std::to_string(in_channels) + " channels do not fit the 160 KB of LDS");
+    rcu_postnet* h = new rcu_postnet;
+    h->in_channels = in_channels; h->nb_classes = nb_classes; h->nb_convs = nb_convs; h->bn = bn ? 1 : 0;
+    *out = h;
+    return RCU_OK;
+}
+
+extern "C" void rcu_postnet_destroy(rcu_postnet* h)
+{
+    if (!h) return;
+    if (h->packed) (void)hipFree(h->packed);
+    if (h->packed_mc) (void)hipFree(h->packed_mc);
+    delete h;
+}
+
+extern "C" int rcu_postnet_load_weight(rcu_postnet* h, const char* name, const float* data, size_t count)
+{
+    if (!h || !name || (!data && count)) return report_error(RCU_ERR_INVALID, "rcu_postnet_load_weight: null argument");
+    std::string key(name);
+    if (key.rfind("module.", 0) == 0) key = key.substr(7);
+    h->host_weights[key].assign(data, data + count);
+    h->finalized = false;
+    return RCU_OK;
+}
+
+static int postnet_weight(rcu_postnet* h, const std::string& key, size_t count, const std::vector<float>** out)
+{
+    auto it = h->host_weights.find(key);
+    if (it == h->host_weights.end()) return report_error(RCU_ERR_WEIGHTS, "missing weight tensor '" + key + "'");
+    if (it->second.size() != count)
+        return report_error(RCU_ERR_WEIGHTS, "weight tensor '" + key + "' has " + std::to_string(it->second.size()) +
+                                                 " elements, expected " + std::to_string(count));
+    *out = &it->second;
+    return RCU_OK;
+}
+
+// folded [32 cb][32 cb] (zero padded) layer -> the LDS image of postnet_kernel: weight tiles [cob][cib][j][lane][4], accumulator
+// start values [cob][j][h][4], constants behind the dropout factor [cob][j][h][4]
+static void postnet_pack_layer(int cb, const std::vector<float>& w, const std::vector<float>& start, const std::vector<float>& after,
+                               float* dst)
+{
+    const int cp = 32 * cb;
+    for (int cob = 0; cob < cb; ++cob)
+        for (int cib = 0; cib < cb; ++cib)
+            for (int j = 0; j < 4; ++j)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 4; ++e)
+                        dst[((((cob * cb + cib) * 4 + j) * 64) + lane) * 4 + e] =
+                            w[(size_t)(32 * cob + (lane & 31)) * cp + 32 * cib + 8 * j + 4 * (lane >> 5) + e];
+    float* bd = dst + cb * cb * 1024;
+    for (int which = 0; which < 2; ++which)
+        for (int cob = 0; cob < cb; ++cob)
+            for (int j = 0; j < 4; ++j)
+                for (int hf = 0; hf < 2; ++hf)
+                    for (int e = 0; e < 4; ++e)
+                        bd[which * cb * 32 + ((cob * 4 + j) * 2 + hf) * 4 + e] = (which ? after : start)[32 * cob + 8 * j + 4 * hf + e];
+}
+
+extern "C" int rcu_postnet_finalize_weights(rcu_postnet* h)
+{
+    if (!h) return report_error(RCU_ERR_INVALID, "rcu_postnet_finalize_weights: null handle");
+    const int C = h->in_channels, L = h->nb_convs + 1, cb = (C + 31) / 32, cp = 32 * cb;
+    const size_t layer = pn_layer_floats(cb);
+    // two images: eval (accumulators start from the whole folded bias) and MC (they start from alpha * conv bias; the dropout factor
+    // and BatchNorm's shift follow the MFMAs)
+    std::vector<float> packed((size_t)L * layer, 0.f), packed_mc((size_t)L * layer, 0.f);
+    for (int l = 0; l < L; ++l) {
+        const bool last = (l == h->nb_convs);
+        const std::string pre = last ? "conv_logits" : "convs." + std::to_string(l) + ".conv2d_batch_relu.conv";
+        const int cout = last ? h->nb_classes : C;
+        const std::vector<float>*w, *b;
+        int rc = postnet_weight(h, pre + ".weight", (size_t)cout * C, &w);
+        if (rc) return rc;
+        if ((rc = postnet_weight(h, pre + ".bias", cout, &b))) return rc;
+        std::vector<float> wf((size_t)cp * cp, 0.f), b_conv(cp, 0.f), b_shift(cp, 0.f), b_all(cp, 0.f);
+        for (int o = 0; o < cout; ++o) {
+            float alpha = 1.f, beta = 0.f, mean = 0.f;
+            if (!last && h->bn) {   // Conv -> [Dropout2d] -> BatchNorm(eval): y = gamma (m conv - mean) / sqrt(var + eps) + beta
+                const std::string bp = "convs." + std::to_string(l) + ".conv2d_batch_relu.bn";
+                const std::vector<float>*g, *be, *rm, *rv;
+                if ((rc = postnet_weight(h, bp + ".weight", C, &g))) return rc;
+                if ((rc = postnet_weight(h, bp + ".bias", C, &be))) return rc;
+                if ((rc = postnet_weight(h, bp + ".running_mean", C, &rm))) return rc;
+                if ((rc = postnet_weight(h, bp + ".running_var", C, &rv))) return rc;
+                alpha = (float)((double)(*g)[o] / std::sqrt((double)(*rv)[o] + 1e-5));
+                beta = (*be)[o];
+                mean = (*rm)[o];
+            }
+            for (int i = 0; i < C; ++i) wf[(size_t)o * cp + i] = alpha * (*w)[(size_t)o * C + i];
+            b_all[o] = alpha * ((*b)[o] - mean) + beta;
+            b_conv[o] = alpha * (*b)[o];
+            b_shift[o] = beta - alpha * mean;
+        }
+        postnet_pack_layer(cb, wf, b_all, std::vector<float>(cp, 0.f), packed.data() + (size_t)l * layer);
+        postnet_pack_layer(cb, wf, last ? b_all : b_conv, b_shift, packed_mc.data() + (size_t)l * layer);
+    }
+    hipError_t e = hipSuccess;
+    if (!h->packed && (e = hipMalloc(reinterpret_cast<void**>(&h->packed), packed.size() * sizeof(float))) != hipSuccess)
+        return hip_failed("hipMalloc(reinterpret_cast<void**>(&h->packed), packed.size() * sizeof(float))", e);
+    if (!h->packed_mc && (e = hipMalloc(reinterpret_cast<void**>(&h->packed_mc), packed_mc.size() * sizeof(float))) != hipSuccess)
+        return hip_failed("hipMalloc(reinterpret_cast<void**>(&h->packed_mc), packed_mc.size() * sizeof(float))", e);
+    if ((e = hipMemcpy(h->packed, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_failed("hipMemcpy(h->packed, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice)", e);
+    if ((e = hipMemcpy(h->packed_mc, packed_mc.data(), packed_mc.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_failed("hipMemcpy(h->packed_mc, packed_mc.data(), packed_mc.size() * sizeof(float), hipMemcpyHostToDevice)", e);
+    h->finalized = true;
+    return RCU_OK;
+}
+
+extern "C" int rcu_postnet_forward(rcu_postnet* h, const float* features_dev, int channel_pitch, int n, int hw,
+                                   const float* masks_dev, float* logits_dev, void* stream)
+{
+    if (!h || !features_dev || !logits_dev) return report_error(RCU_ERR_INVALID, "rcu_postnet_forward: null argument");
+    if (!h->finalized) return report_error(RCU_ERR_STATE, "rcu_postnet_forward before rcu_postnet_finalize_weights");
+    if (n < 0 || hw < 1) return report_error(RCU_ERR_INVALID, "rcu_postnet_forward: bad shape");
+    const int cb = (h->in_channels + 31) / 32;
+    if (channel_pitch < 32 * cb || channel_pitch % 4)
+        return report_error(RCU_ERR_INVALID, "rcu_postnet_forward: channel pitch must be >= in_channels rounded up to 32 and a multiple of 4");
+    const hipError_t e = launch_postnet(features_dev, channel_pitch, (size_t)n * hw, hw, masks_dev ? h->packed_mc : h->packed, h->nb_convs + 1,
+                                        h->nb_classes, h->in_channels, masks_dev, logits_dev, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? RCU_OK
+                           : hip_failed("launch_postnet(features_dev, channel_pitch, (size_t)n * hw, hw, masks_dev ? h->packed_mc : h->packed, h->nb_convs + 1, "
+                                        "h->nb_classes, h->in_channels, masks_dev, logits_dev, static_cast<hipStream_t>(stream))", e);
+}

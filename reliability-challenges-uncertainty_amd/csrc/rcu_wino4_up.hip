@@ -7,7 +7,7 @@
 //     row 0:  4a - 5b + c      row 1: -8b + 2c      row 2: 0      row 3: -3 (b - c)      row 4: b - c      row 5: 4b - 5c + d
 // (row 2 -- the point -1 -- vanishes identically: up2(z)(t) = z(t^2)(1 + t)).  5 x 5 = 25 positions remain; rows 3 and 4 carry the same data up
 // to the factor -3, which the host folds into the packed weights, so 4 x 4 = 16 transformed values per (tile, channel) -- made from the RAW 4x4
-// low-resolution patch -- feed the 25 positions.  Weights: G g G^T without row and column 2 (rcu_api.hip); output transform: A^T M A without
+// low-resolution patch -- feed the 25 positions.  Weights: G g G^T without row and column 2 (rcu_wpack.h); output transform: A^T M A without
 // column 2.  Zero padding of the up-sampled image is zero padding of the low-resolution image under this row map: the buffer resource's
 // out-of-range zeros do all of it.
 //

@@ -256,7 +256,7 @@ class UNet(nn.Module):
 
     def max_group_samples(self, h, w):
         """Largest batch of h x w images whose every activation tensor stays below the 2 GB that the Winograd kernels' 32-bit buffer offsets
-        reach (csrc/rcu_api.hip pick_config: beyond it a layer falls back to the direct kernels -- correct, but slower).  The widest
+        reach (csrc/rcu_plan.hip pick_config: beyond it a layer falls back to the direct kernels -- correct, but slower).  The widest
         full-resolution tensor has ``start_filters`` channels (twice that for the classifier + sigma twin unit)."""
         # (the planner pads every tensor's channels to a multiple of 32 -- pick_config's bound is on the PADDED tensor)
         widest = max(8, (self.start_filters + 31) // 32 * 32 * (2 if self.sigma_out else 1))

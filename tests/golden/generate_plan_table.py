@@ -2,7 +2,7 @@
 """G30: what the planner decides, case by case (no GPU: rcu_unet_plan + rcu_unet_layer_info through tests/plan_rows.py).
 
 Which kernel runs a layer, on which grid, in which layout family and what it reports as executed work follow from tables and rules in
-csrc/rcu_api.hip and the kernels' ConvConfigInfo rows; this fixture pins their outcome so that a change of how those facts are written down
+csrc/rcu_plan.hip and the kernels' ConvConfigInfo rows; this fixture pins their outcome so that a change of how those facts are written down
 can be told from a change of the facts.  Cases:
   explicit  the shipped shapes 192x128, 240x240, 192x256, 256x256 (depth 4, 32 start filters) x 4 and 3 input channels x max_batch 8, 160, 320,
             448, 480, 640 x {default options, every single non-default option value}

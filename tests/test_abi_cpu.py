@@ -242,7 +242,7 @@ def _plan_rows(h, w, n, cin=4, **options):
 
 
 def test_planner_pads_the_levels_of_the_references_real_shapes():
-    """csrc/rcu_api.hip choose_level_extents (round 6).  The reference's BraTS slices are 240 x 240 (scripts/create_brats18_dataset.py:53-72 never
+    """csrc/rcu_plan.hip plan_unet (round 6: choose_level_extents).  The reference's BraTS slices are 240 x 240 (scripts/create_brats18_dataset.py:53-72 never
     crops; levels 240 / 120 / 60 / 30 / 15), ISIC's 192 x 256 ends in a 12 x 16 level (scripts/prepare_isic_data.py:29-30): their levels are
     ALLOCATED with whole-tile extents and every layer runs a Winograd kernel (rounds 1-5: >= 16 of 23 layers of a 240 x 240 slice on the direct
     kernels).  Whole-tile shapes -- the benchmark's 192 x 128 and 256 x 256 -- keep their plans; pad_levels = 0, residual blocks' adding units

@@ -1,4 +1,4 @@
-"""Planner rows of the folded F(4x4,3x3) tile of the 12x8 level, which holds ten slices per work item (csrc/rcu_api.hip pick_config, csrc/rcu_wino4.hip):
+"""Planner rows of the folded F(4x4,3x3) tile of the 12x8 level, which holds ten slices per work item (csrc/rcu_plan.hip pick_config, csrc/rcu_wino4.hip):
 through rcu_unet_plan, no GPU."""
 import pytest
 

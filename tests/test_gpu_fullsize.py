@@ -5,7 +5,7 @@
   160-slice launch are compared bit for bit with an 8-slice launch of the same slices (slices are independent and every
   kernel sums in a fixed order) and with the oracle; the fused forward + softmax + accumulate path likewise with injected masks.
 * Native BraTS 240 x 240 slices (levels 240/120/60/30/15: no whole Winograd tile below the first level -> padded levels, round 6:
-  csrc/rcu_api.hip choose_level_extents), the reference's real ISIC size 192 x 256 (scripts/prepare_isic_data.py:29-30) and
+  csrc/rcu_plan.hip plan_unet), the reference's real ISIC size 192 x 256 (scripts/prepare_isic_data.py:29-30) and
   3 x 256 x 256, full width, against the oracle, asserting which kernel every layer got.
 """
 import numpy as np
@@ -97,7 +97,7 @@ def test_real_data_shapes_full_width_vs_oracle(dev, cin, n, h, w):
     m = _model(params, st, dev)
     rows = m.layer_table(h, w, n)
     assert len(rows) == 23                                       # 19 conv units (conv_cls.0 last) + 4 up-convolutions
-    # kernel selection (csrc/rcu_api.hip, pick_config): which family every layer got at this shape
+    # kernel selection (csrc/rcu_plan.hip, pick_config): which family every layer got at this shape
     kernels = [r['kernel'] for r in rows]
     # the first unit on its own kernel (whole 8x32 tiles), every other layer on a Winograd kernel -- at 240x240 (levels 240 / 120 / 60 / 30 / 15) and
     # at 192x256's 12x16 bottom level through levels ALLOCATED with whole-tile extents (rcu_unet_options.pad_levels; rounds 1-5: >= 16 of the 23
@@ -469,7 +469,7 @@ def test_native_brats_volume_mc20_on_padded_levels(dev):
     """The reference's REAL BraTS volume -- 155 slices of 4 x 240 x 240 (scripts/create_brats18_dataset.py:53-72 never crops;
     config/test_brats_baseline_mc.yaml:30-31 slices the volume) -- at the config's own T = 20, through ShardedMcRunner as
     `bench.py --workload brats-native` runs it: one pass of 155 slices per launch (every tensor below 2 GB), two stream lanes, seeded masks,
-    exact statistics; every layer on a Winograd kernel over padded levels (csrc/rcu_api.hip choose_level_extents; rounds 1-5: >= 16 of 23
+    exact statistics; every layer on a Winograd kernel over padded levels (csrc/rcu_plan.hip plan_unet; rounds 1-5: >= 16 of 23
     layers on the direct kernels).  Three slices against the oracle's 21 forwards under the runner's masks; two lanes == one lane and the
     same seed gives the same bits (exact sums); a slice does not depend on the batch it runs in."""
     from oracle import summary_oracle as so

@@ -1,4 +1,4 @@
-"""Padded levels (rcu_unet_options.pad_levels, csrc/rcu_api.hip choose_level_extents): shapes whose levels are not whole Winograd tiles --
+"""Padded levels (rcu_unet_options.pad_levels, csrc/rcu_plan.hip plan_unet): shapes whose levels are not whole Winograd tiles --
 the reference's real data: BraTS slices are 240 x 240 (scripts/create_brats18_dataset.py:53-72 never crops; levels 240 / 120 / 60 / 30 / 15),
 ISIC images 192 x 256 (scripts/prepare_isic_data.py:29-30; bottom level 12 x 16) -- run on the Winograd kernels over level tensors ALLOCATED
 with whole-tile extents whose padding holds zeros that no kernel writes.  Checked here: against the oracle, against the direct kernels on the
@@ -173,6 +173,48 @@ def test_padding_stays_zero_whatever_ran_before(dev):
     fresh = _model(WIDE, st, dev)
     fresh.reserve(h, w, 9)
     assert torch.equal(used(x.to(dev), masks), fresh(x.to(dev), masks))
+
+
+@pytest.mark.timeout(900)
+def test_workspace_borrower_on_a_padded_plan(dev):
+    """share_workspace (rcu_unet_create_with) on a plan whose levels are padded: the borrower, created for 2 images, is planned for its donor's 4
+    and runs in the donor's tensors -- same bits as a handle of its own for 4 --, the donor's padding survives the borrower's run, and a donor
+    of another shape is refused.  60 x 60 at depth 2 pads every level (60 -> 64, 30 -> 32, 15 -> 16)."""
+    import ctypes
+    import re
+    from oracle import unet_oracle as uo
+    from plan_rows import plan_rows
+    from rcu_amd import _lib
+    params = dict(WIDE, depth=2)
+    h, w = 60, 60
+    rows = plan_rows(h, w, 4, depth=2)
+    real = [(r['height'] // 2, r['width'] // 2) if r['upsample'] else (r['height'], r['width']) for r in rows]
+    assert any(r['grid'] != e for r, e in zip(rows, real)), 'the shape was meant to need padded levels'
+    st_d, st_b = uo.synthetic_state(50, **params), uo.synthetic_state(51, **params)
+    g = torch.Generator().manual_seed(83)
+    _, sites = uo.unet_plan(**params)
+    x2, x4 = torch.randn(2, 4, h, w, generator=g).to(dev), torch.randn(4, 4, h, w, generator=g).to(dev)
+    masks2, masks4 = uo.sample_masks(sites, 2, 0.3, g), uo.sample_masks(sites, 4, 0.3, g)
+    donor, borrower = _model(params, st_d, dev), _model(params, st_b, dev)
+    donor_twin, borrower_twin = _model(params, st_d, dev), _model(params, st_b, dev)
+    for m in (donor, donor_twin, borrower_twin):
+        m.reserve(h, w, 4)
+    borrower.share_workspace(donor)
+    out = borrower(x2, masks2)
+    assert borrower.workspace_bytes(h, w, 2) < borrower_twin.workspace_bytes(h, w, 4)   # packed weights only: the tensors are the donor's
+    assert torch.equal(out, borrower_twin(x2, masks2))
+    assert not torch.equal(out, donor_twin(x2, masks2))                                 # (the two sets of weights do differ)
+    assert torch.equal(donor(x4, masks4), donor_twin(x4, masks4))
+    lib = _lib.load()
+    desc = _lib.UnetDesc(nb_classes=2, in_channels=4, depth=2, start_filters=32, has_dropout=1, dropout_center=-1, sigma_out=0, bn=1, height=64, width=64,
+                         max_batch=2, residual=0, provide_features=0)
+    opts = _lib.UnetOptions()
+    lib.rcu_unet_default_options(ctypes.byref(opts))
+    handle = ctypes.c_void_p()
+    message = "rcu_unet_create_with: the workspace donor's plan differs (shape, options) or is sized for a smaller batch"
+    with pytest.raises(_lib.RcuError, match=re.escape(message)):
+        _lib.check(lib.rcu_unet_create_with(ctypes.byref(desc), ctypes.byref(opts), donor._handle(h, w, 4), ctypes.byref(handle)))
+    assert not handle.value
 
 
 @pytest.mark.timeout(900)

@@ -80,7 +80,7 @@ def test_25_products_match_upsample_then_conv(cin, cout):
 
 OLD = ['upconv_winograd<S8T4x8,N64,K8>', 'upconv_winograd<S2T8x16,N64,K8>', 'upconv_winograd<T16x16,N64,K8>', 'upconv_winograd<T16x32,N32,K8>']
 NEW = ['upconv_winograd4<S8T8x16,N32,K8>', 'upconv_winograd4<S2T16x32,N32,K8>', 'upconv_winograd4<T32x32,N32,K8>', 'upconv_winograd4<T32x32,N32,K8>']
-# what the default rule (csrc/rcu_api.hip, upconv4_wins) takes per plan size of the 192x128 BraTS shape: the per-layer gate admitted every size
+# what the default rule (csrc/rcu_plan.hip, upconv4_wins) takes per plan size of the 192x128 BraTS shape: the per-layer gate admitted every size
 # it measured, 160 to 640 samples (profiles/upconv4_layer_gate.txt); the rule keeps to the plans of the pass-group launches, 480 samples and
 # up, because a 160-sample plan must give the bits of an 8-sample one (tests/test_gpu_fullsize.py)
 DEFAULT_PLANS = {8: OLD, 160: OLD, 320: OLD, 479: OLD, 480: NEW, 640: NEW}
