@@ -202,6 +202,14 @@ int rcu_unet_profile_collect(rcu_unet* h, double* ms_sum, int* forwards);
  * of `channel_pitch` floats per voxel; valid until the next forward call on this handle. */
 int rcu_unet_features(const rcu_unet* h, const float** features_dev, int* channels, int* channel_pitch);
 
+/* Input of the 1x1 classifier conv_cls.1 in the last forward call = the output of conv_cls.0 after BN and ReLU (UNet.head_features when
+ * provide_head_features is set; "Last-layer Laplace" below): a compact channels-last [n * H * W][channel_pitch] float32 tensor in the handle's
+ * workspace, `channels` = start_filters real channels.  Valid after a forward that did not fuse the head (rcu_unet_set_fuse_head(h, 0), or any
+ * forward that takes the separate head kernel), until the next forward on this handle or on one that shares its workspace.  RCU_ERR_STATE
+ * otherwise -- before the first forward, after a forward that fused the head -- and for a sigma_out handle (its head tensor interleaves the sigma
+ * twin's channels). */
+int rcu_unet_head_features(const rcu_unet* h, const float** features_dev, int* channels, int* channel_pitch);
+
 /* ------------------------------------------------------------------------------------------
  * PostNet -- auxiliary confidence network on the U-Net features
  *   (common/model/postnet.py:6-18; bin-dl/brats_test_auxiliary_feat.py:74-77, isic_test_auxiliary_feat.py)
@@ -860,6 +868,53 @@ int rcu_density_moments(const float* features_dev, int channel_pitch, int F, con
 int rcu_density_energy(const float* features_dev, int channel_pitch, int F, size_t n_voxels, int K, const float* A_dev /* [K][F][F] */,
                        const float* b_dev /* [K][F] */, const float* k_dev /* [K] */, float* energy_dev /* [n_voxels] */,
                        float* d2_dev /* [n_voxels][K] or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Last-layer Laplace (EXTENSION: the reference has no post-hoc Bayesian estimate; rcu_amd.laplace, rcu_amd.steps.LaplacePredictStep -- Daxberger et
+ * al. 2021, Laplace Redux; MacKay 1992 for the probit predictive; tests/laplace_reference.py restates this section in float64)
+ *   Symbols.  F = start_filters, D = F + 1.  C = nb_classes, 2 <= C <= RCU_LAPLACE_MAX_CLASSES.  P = C (C + 1) / 2 pairs q = (c, c'), c <= c', in
+ *   row-major order (0,0), (0,1), ..., (1,1), ....  psi(v) in R^F is the output of conv_cls.0 (after BN and ReLU) in an eval-mode forward:
+ *   rcu_unet_head_features, F real channels at channel_pitch floats per voxel (channels F .. pitch - 1 are ignored: they may hold any finite value).
+ *   z(v) = W psi + w0 are the logits the model writes, p(v) its float32 softmax as the default step writes it.  theta* = (W, w0) / temperature, as
+ *   the model applies them, ordered class-major: F weights, then the bias.
+ *   Curvature weights (float32, no contraction).  omega_cc = p_c * (1 - p_c): one float32 subtraction, then one float32 multiplication;
+ *   omega_cc' = -(p_c * p_c'): one multiplication.  numpy in float32 reproduces every omega bit for bit.
+ *   Moments, per slice s and pair q:  w[s][q] = sum_v omega_q,  S[s][q][:] = sum_v omega_q psi,  G[s][q][:][:] = sum_v omega_q psi psi^T (both
+ *   triangles, bitwise symmetric), float64 all.  Accumulated as rcu_density_moments accumulates: a wave owns one chunk of RCU_DENSITY_CHUNK = m
+ *   consecutive voxels of the slice, by voxel index within the slice, and accumulates in float32 -- G_ij, i <= j, by the fp32 MFMA's k-ordered fmaf
+ *   chain of psi_i * fl(omega_q psi_j) over the chunk's voxels (the B operand omega_q psi_j is rounded once; the entry is mirrored to (j, i)); S_i
+ *   adds fl(omega_q psi_i) and w adds omega_q, the voxels of even and of odd index summed separately -- the chunk sums are promoted and added in
+ *   float64 in chunk order (even before odd), no atomics.  The rows of slice s are bit for bit a function of that slice's psi, p, hw, F and C alone:
+ *   not of n, the slice's position in the batch, the alignment of the pointers, the launch geometry or the stream.  Up to four pairs take one pass
+ *   over the features (two above 32 channels): C = 2 is one pass up to 32 channels, two above.
+ *   Error of the moments against float64 sums of the same float32 omega:  |G_ij - exact| <= (m + 2) 2^-24 sum_v |omega_q psi_i psi_j| (density's
+ *   bound plus the one rounding of the B operand), S the same with |omega_q psi_i|, w with |omega_q|.
+ *   Fit (host, float64; rcu_amd.laplace.fit_from_moments).  Every entry is summed over the slices with an exactly rounded sum (math.fsum): the
+ *   same slices in any batches or order give the same bits.  Per pair M_q = [[G_q, S_q], [S_q^T, w_q]] is D x D; H[(c,i),(c',j)] = M_(c,c')[i][j],
+ *   mirrored for c' < c; H_eff = hessian_scale * H (default 1.0, > 0); Sigma = (H_eff + tau I)^-1 by Cholesky.  tau is prior_precision: a float
+ *   > 0, default 1.0, or the string `evidence`: the first maximiser over tau_k = 2^(k/4), k = -80 .. 80, of -(tau/2) |theta*|^2 + (C D / 2) log
+ *   tau - (1/2) sum_i log(max(lambda_i, 0) + tau) with lambda_i the eigenvalues of H_eff (the log-likelihood at theta* does not depend on tau and
+ *   is left out).  Per class c: L = chol(Sigma_cc), lower, Sigma_cc the D x D diagonal block; A_c = (L^T)[:F, :F], b_c = -(L^T)[:F, F], kappa_c =
+ *   L[F][F]^2, so that s2_c(v) = psi~^T Sigma_cc psi~ = |A_c psi - b_c|^2 + kappa_c with psi~ = (psi, 1): density's form plus a constant.
+ *   Voxels are not independent observations: hessian_scale is the user's knob for that.
+ *   Predictive (device, float32, from A, b, kappa rounded once to float32).  s2_c as rcu_density_energy computes d2_c (the fma chain from -b_i in
+ *   the MFMA's order, then the squares added in float32), then + kappa_c.  t_c = fmaf((float)(pi / 8), s2_c, 1.0f), zt_c = z_c / sqrt(t_c) (both
+ *   correctly rounded), p~ = the project's softmax of zt, std_c = sqrt(s2_c): the mean-field probit link of the `laplace` package, the diagonal of
+ *   the logit covariance.  prediction is the first maximum of p~, std_pred the std of that class.  A voxel's outputs are a function of its F
+ *   feature values, its C logits and the parameters alone, whatever n, hw, its position or the presence of the optional outputs.  Error of s2_c
+ *   against float64 on the same float32 parameters: (3 F + 8) 2^-24 sum_i s_i^2 with s_i = sum_j |A_ij psi_j| + |b_i|, plus 2^-23 kappa_c.
+ *   Every argument is checked before the device is touched (RCU_ERR_INVALID, rcu_last_error() names it): F in 1..64, channel_pitch >= F and a
+ *   multiple of 4, C in 2..4, features_dev (and the moments' workspace_dev) 16-byte aligned, n in 1..2^20, hw in 1..2^30.
+ * ------------------------------------------------------------------------------------------ */
+#define RCU_LAPLACE_MAX_CLASSES 4
+size_t rcu_laplace_moments_workspace_bytes(size_t n, size_t hw, int F, int nb_classes);
+int rcu_laplace_moments(const float* features_dev, int channel_pitch, int F, const float* probabilities_dev /* NCHW [n][C][hw] */, size_t n,
+                        size_t hw, int nb_classes, double* w_out_dev /* [n][P] */, double* S_out_dev /* [n][P][F] */,
+                        double* G_out_dev /* [n][P][F][F] */, void* workspace_dev, void* stream);
+int rcu_laplace_predict(const float* features_dev, int channel_pitch, int F, const float* logits_dev /* NCHW [n][C][hw] */, size_t n, size_t hw,
+                        int nb_classes, const float* A_dev /* [C][F][F] */, const float* b_dev /* [C][F] */, const float* kappa_dev /* [C] */,
+                        float* probabilities_dev /* [n][C][hw] */, float* std_dev /* [n][C][hw] or NULL */, float* std_pred_dev /* [n][hw] or NULL */,
+                        uint8_t* prediction_dev /* [n][hw] or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Quantile rescale (EXTENSION: the reference brings an unbounded uncertainty map -- the aleatoric sigma, the density energy -- into [0, 1] with the

@@ -12,6 +12,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # RCU_HIP_LIBRARY: another build of the same library (csrc/Makefile: BUILD= / OUT=) for the timing tools under tools/
 LIB_PATH = os.environ.get('RCU_HIP_LIBRARY') or os.path.join(PKG_DIR, 'librcu_hip.so')
 
+# status codes (include/rcu.h)
+RCU_OK, RCU_ERR_INVALID, RCU_ERR_HIP, RCU_ERR_WEIGHTS, RCU_ERR_STATE = 0, -1, -2, -3, -4
 RCU_MC_MI = 1
 RCU_MC_VAR = 2
 RCU_MC_INPUT_PROBS = 4
@@ -193,6 +195,11 @@ SIGNATURES = {
     'rcu_key_hist': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rcu_quantile_apply_workspace_bytes': (c_size_t, [c_int]),
     'rcu_quantile_apply': (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_unet_head_features': (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int), POINTER(c_int)]),
+    'rcu_laplace_moments_workspace_bytes': (c_size_t, [c_size_t, c_size_t, c_int, c_int]),
+    'rcu_laplace_moments': (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rcu_laplace_predict': (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -68,6 +68,7 @@ struct rcu_unet {
     double temperature = 1.0;  // rcu_unet_set_temperature: conv_cls.1 is packed divided by it
     bool finalized = false;
     bool plan_only = false;   // rcu_unet_plan: no workspace -- the handle can be inspected, never run
+    bool head_input_kept = false;   // the last forward took the separate head kernel: act[plan.t_head] is conv_cls.0's output (rcu_unet_head_features)
     int64_t workspace_bytes = 0;
     std::vector<void*> allocs;
     // optional per-layer timing with HIP events on the caller's stream (rcu_unet_profile_*)
@@ -484,6 +485,7 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     const int n_one = n;
     n *= passes;
     if ((sigma || sigma_sum) && !h->d.sigma_out) return fail(RCU_ERR_INVALID, "sigma output requested from a model without sigma_out");
+    h->head_input_kept = false;
     const Plan& p = h->plan;
     const std::vector<float*>& act = h->ws->dev;
     hipEvent_t* ev = nullptr;
@@ -534,6 +536,7 @@ static int forward_impl(rcu_unet* h, const float* x, int n, const float* masks, 
     } else {
         RCU_HIP(launch_head(a, stream));
     }
+    h->head_input_kept = true;
     if (ev) RCU_HIP(hipEventRecord(*ev++, stream));
     return RCU_OK;
 }
@@ -639,6 +642,22 @@ extern "C" int rcu_unet_features(const rcu_unet* h, const float** features_dev, 
             return RCU_OK;
         }
     return fail(RCU_ERR_STATE, "rcu_unet_features: no conv_cls layer in the plan");
+}
+
+extern "C" int rcu_unet_head_features(const rcu_unet* h, const float** features_dev, int* channels, int* channel_pitch)
+{
+    if (!h || !features_dev) return fail(RCU_ERR_INVALID, "rcu_unet_head_features: null argument");
+    if (!h->finalized) return fail(RCU_ERR_STATE, "rcu_unet_head_features before rcu_unet_finalize_weights");
+    if (h->d.sigma_out)
+        return fail(RCU_ERR_STATE, "rcu_unet_head_features: a sigma_out handle's head tensor interleaves the sigma twin's channels");
+    if (h->plan.t_head < 0) return fail(RCU_ERR_STATE, "rcu_unet_head_features: no conv_cls layer in the plan");
+    if (!h->head_input_kept)
+        return fail(RCU_ERR_STATE, "rcu_unet_head_features: the last forward on this handle fused the classifier into conv_cls.0 (or there was "
+                                   "none): run it with rcu_unet_set_fuse_head(h, 0)");
+    *features_dev = h->ws->dev[h->plan.t_head];
+    if (channels) *channels = h->d.start_filters;
+    if (channel_pitch) *channel_pitch = h->plan.head_cp;
+    return RCU_OK;
 }
 
 extern "C" int rcu_unet_forward_accumulate_passes(rcu_unet* h, const float* x_dev, int n, int passes, const float* masks_dev,

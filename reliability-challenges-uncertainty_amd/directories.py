@@ -24,6 +24,10 @@ _SETTING_OF_RUN = {'baseline': 'BASELINE', 'baseline_mc': 'BASELINE_MC', 'center
 # rcu_amd extension: run types the reference does not have.  They are evaluated when named (--ids density), never by default (RUN_IDS)
 EXTENSION_RUN_IDS = ('density',)
 _SETTING_OF_RUN['density'] = 'DENSITY'
+# ... and the two views of a default run under others.laplace (rcu_amd.laplace): `laplace`, a probabilities run on the predictive, and `laplace_std`,
+# its {subject}_laplace_std.nii.gz, unbounded like sigma.  Evaluated when named (--ids laplace laplace_std)
+LAPLACE_RUN_IDS = ('laplace', 'laplace_std')
+_SETTING_OF_RUN.update(laplace='LAPLACE', laplace_std='LAPLACE_STD')
 for _ds in ('ISIC', 'BRATS'):
     for _run, _key in _SETTING_OF_RUN.items():
         # e.g. BRATS_BASELINE_MC_PREDICT = '<timestamp>_brats_baseline_mc'; unset: the run id itself (out/predictions/brats/baseline_mc)
@@ -70,6 +74,8 @@ MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
 
 def prediction_dir(dataset, run_id):
     """Prediction directory of a run, as rechun/eval/evaldata.py:21-46 composes it: <DS>_PREDICT_DIR / <DS>_<RUN>_PREDICT."""
+    if run_id not in RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS:
+        raise ValueError('unknown run id {!r}: the run types are {}'.format(run_id, ', '.join(RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS)))
     ds = dataset.upper()
     return os.path.join(globals()['{}_PREDICT_DIR'.format(ds)], globals()['{}_{}_PREDICT'.format(ds, _SETTING_OF_RUN[run_id])])
 

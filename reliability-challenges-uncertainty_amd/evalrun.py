@@ -76,6 +76,10 @@ CONFIDENCE_ENTRY = {'baseline': 'probabilities', 'baseline_mc': 'probabilities',
 # rcu_amd extension: a default run under others.density -- its {subject}_density.nii.gz (the feature-space energy, rcu_amd.density) is unbounded
 # like sigma and takes sigma's path through every action: the rescale_sigma rescale (global min-max through the minmax action), then an uncertainty
 CONFIDENCE_ENTRY['density'] = 'density'
+# rcu_amd extension: a default run under others.laplace, seen twice -- `laplace` reads its probabilities (the Laplace predictive: ece_dice, calib
+# and calib_curves speak about it), `laplace_std` its {subject}_laplace_std.nii.gz (the std of the predicted class's logit), which takes sigma's path
+CONFIDENCE_ENTRY['laplace'] = 'probabilities'
+CONFIDENCE_ENTRY['laplace_std'] = 'laplace_std'
 
 
 # ------------------------------------------------------------------------------------- CSV hooks
@@ -442,7 +446,7 @@ class SaveQuantilesAction(EvalAction):
     runs_first = True
     whole_run = True
     checks_range = False
-    ENTRIES = ('sigma', 'density')
+    ENTRIES = ('sigma', 'density', 'laplace_std')
 
     def __init__(self, quantile_dir, quantiles, need_mask):
         super().__init__()

@@ -77,6 +77,12 @@ class UNet(nn.Module):
         # dropped); rcu_amd.model.PostNet consumes it in place
         self.provide_features = provide_features
         self.features = None
+        # EXTENSION (rcu_amd.laplace): when set, ``head_features`` is the input of the 1x1 classifier conv_cls.1 -- conv_cls.0's output after
+        # BN and ReLU -- after every ``forward``: a [N, F, H, W] view of the handle's workspace like ``features``, valid until the next forward.
+        # That forward takes the standalone head kernel; the logits keep the bits of the default forward (fused == unfused).  A plain
+        # attribute, no constructor argument: it changes neither the plan nor the architecture.
+        self.provide_head_features = False
+        self.head_features = None
         self._site_modules = []
         self._sites = None
 
@@ -190,7 +196,7 @@ class UNet(nn.Module):
         for entry in self._handles.values():
             lib.rcu_unet_destroy(entry[0])
         self._handles = {}
-        self.features = None     # a view into a destroyed handle's workspace
+        self.features = self.head_features = None     # views into a destroyed handle's workspace
 
     def __del__(self):
         try:
@@ -224,7 +230,7 @@ class UNet(nn.Module):
         if entry is not None:
             lib.rcu_unet_destroy(entry[0])
             del self._handles[slot]
-            self.features = None     # ``features`` may be a view into that handle's workspace: valid until the next forward only
+            self.features = self.head_features = None     # they may be views into that handle's workspace: valid until the next forward only
         desc = _lib.UnetDesc(nb_classes=self.nb_classes, in_channels=self.in_channels, depth=self.depth,
                              start_filters=self.start_filters, has_dropout=int(self.dropout is not None),
                              dropout_center=-1 if self.dropout_center is None else int(self.dropout_center),
@@ -251,7 +257,7 @@ class UNet(nn.Module):
         while len(self._handles) > self.MAX_HANDLES:    # images of many different sizes: drop the least recently used plan
             old = next(iter(self._handles))
             lib.rcu_unet_destroy(self._handles.pop(old)[0])
-            self.features = None
+            self.features = self.head_features = None
         return handle
 
     def max_group_samples(self, h, w):
@@ -364,23 +370,33 @@ class UNet(nn.Module):
         x = self._check_input(x)
         n, _, h, w = x.shape
         handle = self._handle(h, w, n)
+        self.head_features = None      # a view of the last ``forward``: any forward on the handle ends it
         if masks is None and self.mc_active():
             masks = self.sample_masks(n, x.device)
         elif isinstance(masks, (list, tuple)):
             masks = self.pack_masks(masks, n, x.device)
         logits = torch.empty((n, self.nb_classes, h, w), device=x.device, dtype=torch.float32)
         sigma = torch.empty_like(logits) if self.sigma_out else None
-        _lib.check(_lib.load().rcu_unet_forward(handle, _lib.ptr(x), n, _lib.ptr(masks), _lib.ptr(logits),
-                                                _lib.ptr(sigma), _lib.current_stream()))
+        lib = _lib.load()
+        if self.provide_head_features:
+            if self.sigma_out:
+                raise ValueError('provide_head_features is not defined for a sigma_out model (its head tensor interleaves the sigma twin)')
+            _lib.check(lib.rcu_unet_set_fuse_head(handle, 0))
+        status = lib.rcu_unet_forward(handle, _lib.ptr(x), n, _lib.ptr(masks), _lib.ptr(logits), _lib.ptr(sigma), _lib.current_stream())
+        if self.provide_head_features:      # the switch goes back whatever the forward returned; the forward's own error is the one reported
+            lib.rcu_unet_set_fuse_head(handle, int(self.fuse_head))
+        _lib.check(status)
         if self.provide_features:
             self.features = self._features_view(handle, n, h, w, x.device)
+        if self.provide_head_features:
+            self.head_features = self._features_view(handle, n, h, w, x.device, lib.rcu_unet_head_features)
         if self.sigma_out:
             return logits, sigma
         return logits
 
-    def _features_view(self, handle, n, h, w, device):
+    def _features_view(self, handle, n, h, w, device, accessor=None):
         ptr, ch, pitch = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(_lib.load().rcu_unet_features(handle, ctypes.byref(ptr), ctypes.byref(ch), ctypes.byref(pitch)))
+        _lib.check((accessor or _lib.load().rcu_unet_features)(handle, ctypes.byref(ptr), ctypes.byref(ch), ctypes.byref(pitch)))
         nhwc = _lib.device_view(ptr.value, (n, h, w, pitch.value), device, owner=self)
         return nhwc[..., :ch.value].permute(0, 3, 1, 2)
 
@@ -406,6 +422,7 @@ class UNet(nn.Module):
             if any(not 0 <= b < 32 * votes.n_words for b in bits):
                 raise ValueError('vote bits must be in [0, {})'.format(32 * votes.n_words))
         handle = self._handle(h, w, n * passes, lane)
+        self.head_features = None      # a view of the last ``forward``: any forward on the handle ends it
         if masks is None:
             if passes > 1 and not self.mc_active():
                 raise ValueError('a pass group needs stochastic passes: set_dropout_mode(model, True) or inject masks')
@@ -440,6 +457,7 @@ class UNet(nn.Module):
         if passes < 1:
             raise ValueError('passes must be >= 1')
         handle = self._handle(h, w, n * passes, lane)
+        self.head_features = None      # a view of the last ``forward``: any forward on the handle ends it
         if passes > 1:      # pass group (see forward_accumulate): ``masks`` = a list of ``passes`` mask sets or a concatenated tensor
             if masks is None:
                 if not self.mc_active():
@@ -478,6 +496,7 @@ class UNet(nn.Module):
                 not sigma_sum.is_contiguous() or sigma_sum.device != x.device):
             raise ValueError('sigma_sum must be a contiguous float32 [N, C, H, W] tensor on the input device')
         handle = self._handle(h, w, n * passes, lane)
+        self.head_features = None      # a view of the last ``forward``: any forward on the handle ends it
         if masks is None:
             if passes > 1 and not self.mc_active():
                 raise ValueError('a pass group needs stochastic passes: set_dropout_mode(model, True) or inject masks')

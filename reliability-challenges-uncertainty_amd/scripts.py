@@ -10,6 +10,7 @@ Each function is the ``main`` of the same-named reference script (flags unchange
     bin-eval/eval_uncertainty.py   --ds --ids --act               (bin-eval/eval_uncertainty.py:13-50, 248-288)
     bin-dl/{brats,isic}_fit_temperature.py -config_file           (EXTENSION: temperature scaling, fit_temperature)
     bin-dl/{brats,isic}_fit_density.py -config_file               (EXTENSION: feature-space density, fit_density)
+    bin-dl/{brats,isic}_fit_laplace.py -config_file               (EXTENSION: last-layer Laplace, fit_laplace)
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
 """
@@ -30,6 +31,7 @@ from . import density as density_mod
 from . import distributed as rdist
 from . import evalrun
 from . import evaluation as ev
+from . import laplace as laplace_mod
 from . import loops
 from . import management as mgt
 from . import nifti
@@ -353,20 +355,23 @@ def _other(context, key, default=None):
 _TEST_SCRIPTS = frozenset(('default', 'ensemble', 'aleatoric', 'auxiliary_feat', 'auxiliary_segm'))
 _DEFAULT = frozenset(('default',))
 _ONE_PASS_FIT = 'others.{}: the density fit is one eval-mode pass per batch and does not take it'
+_ONE_PASS_LAPLACE = 'others.{}: the Laplace fit is one eval-mode pass per batch and does not take it'
 _OtherKey = collections.namedtuple('_OtherKey', 'name description home scripts tail overrides', defaults=('', {}))
 # The extension keys of ``others`` that not every script takes, in the order they are checked: name, the description and the home its refusal
 # names, the scripts that take it, a tail to the refusal, the scripts that refuse it in words of their own.  A new key is a row here and its builder.
 _OTHERS = (
     _OtherKey('tta', 'test-time augmentation', 'the default test scripts only', _DEFAULT,
               overrides={'fit_temperature': 'others.tta: the temperature fit does not run under test-time augmentation',
-                         'fit_density': _ONE_PASS_FIT.format('tta')}),
-    _OtherKey('mc', None, None, _TEST_SCRIPTS | {'fit_temperature'}, overrides={'fit_density': _ONE_PASS_FIT.format('mc')}),
-    _OtherKey('temperature', 'temperature scaling', 'the default test scripts only', _DEFAULT),
+                         'fit_density': _ONE_PASS_FIT.format('tta'), 'fit_laplace': _ONE_PASS_LAPLACE.format('tta')}),
+    _OtherKey('mc', None, None, _TEST_SCRIPTS | {'fit_temperature'},
+              overrides={'fit_density': _ONE_PASS_FIT.format('mc'), 'fit_laplace': _ONE_PASS_LAPLACE.format('mc')}),
+    _OtherKey('temperature', 'temperature scaling', 'the default test scripts only', _DEFAULT | {'fit_laplace'}),
     _OtherKey('agreement', 'MC sample agreement', 'the default test scripts with others.mc only', _DEFAULT),
     _OtherKey('mc_adaptive', 'adaptive MC dropout', 'the default test scripts with others.mc only', _DEFAULT),
     _OtherKey('logit_samples', 'test-time logit sampling', 'the aleatoric test scripts only', frozenset(('aleatoric',))),
     _OtherKey('corruption', 'input corruptions', 'the test scripts only', _TEST_SCRIPTS, tail=': calibration is fitted on clean validation data'),
     _OtherKey('density', 'feature-space density uncertainty', 'the default test scripts only', _DEFAULT),
+    _OtherKey('laplace', 'last-layer Laplace uncertainty', 'the default test scripts only', _DEFAULT),
 )
 
 
@@ -392,6 +397,9 @@ _RULES = tuple(('density', key, 'others.density does not compose with others.{}:
     ('agreement', 'tta', 'others.agreement does not compose with others.tta (test-time augmentation): the vote plane holds the passes of MC dropout alone'),
     ('agreement', _lacks_mc, 'others.agreement needs others.mc: there are no samples to compare without MC dropout passes'),
     ('agreement', _sharded, 'others.agreement is not sharded: run the script in one process (a vote plane lives where all passes of a batch run)'),
+) + tuple(('laplace', key, 'others.laplace does not compose with others.{}: the Laplace predictive belongs to the one deterministic pass'.format(key))
+          for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples')) + (
+    ('laplace', 'density', 'others.laplace does not compose with others.density: each replaces the default predict step with its own'),
 )
 
 
@@ -682,30 +690,73 @@ def _density(context):
 class DensityWriteHook(loops.TestLoopHook):
     """``others.density``: ``{subject}_density.nii.gz``, the float32 energy of the subject's voxels (``output['density']``, assembled like the
     probabilities), written beside the files of the run -- whose names and bytes it leaves alone."""
+    KEY = 'density'        # the others.* key that asked for the map
+    ENTRY = 'density'      # the assembled entry and the file's suffix
 
     def __init__(self, in_background=True):
         self.in_background = in_background
 
     def on_test_subject_end(self, subject_context, task_context, context):
         data = subject_context.subject_data
-        energy = data.get('density')
+        energy = data.get(self.ENTRY)
         if energy is None:
-            raise ValueError('others.density: subject {} came without its density map'.format(subject_context.subject_index))
+            raise ValueError('others.{}: subject {} came without its {} map'.format(self.KEY, subject_context.subject_index, self.ENTRY))
         subject = data.get('subject', subject_context.subject_index)
         energy = np.asarray(energy)
         energy = np.ascontiguousarray(energy[..., 0] if energy.shape[-1] == 1 else energy, dtype=np.float32)
-        properties, path = data.get('properties'), os.path.join(context.test_dir, '{}_density.nii.gz'.format(subject))
+        properties, path = data.get('properties'), os.path.join(context.test_dir, '{}_{}.nii.gz'.format(subject, self.ENTRY))
         nifti.do_work(lambda: nifti.write(path, energy, properties), in_background=self.in_background)
 
     def on_termination(self, context):
         nifti.join_all()
 
 
-def _default_plan(context, world, density_fit=None):
-    """The one decision of the default script: density, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the entries they add
-    to the assembled subject, the per-subject hooks that write them)."""
+class LaplaceStdWriteHook(DensityWriteHook):
+    """``others.laplace``: ``{subject}_laplace_std.nii.gz``, the float32 std of the predicted class's logit (``output['laplace_std']``), written
+    beside the files of the run; the probabilities and prediction files hold the Laplace predictive."""
+    KEY = 'laplace'
+    ENTRY = 'laplace_std'
+
+
+class LaplaceRecordHook(CorruptionRecordHook):
+    """``others.laplace``: ``<test_dir>/laplace.json`` -- the fit's scalars, its file, the link, the samples and the seed -- written by the rank
+    that writes the run's output, as the corruption record is."""
+
+    def __init__(self, record):
+        super().__init__(record, 'laplace.json')
+
+
+def _laplace(context):
+    """``others.laplace: <path to laplace.npz>`` (an rcu_amd extension, include/rcu.h "Last-layer Laplace"; the fit_laplace scripts write the
+    file) with ``others.laplace_link`` (probit, the default, or sample) and ``others.laplace_samples`` (the draws of the sample link): the
+    deterministic default run with the Laplace predictive as its probabilities -> (the predict step, the record of ``laplace.json``), or None
+    without the key.  One eval-mode pass per batch: a ValueError that names both keys beside the keys that sample and beside others.density
+    (``_RULES``).  Composes with others.corruption, others.device_metrics and others.temperature -- the fit must have been made at that
+    temperature, which the step checks against the model."""
+    others = context.config.others
+    if not hasattr(others, 'laplace'):
+        return None
+    _check_rules(others, None, 'laplace')      # (its rules name keys alone: no world to ask)
+    value = others.laplace
+    if not isinstance(value, (str, os.PathLike)):
+        raise ValueError('others.laplace must be the path of a laplace.npz (bin-dl/*_fit_laplace.py), got {!r}'.format(value))
+    try:
+        fit = laplace_mod.load_laplace(value)
+        link = _other(context, 'laplace_link', 'probit')
+        seed = 0 if context.config.seed is None else int(context.config.seed)
+        step = steps.LaplacePredictStep(fit, link=link, samples=_other(context, 'laplace_samples', 0), seed=seed)
+    except ValueError as e:
+        raise ValueError('others.laplace: {}'.format(e)) from None
+    return step, dict(fit.as_dict(), file=os.fspath(value), link=link, samples=step.samples, seed=seed)
+
+
+def _default_plan(context, world, density_fit=None, laplace_step=None):
+    """The one decision of the default script: density, laplace, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the entries
+    they add to the assembled subject, the per-subject hooks that write them)."""
     if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
         return [steps.DensityPredictStep(density_fit)], ('density',), [DensityWriteHook()]
+    if laplace_step is not None:     # (the same)
+        return [laplace_step], ('laplace_std',), [LaplaceStdWriteHook()]
     others = context.config.others
     adaptive = _adaptive(context, world)
     agreement = adaptive is None and _agreement(context, world)      # (beside a schedule the key is off: _RULES)
@@ -884,11 +935,13 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     _check_others(context, 'default', world)
     density_fit = _density(context)      # (refuses others.density beside the keys that sample)
+    laplace = _laplace(context)          # (refuses others.laplace beside them and beside others.density)
     corrupt_steps, corrupt_hooks = _corruption(context)
-    test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit)
+    test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit, None if laplace is None else laplace[0])
+    record_hooks = [] if laplace is None else [LaplaceRecordHook(laplace[1])]
     return _run(context, dataset, corrupt_steps + test_steps, WriteHook(link_inputs=dataset == 'isic'),
                 ('probabilities',) + more_entries if dataset == 'brats' else None, world,
-                startup_hooks=_temperature_hooks(context) + corrupt_hooks, subject_hooks=subject_hooks)
+                startup_hooks=_temperature_hooks(context) + corrupt_hooks + record_hooks, subject_hooks=subject_hooks)
 
 
 def test_ensemble(dataset, config_file=None, device='cuda'):
@@ -1164,7 +1217,38 @@ def fit_density(dataset, config_file, device='cuda'):
     return fit
 
 
-for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density):
+def _image_batches(context, device):
+    """The images of every loader batch of ``test_data`` on the device: no labels are read."""
+    for batch in context.test_data.loader:
+        yield batch['images'].float().to(device).contiguous()
+
+
+def fit_laplace(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_laplace.py (EXTENSION): fit the last-layer Laplace approximation (rcu_amd.laplace) on the volumes a test
+    configuration's ``test_data`` names, with one eval-mode pass per batch; no labels are needed.  ``others.laplace_hessian_scale`` (1.0),
+    ``others.laplace_prior_precision`` (1.0; a number > 0 or ``evidence``) and ``others.temperature`` (a number or a temperature.json: the model
+    is fitted as it will run) are the fit's options.  Writes ``laplace.npz`` and a readable ``laplace.json`` into the run directory and returns
+    the fit; ``others.laplace: <that .npz>`` applies it in the default test scripts."""
+    context, _ = _fit_context('fit_laplace', dataset, config_file, device, laplace_mod.check_model)      # (no U-Net, sigma_out, C outside 2..4: refused)
+    if hasattr(context.config.others, 'temperature'):
+        context.model.set_temperature(calibration.load_temperature(context.config.others.temperature))
+    fit = laplace_mod.fit_laplace(context.model, _image_batches(context, context.device),
+                                  hessian_scale=_other(context, 'laplace_hessian_scale', 1.0),
+                                  prior_precision=_other(context, 'laplace_prior_precision', 1.0))
+    path = os.path.join(context.test_dir, 'laplace.npz')
+    laplace_mod.save_laplace(fit, path)
+    record = dict(fit.as_dict(), model_dir=context.config.model_dir, test_at=context.config.test_at, dataset=context.config.test_data.dataset,
+                  prior_precision=_other(context, 'laplace_prior_precision', 1.0))
+    with open(os.path.join(context.test_dir, 'laplace.json'), 'w') as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write('\n')
+    logging.info('Laplace fit: F = %d, C = %d, tau %.6g, hessian_scale %.6g, temperature %.6g, %d voxels -> %s', fit.F, fit.C, fit.tau,
+                 fit.hessian_scale, fit.temperature, fit.voxels, path)
+    print('laplace: {}'.format(path))
+    return fit
+
+
+for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density, fit_laplace):
     _fn.__test__ = False   # not pytest tests
 
 

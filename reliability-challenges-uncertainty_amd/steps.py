@@ -909,6 +909,54 @@ class DensityPredictStep(BatchStep):
         batch_context.output['probabilities'] = softmax(logits)
 
 
+class LaplacePredictStep(BatchStep):
+    """EXTENSION -- last-layer Laplace uncertainty (rcu_amd.laplace, include/rcu.h "Last-layer Laplace") in place of the default predict step: one
+    eval-mode forward with the classifier tap; ``output['logits']`` keeps the bits of SegmentationPredictStep, ``output['probabilities']`` is the
+    predictive of ``fit`` (a laplace.LaplaceFit) and ``output['laplace_std']``, float32 ``[N, 1, H, W]``, the standard deviation of the predicted
+    class's logit -- computed from the tap's view while it is valid, before any other forward on that plan.
+    ``link='probit'``: the mean-field probit softmax(z / sqrt(1 + pi/8 s2)), one kernel.  ``link='sample'``: (1/S) sum_s softmax(z + std * eps_s)
+    with ``samples`` = S draws of diagonal noise by ``sample_logits`` (rcu_logit_sampling), the noise of slice g keyed by ``pass_seed(seed, 0)``
+    and g as AleatoricPredictStep keys it -- the same bits for any batching."""
+
+    LINKS = ('probit', 'sample')
+
+    def __init__(self, fit, link='probit', samples=0, seed=0) -> None:
+        super().__init__()
+        from . import laplace
+        if not isinstance(fit, laplace.LaplaceFit):
+            raise ValueError('LaplacePredictStep needs a laplace.LaplaceFit, got {}'.format(type(fit).__name__))
+        if link not in self.LINKS:
+            raise ValueError('link must be one of {}, got {!r}'.format(', '.join(self.LINKS), link))
+        self.fit, self.link = fit, link
+        self.samples = check_logit_samples(samples) if link == 'sample' else 0
+        if link == 'sample' and self.samples < 1:
+            raise ValueError("link='sample' needs samples >= 1, got {!r}".format(samples))
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError('LaplacePredictStep needs an integer seed, got {!r}'.format(seed))
+        self.seed = seed
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        from . import laplace
+        _check_context(context)
+        model = context.model
+        laplace.check_model(model, self.fit)
+        images = _images_to_device(batch_context, context)
+        sampled = self.link == 'sample'
+        with laplace.eval_head_features(model):
+            logits = model(images)
+            out = laplace.predict(self.fit, model.head_features, logits, std=sampled, std_pred=not sampled, prediction=False)
+        batch_context.output['logits'] = logits
+        if sampled:
+            probs = sample_logits(logits, out['std'], self.samples, pass_seed(self.seed, 0), first_sample_of(batch_context, logits.shape[0]))
+            # the std of the class the sampled predictive chooses: its first maximum, as the writers take it
+            chosen = prediction_and_foreground(probs)[0].long().unsqueeze(1)
+            batch_context.output['probabilities'] = probs
+            batch_context.output['laplace_std'] = torch.gather(out['std'], 1, chosen)
+        else:
+            batch_context.output['probabilities'] = out['probabilities']
+            batch_context.output['laplace_std'] = out['std_pred']
+
+
 class SampleAgreementStep(BatchStep):
     """Behind the summary: pops ``sample_votes`` (McPredictStep with ``agreement=True``) and writes ``output['agreement']``, one int64 row
     ``[(T + 1) + T (T + 1) / 2]`` per slice -- ``hist`` then the upper triangle ``pairs`` of include/rcu.h's rcu_agreement_tables, one image per
