@@ -1,4 +1,4 @@
-"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h).
+"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h and include/rcu_fit.h).
 
 The library is the product: if it is missing or a call fails this module raises -- there is no
 Python / CPU fallback anywhere in the package.
@@ -202,6 +202,14 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
 }
 
+# the second header, include/rcu_fit.h (SIGNATURES is include/rcu.h, name for name)
+FIT_SIGNATURES = {
+    'rcu_postnet_fit_param_count': (c_size_t, [c_int, c_int]),
+    'rcu_postnet_fit_workspace_bytes': (c_size_t, [c_int, c_int, c_size_t, c_size_t]),
+    'rcu_postnet_loss_grad': (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -217,7 +225,7 @@ def load():
         raise RuntimeError('{} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            '(there is no CPU fallback)'.format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

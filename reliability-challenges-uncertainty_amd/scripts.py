@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import auxiliary as auxiliary_mod
 from . import calibration
 from . import corruption as corruption_mod
 from . import data as data_mod
@@ -34,6 +35,7 @@ from . import evaluation as ev
 from . import laplace as laplace_mod
 from . import loops
 from . import management as mgt
+from . import model as model_mod
 from . import nifti
 from . import steps
 
@@ -356,21 +358,25 @@ _TEST_SCRIPTS = frozenset(('default', 'ensemble', 'aleatoric', 'auxiliary_feat',
 _DEFAULT = frozenset(('default',))
 _ONE_PASS_FIT = 'others.{}: the density fit is one eval-mode pass per batch and does not take it'
 _ONE_PASS_LAPLACE = 'others.{}: the Laplace fit is one eval-mode pass per batch and does not take it'
+_ONE_PASS_AUXILIARY = 'others.{}: the auxiliary fit is one eval-mode pass of the frozen U-Net per batch and does not take it'
 _OtherKey = collections.namedtuple('_OtherKey', 'name description home scripts tail overrides', defaults=('', {}))
 # The extension keys of ``others`` that not every script takes, in the order they are checked: name, the description and the home its refusal
 # names, the scripts that take it, a tail to the refusal, the scripts that refuse it in words of their own.  A new key is a row here and its builder.
 _OTHERS = (
     _OtherKey('tta', 'test-time augmentation', 'the default test scripts only', _DEFAULT,
               overrides={'fit_temperature': 'others.tta: the temperature fit does not run under test-time augmentation',
-                         'fit_density': _ONE_PASS_FIT.format('tta'), 'fit_laplace': _ONE_PASS_LAPLACE.format('tta')}),
+                         'fit_density': _ONE_PASS_FIT.format('tta'), 'fit_laplace': _ONE_PASS_LAPLACE.format('tta'),
+                         'fit_auxiliary_feat': _ONE_PASS_AUXILIARY.format('tta')}),
     _OtherKey('mc', None, None, _TEST_SCRIPTS | {'fit_temperature'},
-              overrides={'fit_density': _ONE_PASS_FIT.format('mc'), 'fit_laplace': _ONE_PASS_LAPLACE.format('mc')}),
+              overrides={'fit_density': _ONE_PASS_FIT.format('mc'), 'fit_laplace': _ONE_PASS_LAPLACE.format('mc'),
+                         'fit_auxiliary_feat': _ONE_PASS_AUXILIARY.format('mc')}),
     _OtherKey('temperature', 'temperature scaling', 'the default test scripts only', _DEFAULT | {'fit_laplace'}),
     _OtherKey('agreement', 'MC sample agreement', 'the default test scripts with others.mc only', _DEFAULT),
     _OtherKey('mc_adaptive', 'adaptive MC dropout', 'the default test scripts with others.mc only', _DEFAULT),
     _OtherKey('logit_samples', 'test-time logit sampling', 'the aleatoric test scripts only', frozenset(('aleatoric',))),
     _OtherKey('corruption', 'input corruptions', 'the test scripts only', _TEST_SCRIPTS, tail=': calibration is fitted on clean validation data'),
     _OtherKey('density', 'feature-space density uncertainty', 'the default test scripts only', _DEFAULT),
+    _OtherKey('auxiliary_fit', 'the options of the auxiliary fit', 'the auxiliary fit scripts only', frozenset(('fit_auxiliary_feat',))),
     _OtherKey('laplace', 'last-layer Laplace uncertainty', 'the default test scripts only', _DEFAULT),
 )
 
@@ -1248,7 +1254,77 @@ def fit_laplace(dataset, config_file, device='cuda'):
     return fit
 
 
-for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density, fit_laplace):
+_AUXILIARY_FIT_OPTIONS = {'epochs': 1, 'lr': 1e-4, 'nb_convs': 3}
+
+
+def _auxiliary_fit_options(context):
+    """``others.auxiliary_fit: {epochs, lr: 1e-4, nb_convs: 3}`` -> the three options; anything else in it is refused by name."""
+    value = _other(context, 'auxiliary_fit', None)
+    given = {} if value is None else (dict(value) if isinstance(value, dict) else dict(vars(value)))
+    unknown = sorted(set(given) - set(_AUXILIARY_FIT_OPTIONS))
+    if unknown:
+        raise ValueError('others.auxiliary_fit takes {}; got {}'.format(', '.join(sorted(_AUXILIARY_FIT_OPTIONS)), ', '.join(unknown)))
+    options = dict(_AUXILIARY_FIT_OPTIONS, **given)
+    epochs, lr, nb_convs = options['epochs'], options['lr'], options['nb_convs']
+    if isinstance(epochs, bool) or not isinstance(epochs, int) or epochs < 1:
+        raise ValueError('others.auxiliary_fit.epochs must be an integer >= 1, got {!r}'.format(epochs))
+    if isinstance(nb_convs, bool) or not isinstance(nb_convs, int) or not 1 <= nb_convs <= auxiliary_mod.MAX_CONVS:
+        raise ValueError('others.auxiliary_fit.nb_convs must be an integer in 1..{}, got {!r}'.format(auxiliary_mod.MAX_CONVS, nb_convs))
+    try:
+        lr = float(lr)
+    except (TypeError, ValueError):
+        raise ValueError('others.auxiliary_fit.lr must be a number > 0, got {!r}'.format(lr)) from None
+    if not (np.isfinite(lr) and lr > 0):
+        raise ValueError('others.auxiliary_fit.lr must be a number > 0, got {!r}'.format(lr))
+    return epochs, lr, nb_convs
+
+
+def _check_auxiliary_model(model):
+    channels = density_mod._feature_channels(model)      # (refuses a model that is no U-Net)
+    if channels > auxiliary_mod.MAX_FEATURES:
+        raise ValueError('the auxiliary fit takes U-Nets of up to {} feature channels (start_filters), got {}'.format(auxiliary_mod.MAX_FEATURES, channels))
+
+
+def fit_auxiliary_feat(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_auxiliary_feat.py (EXTENSION; the reference's *_train_auxiliary_feat.py as a post-hoc fit): fit the auxiliary
+    PostNet on the features of the frozen segmentation model the configuration's ``model_dir`` / ``test_at`` name, on the volumes its
+    ``test_data`` names (``batch_size`` and ``shuffle`` honoured under the YAML ``seed``), target arg-max != (labels > 0), all-black slices
+    dropped.  ``others.auxiliary_fit: {epochs, lr: 1e-4, nb_convs: 3}`` are the fit's options.  Writes into the run directory a PostNet model
+    directory ``model_auxiliary_feat`` (a checkpoint per epoch, the last one also as ``best``), ``auxiliary_fit.json`` and ``auxiliary_fit.csv``
+    (one row per epoch: steps, voxels, error fraction, mean loss) and returns the rows.  That directory as ``model_dir`` with the segmentation
+    model under ``others.model_dir`` runs the ``*_test_auxiliary_feat.py`` scripts."""
+    context, seed = _fit_context('fit_auxiliary_feat', dataset, config_file, device, _check_auxiliary_model)
+    epochs, lr, nb_convs = _auxiliary_fit_options(context)
+    params = dict(in_channels=int(context.model.start_filters), nb_classes=2, nb_convs=nb_convs)
+    postnet = model_mod.PostNet(**params)
+    files = mgt.ModelFiles(context.test_dir, 'auxiliary_feat')
+
+    def save(epoch, net, row):
+        state = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+        mgt.save_model(files, 'postnet', params, state, epoch=epoch, is_best=False)
+        if epoch == epochs:
+            mgt.save_model(files, 'postnet', params, state, epoch=epoch, is_best=True)
+        logging.info('auxiliary fit: epoch %d, %d steps, %d voxels, error fraction %.6f, mean loss %.6f', epoch, row['steps'], row['voxels'],
+                     row['error_fraction'], row['mean_loss'])
+
+    rows = auxiliary_mod.fit_auxiliary_feat(context.model, postnet, lambda: _validation_batches(context, dataset, 'cpu'), epochs, lr=lr, seed=seed,
+                                            skip_black=True, on_epoch=save)
+    with open(os.path.join(context.test_dir, 'auxiliary_fit.csv'), 'w', newline='') as f:
+        writer = csv.writer(f)
+        writer.writerow(['epoch', 'steps', 'voxels', 'error_fraction', 'mean_loss'])
+        for row in rows:
+            writer.writerow([row['epoch'], row['steps'], row['voxels'], repr(row['error_fraction']), repr(row['mean_loss'])])
+    record = dict(params, epochs=epochs, lr=lr, seed=seed, model_dir=context.config.model_dir, test_at=context.config.test_at,
+                  dataset=context.config.test_data.dataset, postnet_model_dir=files.model_dir, rows=rows)
+    with open(os.path.join(context.test_dir, 'auxiliary_fit.json'), 'w') as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print('auxiliary_feat: {}'.format(files.model_dir))
+    return rows
+
+
+for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density, fit_laplace,
+            fit_auxiliary_feat):
     _fn.__test__ = False   # not pytest tests
 
 
