@@ -26,7 +26,7 @@ def make_parser():
     parser.add_argument('--ids', type=str, nargs='*', help='the ids of the runs to be evaluated (default: the reference\'s eight; rcu_amd only, when '
                         'named: density -- a default run under others.density, whose <subject>_density.nii.gz is rescaled like the aleatoric sigma, '
                         'run minmax first; laplace laplace_std -- a default run under others.laplace as a probabilities run on the predictive and as its '
-                        '<subject>_laplace_std.nii.gz, rescaled like sigma)')
+                        '<subject>_laplace_std.nii.gz, rescaled like sigma; knn -- a default run under others.knn, whose <subject>_knn.nii.gz is rescaled like sigma)')
     parser.add_argument('--act', type=str, nargs='*', help='the names of the evaluation configuration: minmax, ece_dice, calib, bnf_ue (the default: '
                         'all four) and, rcu_amd only, ue_curves (threshold-free uncertainty-error metrics from a level histogram) components '
                         '(component-level metrics from connected components: false-positive detection by mean uncertainty, filtered Dice) and '

@@ -1,4 +1,4 @@
-"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h and include/rcu_fit.h).
+"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h, include/rcu_fit.h and include/rcu_knn.h).
 
 The library is the product: if it is missing or a call fails this module raises -- there is no
 Python / CPU fallback anywhere in the package.
@@ -210,6 +210,13 @@ FIT_SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
 }
 
+# the third header, include/rcu_knn.h
+RCU_KNN_MAX_FEATURES, RCU_KNN_MAX_BANK, RCU_KNN_MAX_K = 32, 65536, 8
+KNN_SIGNATURES = {
+    'rcu_knn_sample_keys': (c_int, [c_size_t, c_size_t, c_void_p, c_uint64, c_void_p, c_void_p]),
+    'rcu_knn_distances': (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -225,7 +232,7 @@ def load():
         raise RuntimeError('{} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            '(there is no CPU fallback)'.format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FIT_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

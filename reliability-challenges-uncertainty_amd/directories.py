@@ -28,6 +28,10 @@ _SETTING_OF_RUN['density'] = 'DENSITY'
 # its {subject}_laplace_std.nii.gz, unbounded like sigma.  Evaluated when named (--ids laplace laplace_std)
 LAPLACE_RUN_IDS = ('laplace', 'laplace_std')
 _SETTING_OF_RUN.update(laplace='LAPLACE', laplace_std='LAPLACE_STD')
+# ... and a default run under others.knn (rcu_amd.knn): its {subject}_knn.nii.gz, the distance to the k-th nearest bank row, unbounded like sigma.
+# Evaluated when named (--ids knn)
+KNN_RUN_IDS = ('knn',)
+_SETTING_OF_RUN['knn'] = 'KNN'
 for _ds in ('ISIC', 'BRATS'):
     for _run, _key in _SETTING_OF_RUN.items():
         # e.g. BRATS_BASELINE_MC_PREDICT = '<timestamp>_brats_baseline_mc'; unset: the run id itself (out/predictions/brats/baseline_mc)
@@ -74,8 +78,8 @@ MINMAX_PLACEHOLDER = 'eval_summary_minmax_{}.csv'
 
 def prediction_dir(dataset, run_id):
     """Prediction directory of a run, as rechun/eval/evaldata.py:21-46 composes it: <DS>_PREDICT_DIR / <DS>_<RUN>_PREDICT."""
-    if run_id not in RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS:
-        raise ValueError('unknown run id {!r}: the run types are {}'.format(run_id, ', '.join(RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS)))
+    if run_id not in RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS + KNN_RUN_IDS:
+        raise ValueError('unknown run id {!r}: the run types are {}'.format(run_id, ', '.join(RUN_IDS + EXTENSION_RUN_IDS + LAPLACE_RUN_IDS + KNN_RUN_IDS)))
     ds = dataset.upper()
     return os.path.join(globals()['{}_PREDICT_DIR'.format(ds)], globals()['{}_{}_PREDICT'.format(ds, _SETTING_OF_RUN[run_id])])
 

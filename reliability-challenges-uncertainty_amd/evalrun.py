@@ -80,6 +80,9 @@ CONFIDENCE_ENTRY['density'] = 'density'
 # and calib_curves speak about it), `laplace_std` its {subject}_laplace_std.nii.gz (the std of the predicted class's logit), which takes sigma's path
 CONFIDENCE_ENTRY['laplace'] = 'probabilities'
 CONFIDENCE_ENTRY['laplace_std'] = 'laplace_std'
+# rcu_amd extension: a default run under others.knn -- its {subject}_knn.nii.gz (the distance to the k-th nearest bank row, rcu_amd.knn) is unbounded
+# like sigma and takes sigma's path
+CONFIDENCE_ENTRY['knn'] = 'knn'
 
 
 # ------------------------------------------------------------------------------------- CSV hooks
@@ -446,7 +449,7 @@ class SaveQuantilesAction(EvalAction):
     runs_first = True
     whole_run = True
     checks_range = False
-    ENTRIES = ('sigma', 'density', 'laplace_std')
+    ENTRIES = ('sigma', 'density', 'laplace_std', 'knn')
 
     def __init__(self, quantile_dir, quantiles, need_mask):
         super().__init__()

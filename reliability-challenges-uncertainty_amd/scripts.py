@@ -10,6 +10,7 @@ Each function is the ``main`` of the same-named reference script (flags unchange
     bin-eval/eval_uncertainty.py   --ds --ids --act               (bin-eval/eval_uncertainty.py:13-50, 248-288)
     bin-dl/{brats,isic}_fit_temperature.py -config_file           (EXTENSION: temperature scaling, fit_temperature)
     bin-dl/{brats,isic}_fit_density.py -config_file               (EXTENSION: feature-space density, fit_density)
+    bin-dl/{brats,isic}_fit_knn.py -config_file                   (EXTENSION: nearest-neighbour feature uncertainty, fit_knn)
     bin-dl/{brats,isic}_fit_laplace.py -config_file               (EXTENSION: last-layer Laplace, fit_laplace)
 Config ids map to the same YAML names under ``<project>/config``; paths inside the YAML stay relative to the
 working directory, as in the reference.  Datasets: see rcu_amd.data (volume directories instead of pymia HDF5).
@@ -32,6 +33,7 @@ from . import density as density_mod
 from . import distributed as rdist
 from . import evalrun
 from . import evaluation as ev
+from . import knn as knn_mod
 from . import laplace as laplace_mod
 from . import loops
 from . import management as mgt
@@ -377,6 +379,8 @@ _OTHERS = (
     _OtherKey('corruption', 'input corruptions', 'the test scripts only', _TEST_SCRIPTS, tail=': calibration is fitted on clean validation data'),
     _OtherKey('density', 'feature-space density uncertainty', 'the default test scripts only', _DEFAULT),
     _OtherKey('auxiliary_fit', 'the options of the auxiliary fit', 'the auxiliary fit scripts only', frozenset(('fit_auxiliary_feat',))),
+    _OtherKey('knn', 'nearest-neighbour feature uncertainty', 'the default test scripts only', _DEFAULT),
+    _OtherKey('knn_bank', 'the options of the k-NN bank', 'the k-NN fit scripts only', frozenset(('fit_knn',))),
     _OtherKey('laplace', 'last-layer Laplace uncertainty', 'the default test scripts only', _DEFAULT),
 )
 
@@ -406,7 +410,10 @@ _RULES = tuple(('density', key, 'others.density does not compose with others.{}:
 ) + tuple(('laplace', key, 'others.laplace does not compose with others.{}: the Laplace predictive belongs to the one deterministic pass'.format(key))
           for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples')) + (
     ('laplace', 'density', 'others.laplace does not compose with others.density: each replaces the default predict step with its own'),
-)
+) + tuple(('knn', key, 'others.knn does not compose with others.{}: the k-NN map belongs to the one deterministic pass'.format(key))
+          for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples')) + tuple(
+    ('knn', key, 'others.knn does not compose with others.{}: each replaces the default predict step with its own'.format(key))
+    for key in ('density', 'laplace'))
 
 
 _TAKEN_BY = {row.name: row.scripts for row in _OTHERS}
@@ -756,11 +763,52 @@ def _laplace(context):
     return step, dict(fit.as_dict(), file=os.fspath(value), link=link, samples=step.samples, seed=seed)
 
 
-def _default_plan(context, world, density_fit=None, laplace_step=None):
-    """The one decision of the default script: density, laplace, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the entries
-    they add to the assembled subject, the per-subject hooks that write them)."""
+class KnnWriteHook(DensityWriteHook):
+    """``others.knn``: ``{subject}_knn.nii.gz``, the float32 distance of the subject's voxels to their k-th nearest bank row (``output['knn']``),
+    written beside the files of the run -- whose names and bytes it leaves alone."""
+    KEY = 'knn'
+    ENTRY = 'knn'
+
+
+class KnnRecordHook(CorruptionRecordHook):
+    """``others.knn``: ``<test_dir>/knn.json`` -- the bank's scalars, its file and k -- written by the rank that writes the run's output, as the
+    corruption record is."""
+
+    def __init__(self, record):
+        super().__init__(record, 'knn.json')
+
+
+def _knn(context):
+    """``others.knn: <path to knn.npz>`` (an rcu_amd extension, include/rcu_knn.h; the fit_knn scripts write the file) with ``others.knn_k``
+    (1..8, 5 by default): the deterministic default run with the distance to the k-th nearest bank row as one more map per subject -> (the
+    predict step, the record of ``knn.json``), or None without the key.  One eval-mode pass per batch: a ValueError that names both keys beside
+    the keys that sample and beside others.density and others.laplace (``_RULES``).  Composes with others.corruption, others.device_metrics and
+    others.temperature (which rescales conv_cls.1 alone: the features do not move)."""
+    others = context.config.others
+    if not hasattr(others, 'knn'):
+        return None
+    _check_rules(others, None, 'knn')      # (its rules name keys alone: no world to ask)
+    value = others.knn
+    if not isinstance(value, (str, os.PathLike)):
+        raise ValueError('others.knn must be the path of a knn.npz (bin-dl/*_fit_knn.py), got {!r}'.format(value))
+    try:
+        bank = knn_mod.load_knn(value)
+    except ValueError as e:
+        raise ValueError('others.knn: {}'.format(e)) from None
+    try:
+        step = steps.KnnPredictStep(bank, _other(context, 'knn_k', 5))
+    except ValueError as e:
+        raise ValueError('others.knn_k: {}'.format(e)) from None
+    return step, dict(bank.as_dict(), file=os.fspath(value), k=step.k)
+
+
+def _default_plan(context, world, density_fit=None, laplace_step=None, knn_step=None):
+    """The one decision of the default script: density, k-NN, laplace, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the
+    entries they add to the assembled subject, the per-subject hooks that write them)."""
     if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
         return [steps.DensityPredictStep(density_fit)], ('density',), [DensityWriteHook()]
+    if knn_step is not None:         # (the same)
+        return [knn_step], ('knn',), [KnnWriteHook()]
     if laplace_step is not None:     # (the same)
         return [laplace_step], ('laplace_std',), [LaplaceStdWriteHook()]
     others = context.config.others
@@ -941,10 +989,12 @@ def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     _check_others(context, 'default', world)
     density_fit = _density(context)      # (refuses others.density beside the keys that sample)
+    knn = _knn(context)                  # (refuses others.knn beside them, beside others.density and beside others.laplace)
     laplace = _laplace(context)          # (refuses others.laplace beside them and beside others.density)
     corrupt_steps, corrupt_hooks = _corruption(context)
-    test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit, None if laplace is None else laplace[0])
-    record_hooks = [] if laplace is None else [LaplaceRecordHook(laplace[1])]
+    test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit, None if laplace is None else laplace[0],
+                                                            None if knn is None else knn[0])
+    record_hooks = ([] if laplace is None else [LaplaceRecordHook(laplace[1])]) + ([] if knn is None else [KnnRecordHook(knn[1])])
     return _run(context, dataset, corrupt_steps + test_steps, WriteHook(link_inputs=dataset == 'isic'),
                 ('probabilities',) + more_entries if dataset == 'brats' else None, world,
                 startup_hooks=_temperature_hooks(context) + corrupt_hooks + record_hooks, subject_hooks=subject_hooks)
@@ -1223,6 +1273,45 @@ def fit_density(dataset, config_file, device='cuda'):
     return fit
 
 
+_KNN_BANK_OPTIONS = {'per_class': 1024, 'normalize': True}
+
+
+def _knn_bank_options(context):
+    """``others.knn_bank: {per_class: 1024, normalize: true}`` -> the two options; anything else in it is refused by name."""
+    value = _other(context, 'knn_bank', None)
+    given = {} if value is None else (dict(value) if isinstance(value, dict) else dict(vars(value)))
+    unknown = sorted(set(given) - set(_KNN_BANK_OPTIONS))
+    if unknown:
+        raise ValueError('others.knn_bank takes {}; got {}'.format(', '.join(sorted(_KNN_BANK_OPTIONS)), ', '.join(unknown)))
+    options = dict(_KNN_BANK_OPTIONS, **given)
+    per_class, normalize = options['per_class'], options['normalize']
+    if isinstance(per_class, bool) or not isinstance(per_class, int) or not 1 <= 2 * per_class <= knn_mod.MAX_BANK:
+        raise ValueError('others.knn_bank.per_class must be an integer in 1..{}, got {!r}'.format(knn_mod.MAX_BANK // 2, per_class))
+    if not isinstance(normalize, bool):
+        raise ValueError('others.knn_bank.normalize must be true or false, got {!r}'.format(normalize))
+    return per_class, normalize
+
+
+def fit_knn(dataset, config_file, device='cuda'):
+    """bin-dl/{brats,isic}_fit_knn.py (EXTENSION): sample the bank of the nearest-neighbour feature uncertainty (rcu_amd.knn) on the volumes a test
+    configuration's ``test_data`` names -- the VALIDATION volumes, read as ``fit_temperature`` reads them, the slices counted in loader order --
+    with one eval-mode pass per batch, target labels > 0 (K = 2), under the YAML ``seed`` (0 without one).  ``others.knn_bank: {per_class: 1024,
+    normalize: true}`` are the fit's options.  Writes ``knn.npz`` and a readable ``knn.json`` into the run directory and returns the bank;
+    ``others.knn: <that .npz>`` applies it in the default test scripts."""
+    context, seed = _fit_context('fit_knn', dataset, config_file, device, knn_mod.check_model)      # (no U-Net, more than 32 channels: refused)
+    per_class, normalize = _knn_bank_options(context)
+    bank = knn_mod.fit_knn(context.model, _validation_batches(context, dataset, context.device), per_class, seed, normalize=normalize, nb_classes=2)
+    path = os.path.join(context.test_dir, 'knn.npz')
+    knn_mod.save_knn(bank, path)
+    record = dict(bank.as_dict(), model_dir=context.config.model_dir, test_at=context.config.test_at, dataset=context.config.test_data.dataset)
+    with open(os.path.join(context.test_dir, 'knn.json'), 'w') as f:
+        json.dump(record, f, indent=1, sort_keys=True)
+        f.write('\n')
+    logging.info('k-NN bank: F = %d, M = %d, counts %s, normalize %s, seed %d -> %s', bank.F, bank.M, bank.counts(), bank.normalize, bank.seed, path)
+    print('knn: {}'.format(path))
+    return bank
+
+
 def _image_batches(context, device):
     """The images of every loader batch of ``test_data`` on the device: no labels are read."""
     for batch in context.test_data.loader:
@@ -1324,7 +1413,7 @@ def fit_auxiliary_feat(dataset, config_file, device='cuda'):
 
 
 for _fn in (test_default, test_ensemble, test_aleatoric, test_auxiliary_feat, test_auxiliary_segm, fit_temperature, fit_density, fit_laplace,
-            fit_auxiliary_feat):
+            fit_auxiliary_feat, fit_knn):
     _fn.__test__ = False   # not pytest tests
 
 

@@ -909,6 +909,35 @@ class DensityPredictStep(BatchStep):
         batch_context.output['probabilities'] = softmax(logits)
 
 
+class KnnPredictStep(BatchStep):
+    """EXTENSION -- nearest-neighbour feature uncertainty (rcu_amd.knn, include/rcu_knn.h) in place of the default predict step: one eval-mode
+    forward with the feature tap, ``output['logits']`` and ``output['probabilities']`` as SegmentationPredictStep(do_probs=True) gives them, and
+    ``output['knn']``, the float32 distance ``[N, 1, H, W]`` of every voxel's feature vector to its ``k``-th nearest row of ``bank`` (a
+    knn.KnnBank), computed from the feature view while it is valid -- before any other forward on that plan."""
+
+    def __init__(self, bank, k=5) -> None:
+        super().__init__()
+        from . import knn
+        if not isinstance(bank, knn.KnnBank):
+            raise ValueError('KnnPredictStep needs a knn.KnnBank, got {}'.format(type(bank).__name__))
+        self.bank = bank
+        self.k = knn.check_k(bank, k)
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        from . import knn
+        _check_context(context)
+        model = context.model
+        channels = knn.check_model(model)
+        if channels != self.bank.F:
+            raise ValueError('the k-NN bank has F = {} feature channels, the model has {}'.format(self.bank.F, channels))
+        images = _images_to_device(batch_context, context)
+        with knn.eval_features(model):
+            logits = model(images)
+            batch_context.output['knn'] = knn.distances(self.bank, model.features, self.k)
+        batch_context.output['logits'] = logits
+        batch_context.output['probabilities'] = softmax(logits)
+
+
 class LaplacePredictStep(BatchStep):
     """EXTENSION -- last-layer Laplace uncertainty (rcu_amd.laplace, include/rcu.h "Last-layer Laplace") in place of the default predict step: one
     eval-mode forward with the classifier tap; ``output['logits']`` keeps the bits of SegmentationPredictStep, ``output['probabilities']`` is the
