@@ -39,7 +39,7 @@ namespace rcu {
 // Workgroup tile: WS slice groups x WR block rows of MFMA row blocks; a block = SB slices x BR tile rows x BC tile columns = 16
 // tiles of 4x4 pixels spanning the tile's full width.
 // FULLW: the tile spans the image's width (checked by the launcher), so the halo columns are zero padding and are not staged at all:
-// the LDS image holds TW positions per row and the lanes of the first / last tile column zero their outer patch column themselves.
+// the LDS image holds TW positions per row and the lanes of the first / last tile column read their outer patch column from a region of zeros (ZERO_DW).
 // What it buys is LDS: eight slices of 8x16 pixels (the 24x16 level) fit the 160 KB only without the two halo columns.
 // FOLD: 12x8-pixel images (the BraTS bottom level).  A slice is 3 x 2 = 6 tiles of 4x4 pixels, and the workgroup's 64 tile slots -- slot k = wave
 // k / 16, MFMA row k % 16 -- take the tiles of FOLD_TS = 10 consecutive slices one behind the other: slot k < 60 holds tile ((k % 6) / 2, k % 2) of
@@ -67,7 +67,15 @@ struct Wino4Tile {
     static constexpr int W_DW = NPOS * 4 * BN * 2;                           // [p][channel pair][cout][2]
     static constexpr int W_PIECES = W_DW / 256;
     static constexpr int NW = (W_PIECES + WAVES - 1) / WAVES;
-    static constexpr int BUF_DW = A_DW + W_DW;
+    // FULLW: row slots at the row pitch behind the image and the weights of EACH chunk buffer that hold zeros for the whole kernel (cleared once,
+    // never a target of the LDS-DMA: the pieces end at A_DW + W_DW).  The lanes of the first / last tile column read their outer patch column there.
+    // One region per buffer, at the same offset from the buffer's base, because a lane's column addresses are offsets from that base; whole 1 KB
+    // pieces, so the second buffer keeps the alignment of the first.  Four row slots serve the six patch rows: rows 0..3 and rows 4..5 have an
+    // address register each (aCol), and the second one points four rows lower (the 8x32 tile of four slices fills the 160 KB exactly with them).
+    static constexpr int ZERO_ROWS = 4;
+    static constexpr int ZERO_DW = FULLW ? (ZERO_ROWS * PITCH * 8 + 255) / 256 * 256 : 0;
+    static constexpr int ZERO_OFF = A_DW + W_DW;                             // dword offset of the region inside a buffer
+    static constexpr int BUF_DW = A_DW + W_DW + ZERO_DW;
     static constexpr int LDS_BYTES = 2 * BUF_DW * 4;
     static_assert(SB * BR * BC == 16 && WS * WR == WAVES && BC % 4 == 0, "block geometry");
     static_assert(!FOLD || (SB == 2 && BR == 2 && BC == 4 && WS == 4 && WR == 1 && FULLW), "the folded 12x8 geometry descends from the S8 block");
@@ -522,7 +530,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
     // fragment addresses (dword offsets inside a buffer) of the lane's patch columns j = 0..5, for patch rows 0..3 ([0]) and 4..5
     // ([1]: the swizzle's row bit flips); the row itself is an immediate offset
     int aCol[2][6];
-    bool zero_left = false, zero_right = false;   // FULLW: this lane's patch column 0 / 5 lies outside the image
     {
         int s, R0, tc;
         T::row_tile(wave, m16, s, R0, tc);
@@ -532,13 +539,16 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 int x = 4 * tc + j - (T::FULLW ? 1 : 0);   // staged column of patch column j
-                if (T::FULLW) x = min(max(x, 0), T::TW - 1);   // the two columns outside read a neighbour and are zeroed below
-                aCol[ip][j] = base + 8 * (x ^ T::swizzle(x, s, R0 + 4 * ip));
+                int row0 = base;
+                if (T::FULLW) {
+                    // zero padding left and right of the image: the column outside is read from the buffer's zero region -- at the position its
+                    // clamped neighbour has in a row (the row bases are multiples of 64 dwords: the same banks as the neighbour), rows 4..5 four
+                    // rows lower, so that the immediate row offsets i * PITCH * 8 stay inside the region's ZERO_ROWS slots
+                    if (x < 0 || x >= T::TW) row0 = T::ZERO_OFF - 4 * ip * T::PITCH * 8 + 2 * kq;
+                    x = min(max(x, 0), T::TW - 1);
+                }
+                aCol[ip][j] = row0 + 8 * (x ^ T::swizzle(x, s, R0 + 4 * ip));
             }
-        if (T::FULLW) {
-            zero_left = tc == 0;
-            zero_right = tc == T::TCOLS - 1;
-        }
     }
     const int b_addr = T::A_DW + (kq * T::BN + 2 * m16) * 2;
     const uint32_t w_voff = (uint32_t)(lane * 16);
@@ -612,6 +622,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
     if constexpr (HEAD) {   // the classifier: [2][32] weights, [2] biases (wino4_epilogue_head)
         if (tid < 66) smem[2 * T::BUF_DW + tid] = tid < 64 ? a.head_w[tid] : a.head_b[tid - 64];
     }
+    if constexpr (T::FULLW) {   // the zero regions of both buffers, once per kernel: nothing writes them again
+#pragma unroll
+        for (int i = 0; i < T::ZERO_DW; i += T::THREADS) smem[T::ZERO_OFF + i + tid] = smem[T::BUF_DW + T::ZERO_OFF + i + tid] = 0.f;
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     __syncthreads();
     {
@@ -637,11 +651,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
         for (int j = 0; j < 6; ++j)
             // volatile: keeps hipcc from fusing pairs of these reads into ds_read2_b64
             d[6 * i + j] = *(const volatile __attribute__((address_space(3))) f32x2*)(Ab + aCol[i >> 2][j] + i * (T::PITCH * 8));
-        if constexpr (T::FULLW) {   // zero padding left and right of the image
-            const f32x2 z = {0.f, 0.f};
-            d[6 * i] = zero_left ? z : d[6 * i];
-            d[6 * i + 5] = zero_right ? z : d[6 * i + 5];
-        }
     };
     auto load_weights = [&](f32x4 (&bv)[36], const float* Ab, int p) { bv[p] = *reinterpret_cast<const f32x4*>(Ab + b_addr + p * (8 * T::BN)); };
     // B^T d B in place on channel pairs (packed operations).  One-dimensional transform of (x0..x5):
