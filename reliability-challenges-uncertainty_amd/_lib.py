@@ -1,4 +1,4 @@
-"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h, include/rcu_fit.h and include/rcu_knn.h).
+"""ctypes binding of librcu_hip.so (the C ABI declared in include/rcu.h, include/rcu_fit.h, include/rcu_knn.h and include/rcu_warp.h).
 
 The library is the product: if it is missing or a call fails this module raises -- there is no
 Python / CPU fallback anywhere in the package.
@@ -217,6 +217,13 @@ KNN_SIGNATURES = {
     'rcu_knn_distances': (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# the fourth header, include/rcu_warp.h
+RCU_WARP_MAX_MATRICES = 64
+WARP_SIGNATURES = {
+    'rcu_warp_affine': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'rcu_mc_accumulate_warped': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -232,7 +239,7 @@ def load():
         raise RuntimeError('{} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                            '(there is no CPU fallback)'.format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FIT_SIGNATURES.items()) + list(KNN_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FIT_SIGNATURES.items()) + list(KNN_SIGNATURES.items()) + list(WARP_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes

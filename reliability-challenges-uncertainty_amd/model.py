@@ -364,12 +364,13 @@ class UNet(nn.Module):
             raise RuntimeError('rcu_amd.model.UNet only runs on the GPU (librcu_hip); got a {} tensor'.format(x.device))
         return x.to(torch.float32).contiguous()
 
-    def forward(self, x, masks=None):
+    def forward(self, x, masks=None, lane=0):
         """``masks``: None -> eval mode, or sampled if any Dropout2d is in train mode
-        (set_dropout_mode); a concatenated device tensor / list of per-site arrays to inject."""
+        (set_dropout_mode); a concatenated device tensor / list of per-site arrays to inject.
+        ``lane``: the workspace of that stream lane (``_handle``), for forwards that run concurrently on several HIP streams."""
         x = self._check_input(x)
         n, _, h, w = x.shape
-        handle = self._handle(h, w, n)
+        handle = self._handle(h, w, n, lane)
         self.head_features = None      # a view of the last ``forward``: any forward on the handle ends it
         if masks is None and self.mc_active():
             masks = self.sample_masks(n, x.device)

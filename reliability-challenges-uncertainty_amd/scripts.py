@@ -381,6 +381,10 @@ _OTHERS = (
     _OtherKey('auxiliary_fit', 'the options of the auxiliary fit', 'the auxiliary fit scripts only', frozenset(('fit_auxiliary_feat',))),
     _OtherKey('knn', 'nearest-neighbour feature uncertainty', 'the default test scripts only', _DEFAULT),
     _OtherKey('knn_bank', 'the options of the k-NN bank', 'the k-NN fit scripts only', frozenset(('fit_knn',))),
+    _OtherKey('tta_affine', 'affine test-time augmentation', 'the default test scripts only', _DEFAULT,
+              overrides={'fit_temperature': 'others.tta_affine: the temperature fit does not run under test-time augmentation',
+                         'fit_density': _ONE_PASS_FIT.format('tta_affine'), 'fit_laplace': _ONE_PASS_LAPLACE.format('tta_affine'),
+                         'fit_auxiliary_feat': _ONE_PASS_AUXILIARY.format('tta_affine')}),
     _OtherKey('laplace', 'last-layer Laplace uncertainty', 'the default test scripts only', _DEFAULT),
 )
 
@@ -407,6 +411,13 @@ _RULES = tuple(('density', key, 'others.density does not compose with others.{}:
     ('agreement', 'tta', 'others.agreement does not compose with others.tta (test-time augmentation): the vote plane holds the passes of MC dropout alone'),
     ('agreement', _lacks_mc, 'others.agreement needs others.mc: there are no samples to compare without MC dropout passes'),
     ('agreement', _sharded, 'others.agreement is not sharded: run the script in one process (a vote plane lives where all passes of a batch run)'),
+) + (
+    ('tta_affine', 'tta', 'others.tta_affine does not compose with others.tta: a run takes its transforms from one of the two keys'),
+    ('tta_affine', 'agreement', 'others.tta_affine does not compose with others.agreement: the vote plane holds the passes of MC dropout alone'),
+    ('tta_affine', 'mc_adaptive', 'others.tta_affine does not compose with others.mc_adaptive: the transforms of a slice share its statistics'),
+) + tuple(('tta_affine', key, 'others.tta_affine does not compose with others.{}: that map belongs to the one deterministic pass'.format(key))
+          for key in ('density', 'laplace', 'knn')) + (
+    ('tta_affine', _sharded, 'others.tta_affine is not sharded: run the script in one process'),
 ) + tuple(('laplace', key, 'others.laplace does not compose with others.{}: the Laplace predictive belongs to the one deterministic pass'.format(key))
           for key in ('mc', 'tta', 'agreement', 'mc_adaptive', 'logit_samples')) + (
     ('laplace', 'density', 'others.laplace does not compose with others.density: each replaces the default predict step with its own'),
@@ -802,9 +813,52 @@ def _knn(context):
     return step, dict(bank.as_dict(), file=os.fspath(value), k=step.k)
 
 
-def _default_plan(context, world, density_fit=None, laplace_step=None, knn_step=None):
-    """The one decision of the default script: density, k-NN, laplace, tta, adaptive, agreement, sharded mc, mc or plain -> (batch steps, the
-    entries they add to the assembled subject, the per-subject hooks that write them)."""
+TTA_AFFINE_OPTIONS = ('samples', 'rotation', 'scale', 'shift', 'flip')
+
+
+class TtaAffineRecordHook(CorruptionRecordHook):
+    """``others.tta_affine``: ``<test_dir>/tta_affine.json`` -- the seed, the options and the V forward matrices -- written by the rank that writes
+    the run's output, as the corruption record is."""
+
+    def __init__(self, record):
+        super().__init__(record, 'tta_affine.json')
+
+
+def _tta_affine(context, world):
+    """``others.tta_affine: {samples: V, rotation: deg, scale: s, shift: px, flip: bool}`` (an rcu_amd extension, include/rcu_warp.h): test-time
+    augmentation over V seeded affine transforms, the first the identity (steps.affine_tta_draw under the YAML file's ``seed``, 0 without one),
+    composed with ``others.mc`` when that is set (V x T passes, with the weight-scaling pass), else alone in eval mode -- in place of the predict
+    step, followed by MultiPredictionSummary -> (batch steps, the record of ``tta_affine.json``), or None without the key.  One process; not
+    beside tta, agreement, mc_adaptive, density, laplace or knn (``_RULES``): a ValueError that names the key otherwise."""
+    others = context.config.others
+    if not hasattr(others, 'tta_affine'):
+        return None
+    _check_rules(others, world, 'tta_affine')
+    value = others.tta_affine
+    if not isinstance(value, dict):
+        value = dict(vars(value)) if hasattr(value, '__dict__') else value
+    if not isinstance(value, dict) or 'samples' not in value or set(value) - set(TTA_AFFINE_OPTIONS):
+        raise ValueError('others.tta_affine must be a mapping with samples and any of rotation, scale, shift, flip, got {!r}'.format(value))
+    flip = value.get('flip', False)
+    if not isinstance(flip, bool):
+        raise ValueError('others.tta_affine: flip must be true or false, got {!r}'.format(flip))
+    mc = int(getattr(others, 'mc', 0) or 0)
+    seed = 0 if context.config.seed is None else int(context.config.seed)
+    try:
+        step = steps.AffineTtaMcPredictStep(value['samples'], mc_steps=mc, seed=seed, rotation=value.get('rotation', 0.0),
+                                            scale=value.get('scale', 0.0), shift=value.get('shift', 0.0), flip=flip,
+                                            group_pixels=_other(context, 'group_pixels'), exact=bool(_other(context, 'exact', True)), ws_pass=mc > 0)
+    except (TypeError, ValueError) as e:
+        raise ValueError('others.tta_affine: {}'.format(e)) from None
+    record = dict(step.options, samples=step.transforms, seed=seed, mc=mc, matrices=step.matrices.tolist())
+    return [step, steps.MultiPredictionSummary()], record
+
+
+def _default_plan(context, world, density_fit=None, laplace_step=None, knn_step=None, affine_steps=None):
+    """The one decision of the default script: affine tta, density, k-NN, laplace, tta, adaptive, agreement, sharded mc, mc or plain -> (batch
+    steps, the entries they add to the assembled subject, the per-subject hooks that write them)."""
+    if affine_steps is not None:     # (the written maps keep their names)
+        return affine_steps, (), []
     if density_fit is not None:      # one deterministic pass per batch: under a multi-process launch the run is rank 0's alone (_run)
         return [steps.DensityPredictStep(density_fit)], ('density',), [DensityWriteHook()]
     if knn_step is not None:         # (the same)
@@ -988,13 +1042,15 @@ def _abandon_process_group(timeout_s=10.0):
 def test_default(dataset, config_file=None, config_id=None, device='cuda'):
     context, world = _context(device, config_file or _config_path(dataset, config_id))
     _check_others(context, 'default', world)
+    affine = _tta_affine(context, world)      # (refuses others.tta_affine beside the keys of its _RULES rows and under a multi-rank launch)
     density_fit = _density(context)      # (refuses others.density beside the keys that sample)
     knn = _knn(context)                  # (refuses others.knn beside them, beside others.density and beside others.laplace)
     laplace = _laplace(context)          # (refuses others.laplace beside them and beside others.density)
     corrupt_steps, corrupt_hooks = _corruption(context)
     test_steps, more_entries, subject_hooks = _default_plan(context, world, density_fit, None if laplace is None else laplace[0],
-                                                            None if knn is None else knn[0])
-    record_hooks = ([] if laplace is None else [LaplaceRecordHook(laplace[1])]) + ([] if knn is None else [KnnRecordHook(knn[1])])
+                                                            None if knn is None else knn[0], None if affine is None else affine[0])
+    record_hooks = (([] if laplace is None else [LaplaceRecordHook(laplace[1])]) + ([] if knn is None else [KnnRecordHook(knn[1])]) +
+                    ([] if affine is None else [TtaAffineRecordHook(affine[1])]))
     return _run(context, dataset, corrupt_steps + test_steps, WriteHook(link_inputs=dataset == 'isic'),
                 ('probabilities',) + more_entries if dataset == 'brats' else None, world,
                 startup_hooks=_temperature_hooks(context) + corrupt_hooks + record_hooks, subject_hooks=subject_hooks)

@@ -10,6 +10,7 @@ Mirrors (names, arguments, output keys, error behaviour):
   AleatoricMcPredictStep        extension (BASELINE config 'aleatoric + MC'): composition of the two above
   (both with logit_samples = S)  extension: test-time logit sampling, the predictive E_eps[softmax(mu + sigma eps)] (include/rcu.h)
   TtaMcPredictStep              extension: test-time augmentation (D4 transforms), alone or composed with MC dropout
+  AffineTtaMcPredictStep        extension: test-time augmentation with bilinear affine warps (include/rcu_warp.h), alone or with MC dropout
   BatchContext / TaskContext    common/trainloop/context.py:334-355
 A step is called as ``step(batch_context, task_context, context)``, reads
 ``batch_context.input['images']`` and writes torch tensors with the channel dim at 1 into
@@ -1639,6 +1640,278 @@ class TtaMcPredictStep(BatchStep):
                     probs.append(p if e == 0 else tta_transform(p, TTA_INVERSE[e]))
         finally:
             set_dropout_mode(model, is_train=False)
+        return torch.stack(probs)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# affine test-time augmentation (EXTENSION; include/rcu_warp.h "Affine test-time augmentation")
+# ------------------------------------------------------------------------------------------------------------------------------
+AFFINE_MAX_TRANSFORMS = _lib.RCU_WARP_MAX_MATRICES
+AFFINE_IDENTITY = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0))
+# D4 element code -> the integer-tap matrix whose warp is rcu_tta_transform's gather (codes 4-7 on square planes)
+TTA_AFFINE = (((1, 0, 0), (0, 1, 0)), ((1, 0, 0), (0, -1, 0)), ((-1, 0, 0), (0, 1, 0)), ((-1, 0, 0), (0, -1, 0)),
+              ((0, 1, 0), (1, 0, 0)), ((0, 1, 0), (-1, 0, 0)), ((0, -1, 0), (1, 0, 0)), ((0, -1, 0), (-1, 0, 0)))
+
+
+def _affine_array(mats, name='matrices'):
+    """Anything shaped ``[V, 2, 3]`` (or one ``[2, 3]``) -> float64 numpy ``[V, 2, 3]``; ValueError for other shapes, non-finite entries or
+    counts outside 1..64."""
+    import numpy as np
+    a = np.array(mats.detach().cpu().numpy() if torch.is_tensor(mats) else mats, dtype=np.float64)
+    if a.shape == (2, 3):
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] != (2, 3) or not 1 <= a.shape[0] <= AFFINE_MAX_TRANSFORMS:
+        raise ValueError('{} must be 1..{} matrices of 2 x 3 numbers, got shape {}'.format(name, AFFINE_MAX_TRANSFORMS, a.shape))
+    if not np.isfinite(a).all():
+        raise ValueError('{} must be finite, got {}'.format(name, a.tolist()))
+    return np.ascontiguousarray(a)
+
+
+def affine_matrix(rotation_deg=0.0, scale=1.0, shift_y=0.0, shift_x=0.0, flip=False):
+    """The output-to-source matrix (include/rcu_warp.h: float64 ``[2, 3]``, pixel units about the plane centre, rows (y, x)) of the input warp
+    "rotate by ``rotation_deg``, magnify by ``scale``, mirror the columns if ``flip``, shift": R(rotation) / scale, its second column negated for
+    ``flip``, the shifts in the last column."""
+    import numpy as np
+    scale = float(scale)
+    if not scale > 0.0 or not np.isfinite(scale):
+        raise ValueError('scale must be a positive finite number, got {!r}'.format(scale))
+    a = np.deg2rad(float(rotation_deg))
+    c, s = np.cos(a) / scale, np.sin(a) / scale
+    sign = -1.0 if flip else 1.0
+    m = np.array([[c, -s * sign, float(shift_y)], [s, c * sign, float(shift_x)]], dtype=np.float64)
+    return _affine_array(m, 'the matrix')[0]
+
+
+def affine_inverse(M):
+    """The matrix of the inverse map of ``M`` (float64 on the host): what ``accumulate_warped`` needs for samples whose inputs were warped with
+    ``M``.  ValueError for a singular matrix."""
+    import numpy as np
+    m = _affine_array(M, 'M')[0]
+    a, b, c, d = m[0, 0], m[0, 1], m[1, 0], m[1, 1]
+    det = a * d - b * c
+    if not np.isfinite(det) or abs(det) <= 1e-12 * max(abs(a), abs(b), abs(c), abs(d), 1e-300) ** 2:
+        raise ValueError('the matrix {} is singular'.format(m.tolist()))
+    lin = np.array([[d, -b], [-c, a]], dtype=np.float64) / det
+    out = np.empty((2, 3), dtype=np.float64)
+    out[:, :2] = lin
+    out[:, 2] = -(lin @ m[:, 2]) + 0.0      # (+ 0.0: no negative zero in the shifts)
+    return _affine_array(out, 'the inverse')[0]
+
+
+def _affine_uniform(seed, v, e):
+    """Uniform e (0..4) of transform v under ``seed``: ((x >> 11) + 0.5) * 2^-53 of x = SplitMix64(key + (8 v + e + 1) * 0x9E3779B97F4A7C15), the
+    key ``pass_seed(seed, 0)`` + 64 * 2^40 (the step below the mask keys of ``affine_pass_seed``; no other draw uses it)."""
+    from .corruption import _M64, _splitmix64
+    key = (pass_seed(seed, 0) + 64 * (1 << 40)) % (2 ** 63 - 1)
+    x = _splitmix64((key + (8 * int(v) + e + 1) * 0x9E3779B97F4A7C15) & _M64)
+    return ((x >> 11) + 0.5) * 2.0 ** -53
+
+
+def affine_tta_draw(seed, count, rotation=0.0, scale=0.0, shift=0.0, flip=False):
+    """The ``count`` (<= 64) forward matrices of a run seeded with ``seed`` -> float64 ``[count, 2, 3]``.  Transform 0 is the identity; transform
+    v >= 1 is a function of (seed, v) alone: the rotation uniform in +-``rotation`` degrees, log2 of the magnification uniform in
+    +-log2(1 + ``scale``), the two shifts uniform in +-``shift`` pixels, the mirror a fair coin when ``flip`` -- five uniforms from SplitMix64 of
+    the key, as ``corruption.bias_coefficients`` draws its coefficients."""
+    import math
+
+    import numpy as np
+    count = operator.index(count)
+    if not 1 <= count <= AFFINE_MAX_TRANSFORMS:
+        raise ValueError('samples must be in 1..{}, got {}'.format(AFFINE_MAX_TRANSFORMS, count))
+    rotation, scale, shift = float(rotation), float(scale), float(shift)
+    for name, value in (('rotation', rotation), ('scale', scale), ('shift', shift)):
+        if not (math.isfinite(value) and value >= 0.0):
+            raise ValueError('{} must be a finite number >= 0, got {!r}'.format(name, value))
+    out = np.empty((count, 2, 3), dtype=np.float64)
+    out[0] = AFFINE_IDENTITY
+    for v in range(1, count):
+        u = [2.0 * _affine_uniform(seed, v, e) - 1.0 for e in range(5)]
+        out[v] = affine_matrix(u[0] * rotation, 2.0 ** (u[1] * math.log2(1.0 + scale)), u[2] * shift, u[3] * shift, bool(flip) and u[4] < 0.0)
+    return out
+
+
+def affine_pass_seed(seed, v, job):
+    """Key of the library's mask draw for MC pass ``job`` (1..T) of the images warped with transform ``v`` (0..63): a function of (seed, v, pass)
+    alone.  Transform 0, the identity, has the key ``pass_seed(seed, job)`` of McPredictStep; transform v >= 1 adds (64 + v) * 2^40, i.e.
+    65 .. 127 steps of 2^40.  The D4 elements use steps 0..7 (``tta_pass_seed``), the corruption stages 16..23 (``corruption.corruption_seed``),
+    the k-NN bank draw step 32 (``knn.knn_seed``), and the Laplace and logit sampling a pass's own key (step 0): with passes within 1..2048 of
+    ``pass_seed(seed, 0)`` no key of one family equals a key of another, and everything is far below the modulus 2^63 - 1."""
+    v = operator.index(v)
+    if not 0 <= v < AFFINE_MAX_TRANSFORMS:
+        raise ValueError('transform index must be in 0..{}, got {}'.format(AFFINE_MAX_TRANSFORMS - 1, v))
+    return (pass_seed(seed, job) + ((64 + v) * (1 << 40) if v else 0)) % (2 ** 63 - 1)
+
+
+def _affine_device(mats, device):
+    return torch.from_numpy(_affine_array(mats)).to(device)
+
+
+def _warp_affine_device(x, m, out=None):
+    """``warp_affine`` with the matrices already on the device (float64 ``[V, 2, 3]``, checked when they were uploaded)."""
+    x = x.to(torch.float32).contiguous()
+    n, c, h, w = x.shape
+    if out is None:
+        out = torch.empty((m.shape[0], n, c, h, w), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (m.shape[0], n, c, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('out must be a contiguous float32 tensor of shape {}'.format((m.shape[0], n, c, h, w)))
+    _lib.check(_lib.load().rcu_warp_affine(_lib.ptr(x), n, c, h, w, _lib.ptr(m), m.shape[0], _lib.ptr(out), _lib.current_stream()))
+    return out
+
+
+def warp_affine(x, mats, out=None):
+    """``[N, C, H, W]`` float32 -> ``[V, N, C, H, W]``: x warped with each of the V matrices ``mats`` (include/rcu_warp.h rcu_warp_affine; host
+    numbers ``[V, 2, 3]`` or one ``[2, 3]``, refused unless finite), into a new tensor or ``out``."""
+    return _warp_affine_device(x, _affine_device(mats, x.device), out)
+
+
+def _accumulate_warped_device(inp, stats, m, from_probs=False):
+    """``accumulate_warped`` with the matrices already on the device (float64 ``[G, 2, 3]``, checked when they were uploaded)."""
+    inp = inp.to(torch.float32).contiguous()
+    if inp.dim() != 5 or tuple(inp.shape) != (m.shape[0], stats.n, stats.nb_classes, stats.height, stats.width):
+        raise ValueError('expected samples of shape {}, got {}'.format((m.shape[0], stats.n, stats.nb_classes, stats.height, stats.width),
+                                                                       tuple(inp.shape)))
+    flags = stats.flags | (_lib.RCU_MC_INPUT_PROBS if from_probs else 0)
+    _lib.check(_lib.load().rcu_mc_accumulate_warped(_lib.ptr(inp), _lib.ptr(stats.blob), stats.n, stats.height, stats.width, stats.nb_classes,
+                                                    flags, _lib.ptr(m), m.shape[0], _lib.current_stream()))
+    stats.count += m.shape[0]
+
+
+def accumulate_warped(inp, stats, mats, from_probs=False):
+    """Add the G samples ``inp`` ``[G, N, C, H, W]`` (logits, or probabilities with ``from_probs``) to the McStatistics ``stats`` of the N
+    canonical slices, each read through the warp with its matrix of ``mats`` (include/rcu_warp.h rcu_mc_accumulate_warped; pass the INVERSE of
+    the matrices the inputs were warped with; host numbers, refused unless finite).  ``stats.count`` grows by G."""
+    _accumulate_warped_device(inp, stats, _affine_device(mats, inp.device), from_probs)
+
+
+class AffineTtaMcPredictStep(BatchStep):
+    """EXTENSION -- test-time augmentation with small rotations, scalings, shifts and mirrors (Wang et al. 2019), alone or composed with MC
+    dropout.  The V = ``samples`` transforms are ``affine_tta_draw(seed, V, rotation, scale, shift, flip)`` -- transform 0 is the identity -- or the
+    explicit forward matrices ``matrices``.  Every batch runs on its images warped with each transform (bilinear, border mode: edge values are
+    replicated); each sample's softmax is read back through the inverse warp as it enters the canonical statistics (a resampled entropy is not the
+    entropy of the resampled probabilities, so nothing is folded afterwards), and ``MultiPredictionSummary`` finalises V x max(T, 1) samples.
+      ``mc_steps = 0``: eval mode, one pass per transform.  ``mc_steps = T``: T seeded dropout passes per transform, the factors of (transform v,
+      pass t) for the slice with global index s drawn at s under ``affine_pass_seed(seed, v, t)`` -- the identity's key is McPredictStep's.
+    A launch stacks G (transform, pass) pairs of the n images into one batch of G * n warped samples (rcu_warp_affine writes that layout), runs
+    ``model.forward`` on it and hands the logits to ``accumulate_warped``; G is ``pass_group_size``, and the plan is reserved for n * min(G, V x T)
+    samples before the first forward, so a sample's logits do not depend on the launches.  The launches alternate over ``lanes`` stream lanes
+    (default McPredictStep.LANES; ``UNet.forward(..., lane=)``), each lane adding into statistics of its own that are added into lane 0's at the
+    end.  ``exact`` (default; while V x T <= 2048): exact sums -- the outputs do not depend on the grouping or the lanes; otherwise the result is
+    that of the launch and lane order above.  ``ws_probabilities`` is the plain identity pass in eval mode."""
+
+    def __init__(self, samples=None, mc_steps=0, seed=None, rotation=0., scale=0., shift=0., flip=False, matrices=None, group_pixels=None,
+                 exact=True, do_mi=False, do_var=False, ws_pass=True, lanes=None) -> None:
+        super().__init__()
+        if int(mc_steps) < 0:
+            raise ValueError('mc_steps must be >= 0')
+        self.mc_steps = int(mc_steps)
+        self.seed = seed
+        self.lanes = McPredictStep.LANES if lanes is None else max(1, int(lanes))
+        if matrices is not None:
+            self.matrices = _affine_array(matrices, 'matrices')
+            if samples is not None and operator.index(samples) != len(self.matrices):
+                raise ValueError('samples is {} but {} matrices were given'.format(samples, len(self.matrices)))
+        else:
+            if samples is None or isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= AFFINE_MAX_TRANSFORMS:
+                raise ValueError('samples must be an integer in 1..{}, got {!r}'.format(AFFINE_MAX_TRANSFORMS, samples))
+            if seed is None and samples > 1:
+                raise ValueError('seed is needed to draw the transforms (or pass matrices)')
+            self.matrices = affine_tta_draw(0 if seed is None else seed, samples, rotation, scale, shift, flip)
+        try:
+            self.inverses = _affine_array([affine_inverse(m) for m in self.matrices], 'matrices')
+        except ValueError as e:
+            raise ValueError('matrices: {}'.format(e)) from None
+        self.options = dict(rotation=float(rotation), scale=float(scale), shift=float(shift), flip=bool(flip))
+        self.transforms = len(self.matrices)
+        self.samples = self.transforms * max(self.mc_steps, 1)
+        self.group_pixels = McPredictStep.GROUP_PIXELS if group_pixels is None else group_pixels
+        self.exact = bool(exact) and self.samples <= _lib.RCU_MC_EXACT_MAX_PASSES
+        self.do_mi, self.do_var = do_mi, do_var
+        self.ws_pass = ws_pass
+
+    def __call__(self, batch_context, task_context, context) -> None:
+        _check_context(context)
+        model = context.model
+        if not isinstance(model, model_mod.UNet):
+            raise ValueError('model: AffineTtaMcPredictStep needs a rcu_amd.model.UNet (the warps run on librcu_hip), got {}'.format(
+                type(model).__name__))
+        if model.sigma_out:
+            raise ValueError('model: AffineTtaMcPredictStep does not take a sigma-head model (sigma_out)')
+        images = _images_to_device(batch_context, context)
+        n, _, h, w = images.shape
+        k = first_sample_of(batch_context, n)
+        seed = self.seed
+        if seed is None and self.mc_steps > 0:
+            seed = int(torch.randint(2 ** 31 - 1, (1,)).item())
+        ws = torch.empty((n, model.nb_classes, h, w), device=images.device, dtype=torch.float32) if self.ws_pass else None
+        if ws is not None:
+            batch_context.output['ws_probabilities'] = ws
+        batch_context.output['multi_probabilities'] = self._fused(model, images, self.do_mi, self.do_var, k, seed, ws)
+
+    def _chunks(self, model, images, lanes=1):
+        """The launches of a batch: (first pair, pairs) of at most G (transform, pass) pairs, in pair order; reserves the canonical plan --
+        n * min(G, V x T) samples, not a function of the launches made -- on every lane."""
+        n, _, h, w = images.shape
+        pairs = self._pairs()
+        group = pass_group_size(model, n, h, w, self.group_pixels)
+        for lane in range(lanes):
+            model.reserve(h, w, n * min(group, len(pairs)), lane)
+        return [(b, pairs[b:b + group]) for b in range(0, len(pairs), group)]
+
+    def _pairs(self):
+        return [(v, t) for v in range(self.transforms) for t in range(1, max(self.mc_steps, 1) + 1)]
+
+    def _pair_matrices(self, device):
+        """The forward and the inverse matrix of every pair on the device, ``[2, V x T, 2, 3]``: one upload per batch on the caller's stream (a
+        pageable upload inside a launch would make the host wait for that lane's queue), and a launch's matrices are a slice of it."""
+        index = [v for v, _ in self._pairs()]
+        return _affine_device(self.matrices[index], device), _affine_device(self.inverses[index], device)
+
+    def _logits(self, model, images, forward, first, chunk, first_sample, seed, lane=0):
+        """The logits ``[G, n, C, H, W]`` of one launch: the n images warped with the transforms of the G pairs of ``chunk``, one forward."""
+        n, _, h, w = images.shape
+        x = _warp_affine_device(images, forward[first:first + len(chunk)]).view(len(chunk) * n, images.shape[1], h, w)
+        masks = None
+        if self.mc_steps > 0:
+            masks = HipEngine(model).seeded_masks(images, [affine_pass_seed(seed, v, t) for v, t in chunk], first_sample)
+        return model(x, masks, lane=lane).view(len(chunk), n, model.nb_classes, h, w)
+
+    def _fused(self, model, images, do_mi, do_var, first_sample, seed, ws=None):
+        engine = HipEngine(model, do_mi, do_var, self.exact)
+        set_dropout_mode(model, is_train=False)
+        stats = engine.side_statistics(images)
+        lanes = StreamLanes(images.device, min(self.lanes, self.samples))
+        chunks = self._chunks(model, images, lanes.count)
+        forward, back = self._pair_matrices(images.device)
+        lanes.begin(stats, lambda: engine.side_statistics(images), inputs=(images, forward, back))
+        if ws is not None:
+            engine.ws_pass(images, ws)          # on the caller's stream, beside the side lanes' first launches
+
+        def launch(st, lane, first, chunk):
+            logits = self._logits(model, images, forward, first, chunk, first_sample, seed, lane)
+            _accumulate_warped_device(logits, st, back[first:first + len(chunk)])
+
+        for first, chunk in chunks:
+            lanes.run(lambda st, lane, first=first, chunk=chunk: launch(st, lane, first, chunk))
+        if lanes.count > 1:
+            lanes.end(engine.merge)
+
+        def recipe(mi, var, materialize=False):
+            if materialize:
+                return self._materialized(model, images, first_sample, seed)
+            return self._fused(model, images, mi, var, first_sample, seed)
+
+        stats.recipe = recipe
+        return stats
+
+    def _materialized(self, model, images, first_sample, seed):
+        """The V x T probability volumes ``[V*T, N, C, H, W]`` warped back to the canonical grid, transform-major."""
+        set_dropout_mode(model, is_train=False)
+        forward, back = self._pair_matrices(images.device)
+        probs = []
+        for first, chunk in self._chunks(model, images):
+            logits = self._logits(model, images, forward, first, chunk, first_sample, seed)
+            for g in range(len(chunk)):
+                probs.append(_warp_affine_device(softmax(logits[g]), back[first + g:first + g + 1])[0])
         return torch.stack(probs)
 
 
