@@ -84,7 +84,10 @@ typedef struct rcu_unet_options {
                                  work items fill the chip's rounds of workgroups (pick_config) --; 2: wherever its tiles fit, whatever the fill (parity
                                  tests on small batches); 0: F(2x2,3x3) only; 3: F(4x4,3x3) for the units with >= 64 output channels only (the round-2 selection) */
     int32_t conv_first;       /* 1 (default): the unpadded first-unit kernel; 0: the tiled kernel + channels-last input copy */
-    int32_t act_layout;       /* 0 (default): channel-blocked activations between Winograd kernels; 1: channels-last everywhere */
+    int32_t act_layout;       /* 0 (default): channel-blocked activations between Winograd kernels, and the pixel-pair form of that layout
+                                 ([N][C/8][H][W/2][4 channel pairs][2 pixels][2 channels]) for the tensors only F(4x4,3x3) kernels touch on unpadded
+                                 levels; 1: channels-last everywhere; 2: channel-blocked, never paired (A/B measurements, bitwise tests).  A layout is
+                                 an addressing choice: the results have the same bits under every value */
     int32_t fuse_head;        /* 1 (default): 1x1 classifier + softmax + statistics in conv_cls.0's epilogue where the shapes allow;
                                  0: the standalone head kernel (also settable per handle at run time: rcu_unet_set_fuse_head) */
     int32_t head_winograd4;   /* 1 (default): conv_cls.0 -- with the classifier fused into its epilogue or not -- takes F(4x4,3x3) where the 32x32 tile
@@ -185,6 +188,10 @@ typedef struct rcu_layer_info {
 } rcu_layer_info;
 int rcu_unet_num_layers(const rcu_unet* h);
 int rcu_unet_layer_info(const rcu_unet* h, int layer, rcu_layer_info* out);
+/* The activation layouts the planner chose (rcu_unet_options.act_layout) for the tensors of layer `layer`: its source, its second source (the
+ * skip tensor of a cat-free decoder unit), its output and its pooled output; -1 where the layer has no such tensor.  Any pointer may be NULL. */
+enum { RCU_LAYOUT_NHWC = 0, RCU_LAYOUT_BLOCKED = 1, RCU_LAYOUT_PAIRED = 2 };
+int rcu_unet_layer_layouts(const rcu_unet* h, int layer, int32_t* src1, int32_t* src2, int32_t* out, int32_t* pooled);
 /* Runs only conv layer `layer` on the handle's current workspace contents (benchmark aid; layer 0 then reads the
    workspace's channels-last input copy, which a forward pass only fills when its first-layer kernel does not read the
    caller's NCHW input directly -- timing only). */

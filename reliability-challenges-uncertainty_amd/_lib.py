@@ -106,6 +106,7 @@ SIGNATURES = {
     'rcu_postnet_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'rcu_unet_num_layers': (c_int, [c_void_p]),
     'rcu_unet_layer_info': (c_int, [c_void_p, c_int, POINTER(LayerInfo)]),
+    'rcu_unet_layer_layouts': (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     'rcu_unet_run_layer': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'rcu_unet_profile_begin': (c_int, [c_void_p, c_int]),
     'rcu_unet_profile_collect': (c_int, [c_void_p, POINTER(c_double), POINTER(c_int)]),

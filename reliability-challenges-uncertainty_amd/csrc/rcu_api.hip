@@ -113,7 +113,7 @@ static int make_plan(const rcu_unet_desc* desc, const rcu_unet_options* opts, co
     if (opts) {
         o = *opts;
         if ((o.conv_winograd | 1) != 1 || (o.conv_winograd4 < 0 || o.conv_winograd4 > 3) ||
-            (o.conv_first | 1) != 1 || (o.act_layout | 1) != 1 || (o.fuse_head | 1) != 1 || (o.head_winograd4 | 1) != 1 || (o.pad_levels | 1) != 1 ||
+            (o.conv_first | 1) != 1 || o.act_layout < 0 || o.act_layout > 2 || (o.fuse_head | 1) != 1 || (o.head_winograd4 | 1) != 1 || (o.pad_levels | 1) != 1 ||
             (o.upconv_winograd4 < 0 || o.upconv_winograd4 > 2))
             return fail(RCU_ERR_INVALID, "rcu_unet_create_with: bad rcu_unet_options value");
     }
@@ -393,12 +393,10 @@ static int run_layer(rcu_unet* h, int layer, int n, const float* masks, hipStrea
     a.N = n; a.H = gh; a.W = gw;
     const PlanTensor& tsrc = p.tensors[L.t_src1];
     const PlanTensor& tout = p.tensors[L.t_out];
-    const int os = L.upsample ? 2 : 1;
     if (cfg_handles_padding(L.cfg)) {
         // padded level on either side (ConvArgs::part): the tiles walk the allocated grid, the stores keep to the real image, the output and
         // pooled tensors have the extents of their own levels (the head unit's output: exactly the real image)
-        const bool pool_differs = L.t_pool >= 0 && (p.tensors[L.t_pool].H != gh / 2 || p.tensors[L.t_pool].W != gw / 2);
-        if (tsrc.padded() || tout.H != os * gh || tout.W != os * gw || pool_differs) {
+        if (layer_runs_part(p, L)) {
             a.part = 1;
             a.Hr = L.upsample ? 2 * (L.H / 2) : L.H;
             a.Wr = L.upsample ? 2 * (L.W / 2) : L.W;
@@ -440,6 +438,9 @@ static int run_layer(rcu_unet* h, int layer, int n, const float* masks, hipStrea
         strides(tsrc, a.in_pix_bytes, a.in_chunk_bytes);
         strides(tout, a.out_pix_bytes, a.out_chunk_bytes);
         if (L.t_pool >= 0) strides(p.tensors[L.t_pool], a.pool_pix_bytes, a.pool_chunk_bytes);
+        // a paired tensor has the strides of the blocked one (assign_layouts: both sources alike, output and pooled output alike)
+        a.in_paired = tsrc.paired ? 1 : 0;
+        a.out_paired = tout.paired ? 1 : 0;
     }
     a.src1_bytes = (uint32_t)std::min<size_t>(tsrc.floats_per_slice * (size_t)n * 4, 0xFFFFFFFFu);
     a.src2_bytes = L.t_src2 >= 0 ? (uint32_t)std::min<size_t>(p.tensors[L.t_src2].floats_per_slice * (size_t)n * 4, 0xFFFFFFFFu) : 0u;
@@ -690,6 +691,22 @@ extern "C" int rcu_unet_layer_info(const rcu_unet* h, int layer, rcu_layer_info*
 {
     if (!h || !out || layer < 0 || layer >= (int)h->plan.layers.size()) return fail(RCU_ERR_INVALID, "bad layer index");
     plan_layer_info(h->plan, h->d, layer, out);
+    return RCU_OK;
+}
+
+extern "C" int rcu_unet_layer_layouts(const rcu_unet* h, int layer, int32_t* src1, int32_t* src2, int32_t* out, int32_t* pooled)
+{
+    if (!h || layer < 0 || layer >= (int)h->plan.layers.size()) return fail(RCU_ERR_INVALID, "bad layer index");
+    const PlanLayer& L = h->plan.layers[layer];
+    auto layout = [&](int t) -> int32_t {
+        if (t < 0) return -1;
+        const PlanTensor& T = h->plan.tensors[t];
+        return T.paired ? RCU_LAYOUT_PAIRED : T.blocked ? RCU_LAYOUT_BLOCKED : RCU_LAYOUT_NHWC;
+    };
+    if (src1) *src1 = layout(L.t_src1);
+    if (src2) *src2 = layout(L.t_src2);
+    if (out) *out = layout(L.t_out);
+    if (pooled) *pooled = layout(L.t_pool);
     return RCU_OK;
 }
 

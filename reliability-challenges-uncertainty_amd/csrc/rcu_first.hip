@@ -23,6 +23,12 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// exchange with the neighbouring lane (lane ^ 1): DPP quad_perm [1,0,3,2]
+__device__ __forceinline__ float swap_adjacent(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
+}
+
 constexpr int FIRST_TH = 8, FIRST_TW = 32, FIRST_THREADS = 256;
 constexpr int FIRST_HR = FIRST_TH + 2, FIRST_HC = FIRST_TW + 2;   // halo tile
 constexpr int FIRST_TILE_FLOATS = 3072;                          // packed [tap][32 couts][8 channels], padded (rcu_wpack.h)
@@ -123,13 +129,26 @@ __global__ __launch_bounds__(FIRST_THREADS) void conv3x3_first_kernel(const Conv
                 const int r = 2 * wave + (seg >> 1), c0 = 16 * (seg & 1);
                 if (y0 + r >= Hr || x0 + c0 + n16 >= Wr) continue;   // beyond the real image (padded level): the zeros there are never written
                 // (sample, pixel, channel b * 16 + 4 g): NHWC or blocked [C/8][H][W][8], see ConvArgs
-                char* const op = reinterpret_cast<char*>(a.out) + (size_t)ns * a.H * a.W * a.CoutP * 4 +
-                                 (size_t)((y0 + r) * a.W + x0 + c0 + n16) * a.out_pix_bytes + (size_t)(g >> 1) * a.out_chunk_bytes + (g & 1) * 16;
+                // paired: unit 2 (g & 1) + (pixel parity) of the pixel pair's 64 bytes
+                const int px = (y0 + r) * a.W + x0 + c0 + n16;
+                char* const op = reinterpret_cast<char*>(a.out) + (size_t)ns * a.H * a.W * a.CoutP * 4 + (size_t)(g >> 1) * a.out_chunk_bytes +
+                                 (a.out_paired ? (size_t)(px >> 1) * 64 + (size_t)(2 * (g & 1) + (px & 1)) * 16
+                                               : (size_t)px * a.out_pix_bytes + (size_t)(g & 1) * 16);
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
                     f32x4 v = acc[seg][b] * scale[b] + shift[b];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], floor_v);
+                    if (a.out_paired) {
+                        // paired output (rcu_kernels.h; never a padded level, so no lane has left the loop): the lane holds channel pairs kq = 2 (g & 1),
+                        // 2 (g & 1) + 1 of its pixel and trades with the lane of the other pixel of the pair (n16 ^ 1): the even pixel's lane ends up
+                        // with unit kq = 2 (g & 1) of the pair's 64 bytes -- both pixels x two channels --, the odd one's with the unit behind it.
+                        // The 32 lanes (16 pixels, g & 1) of a chunk still write 512 contiguous bytes.
+                        const bool odd = (n16 & 1) != 0;
+                        const float s0 = odd ? v[0] : v[2], s1 = odd ? v[1] : v[3];
+                        const float r0 = swap_adjacent(s0), r1 = swap_adjacent(s1);
+                        v = odd ? f32x4{r0, r1, v[2], v[3]} : f32x4{v[0], v[1], r0, r1};
+                    }
                     *reinterpret_cast<f32x4*>(op + (size_t)(2 * b) * a.out_chunk_bytes) = v;
                 }
             }
@@ -148,8 +167,9 @@ hipError_t launch_first(const ConvArgs& a, hipStream_t stream)
     return hipGetLastError();
 }
 
-// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: reads the caller's NCHW input or the NHWC copy, writes either layout; 9 taps
-const ConvConfigInfo kFirstInfo = {1, FIRST_TH, FIRST_TW, 32, 8, 9, "conv3x3_first<T8x32,K36>", 8, 0, {ConvFamily::First, false, false, true, true, 1, 9.0}};
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults, reads_paired, writes_paired: reads the caller's NCHW input or the NHWC copy,
+// writes any layout; 9 taps
+const ConvConfigInfo kFirstInfo = {1, FIRST_TH, FIRST_TW, 32, 8, 9, "conv3x3_first<T8x32,K36>", 8, 0, {ConvFamily::First, false, false, true, true, 1, 9.0, false, true}};
 
 }  // namespace
 
@@ -159,7 +179,7 @@ const ConvConfigInfo& first_config_info() { return kFirstInfo; }
 hipError_t launch_conv_first(const ConvArgs& a, hipStream_t stream)
 {
     if (a.C1 != 8 || a.C2 != 0 || a.H % FIRST_TH != 0 || a.W % FIRST_TW != 0 || a.pooled != nullptr || a.mask2 != nullptr ||
-        (a.CoutP != 32 && a.CoutP != 64))
+        (a.CoutP != 32 && a.CoutP != 64) || (a.out_paired && (a.part || a.out_pix_bytes != 32u)))
         return hipErrorInvalidValue;
     const bool wide = a.cin_real > 4;
     if (a.CoutP == 32) return wide ? launch_first<2, 2>(a, stream) : launch_first<1, 2>(a, stream);

@@ -45,8 +45,13 @@ inline int check_batch(const std::string& f, size_t n, int n_volumes, int max_vo
 //   blocked  [N][C/8][H][W][8]: a pixel's 8-channel group (the Cin chunk of the Winograd kernels) is 32 contiguous bytes and
 //            the groups of neighbouring pixels follow each other, so an LDS-DMA instruction that stages 8 channels of 32..64
 //            pixels touches 8..16 whole 128-byte lines instead of 32..64 quarter lines (Winograd kernels + rcu_first.hip only)
-// Both are addressed as  sample * (H W C 4) + chunk * chunk_bytes + (y W + x) * pix_bytes + (c mod 8) * 4  with
+//   paired   [N][C/8][H][W/2][4 channel pairs][2 pixels][2 channels]: the blocked layout with the 64 bytes of each aligned pixel pair permuted, so
+//            that a lane of the F(4x4,3x3) epilogues -- two couts of adjacent pixels -- stores 16 contiguous bytes without trading with its
+//            neighbour (rcu_wino4_geom.h; rcu_wino4.hip, rcu_wino4_up.hip, rcu_first.hip only; even W, unpadded levels)
+// NHWC and blocked are addressed as  sample * (H W C 4) + chunk * chunk_bytes + (y W + x) * pix_bytes + (c mod 8) * 4  with
 //   NHWC: pix_bytes = 4 C, chunk_bytes = 32;   blocked: pix_bytes = 32, chunk_bytes = 32 H W.
+// A paired tensor has the strides of the blocked one and in_paired / out_paired set: inside a chunk plane
+//   ((y W + x) >> 1) * 64 + ((c mod 8) >> 1) * 16 + (x & 1) * 8 + (c & 1) * 4.
 struct ConvArgs {
     const float* src1;   // [N][H][W][C1]   first  K-range (channels [0, C1))
     const float* src2;   // [N][H][W][C2]   second K-range (cat-free decoder), may be null (C2 = 0)
@@ -97,6 +102,8 @@ struct ConvArgs {
     size_t head_V;         // voxels of one pass = images * H * W
     int head_passes;       // MC passes in this launch: sample t * head_images + i is image i (pass groups); its statistics entry is i's
     int head_images;
+    int in_paired;         // the sources (both alike) are paired tensors
+    int out_paired;        // `out` and `pooled` (both alike) are paired tensors
 };
 
 enum ConvConfig {
@@ -159,6 +166,8 @@ struct ConvFamilyTraits {
     bool part;            // store side honours ConvArgs::part: may read or write the tensors of a padded level
     int weight_sets;      // weight-tile sets per (Cin chunk, cout tile): 1, 2 or 4 (one per parity class or pair of classes)
     double mults;         // multiplications executed per pixel of the walked grid and (cin, cout) pair
+    bool reads_paired = false;    // takes its sources in the paired layout too (whole tiles of unpadded levels)
+    bool writes_paired = false;   // ... its output and pooled output
 };
 struct ConvConfigInfo {
     int TS, TH, TW, BN, KC, TAPS;

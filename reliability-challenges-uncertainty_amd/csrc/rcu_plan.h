@@ -36,9 +36,10 @@ struct PlanTensor {
     int Hr = 0, Wr = 0;       // real extent; smaller on a padded level (plan_unet): the pixels beyond it hold zeros nobody writes
     bool padded() const { return H != Hr || W != Wr; }
     bool blocked = false;     // [N][C/8][H][W][8] instead of NHWC (rcu_kernels.h, ConvArgs): decided per tensor by assign_layouts
+    bool paired = false;      // blocked, with the 64 bytes of each aligned pixel pair permuted (rcu_kernels.h): F(4x4,3x3) kernels on both sides only
     bool operator==(const PlanTensor& o) const
     {
-        return floats_per_slice == o.floats_per_slice && H == o.H && W == o.W && Hr == o.Hr && Wr == o.Wr && cp == o.cp && blocked == o.blocked &&
+        return floats_per_slice == o.floats_per_slice && H == o.H && W == o.W && Hr == o.Hr && Wr == o.Wr && cp == o.cp && blocked == o.blocked && paired == o.paired &&
                zero_fill == o.zero_fill;
     }
 };
@@ -63,6 +64,8 @@ int plan_unet(const rcu_unet_desc& d, const rcu_unet_options& opt, Plan* out);
 
 // the kernels whose store side honours ConvArgs::part (a padded level)
 bool cfg_handles_padding(int cfg);
+// does layer L run in the ConvArgs::part form: a padded level on either side, or output / pooled tensors with extents of their own
+bool layer_runs_part(const Plan& p, const PlanLayer& L);
 // the plan's last unit can take the classifier into its epilogue: two classes, no sigma twin, one 32-cout Winograd tile of either family
 bool head_fusable(const Plan& p, const rcu_unet_desc& d);
 // the rcu_layer_info of layer `layer` (0 <= layer < p.layers.size())

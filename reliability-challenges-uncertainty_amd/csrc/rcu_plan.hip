@@ -216,9 +216,55 @@ bool cfg_handles_padding(int cfg) { return conv_config_info(cfg).family.part; }
 // producers and consumers are Winograd kernels (rcu_first.hip as a producer), except the network input, the head unit's output
 // (head_kernel reads channels-last) and -- when the caller wants rcu_unet_features -- the feature tensor.  The two sources of a
 // cat-free decoder unit share one layout.  rcu_unet_options.act_layout = 1 keeps everything channels-last (A/B tests).
+// One level further, the paired layout (rcu_kernels.h): a blocked tensor of even width all of whose producers and consumers are F(4x4,3x3) kernels
+// not in the ConvArgs::part form (conv units with or without the fused head, up-convolutions; rcu_first.hip as a producer).  The two sources of a
+// cat-free unit share it, and so do a unit's output and pooled output.  act_layout = 2 stops at blocked.
+bool layer_runs_part(const Plan& p, const PlanLayer& L)
+{
+    if (!cfg_handles_padding(L.cfg)) return false;
+    const PlanTensor &tsrc = p.tensors[L.t_src1], &tout = p.tensors[L.t_out];
+    const int os = L.upsample ? 2 : 1;
+    const bool pool_differs = L.t_pool >= 0 && (p.tensors[L.t_pool].H != L.gh / 2 || p.tensors[L.t_pool].W != L.gw / 2);
+    return tsrc.padded() || tout.H != os * L.gh || tout.W != os * L.gw || pool_differs;
+}
+
+static void assign_paired(Plan& p, const rcu_unet_options& opt)
+{
+    for (PlanTensor& t : p.tensors) t.paired = opt.act_layout == 0 && t.blocked && !t.padded() && t.W % 2 == 0;
+    for (bool changed = true; changed;) {
+        changed = false;
+        auto clear = [&](int t) {
+            if (t >= 0 && p.tensors[t].paired) {
+                p.tensors[t].paired = false;
+                changed = true;
+            }
+        };
+        for (const PlanLayer& L : p.layers) {
+            const ConvFamilyTraits& family = conv_config_info(L.cfg).family;
+            const bool part = layer_runs_part(p, L);
+            if (!family.reads_paired || part) {
+                clear(L.t_src1);
+                clear(L.t_src2);
+            }
+            if (!family.writes_paired || part) {
+                clear(L.t_out);
+                clear(L.t_pool);
+            }
+            if (L.t_src2 >= 0 && p.tensors[L.t_src1].paired != p.tensors[L.t_src2].paired) {
+                clear(L.t_src1);
+                clear(L.t_src2);
+            }
+            if (L.t_pool >= 0 && p.tensors[L.t_out].paired != p.tensors[L.t_pool].paired) {
+                clear(L.t_out);
+                clear(L.t_pool);
+            }
+        }
+    }
+}
+
 static void assign_layouts(Plan& p, const rcu_unet_desc& d, const rcu_unet_options& opt)
 {
-    const bool on = opt.act_layout == 0;
+    const bool on = opt.act_layout != 1;
     for (PlanTensor& t : p.tensors) t.blocked = on && t.cp % 8 == 0 && !t.zero_fill;
     p.tensors[p.t_input].blocked = false;
     p.tensors[p.t_head].blocked = false;
@@ -247,6 +293,7 @@ static void assign_layouts(Plan& p, const rcu_unet_desc& d, const rcu_unet_optio
             }
         }
     }
+    assign_paired(p, opt);
 }
 
 // Builds layers and tensors of `p` for the level extents `level_ext` (plan_unet: the real extents first, then padded ones).

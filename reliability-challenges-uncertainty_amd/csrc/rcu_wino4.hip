@@ -28,106 +28,17 @@
 //     two-dword slots of the 64 banks: 2-way, the minimum for 8-dword positions.
 //   * D: lane (n = lane & 15, g = lane >> 4) holds the four horizontally adjacent tiles 4g .. 4g+3 of one tile row (4 x 16
 //     pixels) for couts (2n, 2n+1): output transform A^T M A (100 operations per tile and cout), epilogue and 2x2 max-pool are
-//     lane-local; neighbouring lanes trade pixel columns by DPP so that every store writes 16 bytes.
+//     lane-local.  Every store writes 16 bytes: into a paired tensor (rcu_wino4_geom.h) the lane's own two couts of two adjacent pixels; into
+//     a blocked or channels-last one four couts of one pixel, for which neighbouring lanes trade pixel columns by DPP.
 //   * staging by LDS-DMA only, double-buffered chunk pipeline running across the tiles of a workgroup, buffer-resource zero
 //     padding: as rcu_wino.hip.
 #include "rcu_wino_common.h"
 #include "rcu_head_common.h"
+#include "rcu_wino4_geom.h"
 
 namespace rcu {
 
-// Workgroup tile: WS slice groups x WR block rows of MFMA row blocks; a block = SB slices x BR tile rows x BC tile columns = 16
-// tiles of 4x4 pixels spanning the tile's full width.
-// FULLW: the tile spans the image's width (checked by the launcher), so the halo columns are zero padding and are not staged at all:
-// the LDS image holds TW positions per row and the lanes of the first / last tile column read their outer patch column from a region of zeros (ZERO_DW).
-// What it buys is LDS: eight slices of 8x16 pixels (the 24x16 level) fit the 160 KB only without the two halo columns.
-// FOLD: 12x8-pixel images (the BraTS bottom level).  A slice is 3 x 2 = 6 tiles of 4x4 pixels, and the workgroup's 64 tile slots -- slot k = wave
-// k / 16, MFMA row k % 16 -- take the tiles of FOLD_TS = 10 consecutive slices one behind the other: slot k < 60 holds tile ((k % 6) / 2, k % 2) of
-// slice k / 6, slots 60..63 are idle -- their MFMA rows read slice 9's last patch again and are never stored.  60 of 64 slots work: 2.25 x 64/60 =
-// 2.4 multiplications per pixel against F(2x2,3x3)'s 4.  (Until the tile held ten slices a slice had the 8 slots of the S8 block geometry the tile
-// descends from, two of them idle: 48 of 64.)  A slice's tiles do not line up with the waves or with a lane's four accumulator rows any more: wave 0
-// holds slices 0, 1 and four tiles of slice 2, and the four slots 4j .. 4j+3 (j = 4 wave + g) of D-side lane (n, g) are tiles 0-3 of a slice
-// (j % 3 = 0), tiles 2-5 (j % 3 = 2), or tiles 4, 5 of one slice and 0, 1 of the next (j % 3 = 1); j = 15 is idle.  So slice, Dropout2d factor and
-// store offset are per tile in this geometry, derived in the epilogue (wino4_epilogue), not per lane.
-template <int SB_, int BR_, int BC_, int WS_, int WR_, bool FULLW_ = false, bool FOLD_ = false>
-struct Wino4Tile {
-    static constexpr int SB = SB_, BR = BR_, BC = BC_, WS = WS_, WR = WR_;
-    static constexpr bool FULLW = FULLW_, FOLD = FOLD_;
-    static constexpr int FOLD_TS = 10;                                       // slices of a folded tile: 60 of the 64 slots
-    static constexpr int TS = FOLD ? FOLD_TS : SB * WS, TH = FOLD ? 12 : 4 * BR * WR, TW = FOLD ? 8 : 4 * BC;
-    static constexpr int TCOLS = FOLD ? 2 : BC;                              // tile columns of the workgroup tile
-    static constexpr int BN = 32, KC = 8, THREADS = 256, WAVES = 4, NPOS = 36;
-    static constexpr int XCOLS = FULLW ? TW : TW + 2;                        // staged pixel columns per row: x = -1 .. TW, or 0 .. TW - 1
-    static constexpr int PITCH = (XCOLS + 3) / 4 * 4;                        // positions per halo row, a multiple of 4
-    static constexpr int SLICE_POS = ((TH + 2) * PITCH + 15) / 16 * 16;      // positions per slice image, a multiple of 16
-    static constexpr int A_POS = 2 * TS * SLICE_POS;                         // 16-byte units: [slice][halo row][position][channel half]
-    static constexpr int A_PIECES = (A_POS + 63) / 64;
-    static constexpr int NA = (A_PIECES + WAVES - 1) / WAVES;
-    static constexpr int A_DW = A_PIECES * 256;
-    static constexpr int W_DW = NPOS * 4 * BN * 2;                           // [p][channel pair][cout][2]
-    static constexpr int W_PIECES = W_DW / 256;
-    static constexpr int NW = (W_PIECES + WAVES - 1) / WAVES;
-    // FULLW: row slots at the row pitch behind the image and the weights of EACH chunk buffer that hold zeros for the whole kernel (cleared once,
-    // never a target of the LDS-DMA: the pieces end at A_DW + W_DW).  The lanes of the first / last tile column read their outer patch column there.
-    // One region per buffer, at the same offset from the buffer's base, because a lane's column addresses are offsets from that base; whole 1 KB
-    // pieces, so the second buffer keeps the alignment of the first.  Four row slots serve the six patch rows: rows 0..3 and rows 4..5 have an
-    // address register each (aCol), and the second one points four rows lower (the 8x32 tile of four slices fills the 160 KB exactly with them).
-    static constexpr int ZERO_ROWS = 4;
-    static constexpr int ZERO_DW = FULLW ? (ZERO_ROWS * PITCH * 8 + 255) / 256 * 256 : 0;
-    static constexpr int ZERO_OFF = A_DW + W_DW;                             // dword offset of the region inside a buffer
-    static constexpr int BUF_DW = A_DW + W_DW + ZERO_DW;
-    static constexpr int LDS_BYTES = 2 * BUF_DW * 4;
-    static_assert(SB * BR * BC == 16 && WS * WR == WAVES && BC % 4 == 0, "block geometry");
-    static_assert(!FOLD || (SB == 2 && BR == 2 && BC == 4 && WS == 4 && WR == 1 && FULLW), "the folded 12x8 geometry descends from the S8 block");
-    static_assert(!FOLD || 6 * TS <= 16 * WAVES, "a folded slice is 6 tiles");
-    static_assert(W_DW % 256 == 0 && LDS_BYTES <= 160 * 1024, "LDS");
-    // wave -> (first slice of its block inside the tile, top pixel row of its block inside the slice tile)
-    static __device__ __forceinline__ void block_origin(int wave, int& s, int& y)
-    {
-        s = (wave / WR) * SB;
-        y = (wave % WR) * (4 * BR);
-    }
-    // tile m of a block -> (slice inside the block, tile row, tile column)
-    static __device__ __forceinline__ void tile_of(int m, int& sb, int& tr, int& tc)
-    {
-        sb = m / (BR * BC);
-        tr = (m / BC) % BR;
-        tc = m % BC;
-    }
-    // MFMA row m of wave `wave` -> (slice inside the workgroup tile, top pixel row of the 4x4 tile inside the slice tile, tile column)
-    static __device__ __forceinline__ void row_tile(int wave, int m, int& s, int& y, int& tc)
-    {
-        if constexpr (FOLD) {
-            const int k = min(16 * wave + m, 6 * TS - 1);   // the idle slots read the last tile's patch
-            s = k / 6;
-            const int t = k - 6 * s;
-            y = 4 * (t >> 1);
-            tc = t & 1;
-        } else {
-            int bs, by, sb, tr;
-            block_origin(wave, bs, by);
-            tile_of(m, sb, tr, tc);
-            s = bs + sb;
-            y = by + 4 * tr;
-        }
-    }
-    // FOLD: does MFMA row m of wave `wave` hold a tile?
-    static __device__ __forceinline__ bool row_works(int wave, int m) { return !FOLD || 16 * wave + m < 6 * TS; }
-    static __device__ __forceinline__ int swizzle(int x, int s, int R) { return (((x >> 3) ^ s) & 1) | (((R >> 2) & 1) << 1); }
-};
-
-template <class T>
-__device__ __forceinline__ uint32_t wino4_slot_geometry(int j, int wave, int lane)
-{
-    const int f = (j * T::WAVES + wave) * 64 + lane;       // 16-byte unit of the LDS image: adjacent lanes fetch the two halves of a pixel's 32 bytes
-    const int hh = f & 1, rem = f >> 1;
-    const int s = rem / T::SLICE_POS, r2 = rem % T::SLICE_POS;
-    const int yy = r2 / T::PITCH, pos = r2 % T::PITCH;
-    const int x = pos ^ T::swizzle(pos, s, yy);             // the swizzle only moves a position inside its aligned group of four
-    const bool real = f < T::A_POS && yy < T::TH + 2 && x < T::XCOLS;
-    // the x field is the column in halo coordinates (image column + 1), whichever layout the image has
-    return real ? (uint32_t)((x + (T::FULLW ? 1 : 0)) | (yy << 8) | (s << 16) | (hh << 24)) : 0xFFFFFFFFu;
-}
+// The workgroup tiles (Wino4Tile), the LDS image and the slot / fragment geometry of both source layouts: rcu_wino4_geom.h.
 
 template <class T>
 __device__ __forceinline__ WinoEpiRaw wino4_epilogue_load(const ConvArgs& a, int ntile, int n0, int wave, int lane, int r = 0)
@@ -233,19 +144,25 @@ __device__ __forceinline__ float wino4_acc(const f32x4 (&accv)[8])
 struct Wino4StorePlan {
     uint32_t out, pool;
 };
-template <class T, bool PART>
+// PAIRED (out and pooled in the paired layout): every lane stores its own cout pair kq = n & 3 of chunk n >> 2 for pixel pairs -- unit kq of the
+// pair's 64 bytes, 16 kq bytes into it where wino_out_offset counts 8 kq.
+template <class T, bool PART, bool PAIRED>
 __device__ __forceinline__ Wino4StorePlan wino4_store_plan(const ConvArgs& a, int wave, int lane)
 {
     int s, ty, tc;
     T::row_tile(wave, 4 * (lane >> 4), s, ty, tc);
     if constexpr (T::FOLD) s = ty = tc = 0;
-    const int n16 = lane & 15, odd = n16 & 1, c = 2 * n16 - 2 * odd;   // the even lane stores four couts of one pixel column, the odd lane of the next
+    const int n16 = lane & 15, odd = PAIRED ? 0 : n16 & 1, c = 2 * n16 - 2 * odd;   // the even lane stores four couts of one pixel column, the odd lane of the next
     // PART (padded levels, ConvArgs::part): `out` and `pooled` have extents of their own
     const int oH = PART ? a.out_H : a.H, oW = PART ? a.out_W : a.W;
     const int Hp = PART ? a.pool_H : a.H >> 1, Wp = PART ? a.pool_W : a.W >> 1;
     Wino4StorePlan p;
     p.out = wino_out_offset(s, oH * oW, a.CoutP, (uint32_t)(ty * oW + 4 * tc + odd), c, a.out_pix_bytes, a.out_chunk_bytes);
     p.pool = wino_out_offset(s, Hp * Wp, a.CoutP, (uint32_t)((ty >> 1) * Wp + 2 * tc + odd), c, a.pool_pix_bytes, a.pool_chunk_bytes);
+    if constexpr (PAIRED) {
+        p.out += (uint32_t)(n16 & 3) * 8u;
+        p.pool += (uint32_t)(n16 & 3) * 8u;
+    }
     return p;
 }
 
@@ -289,14 +206,16 @@ __device__ __forceinline__ void wino4_output_tile(const f32x4 (&accv)[8], const 
 // tile r of the lane's four.
 // PART: the level is padded (ConvArgs::part) -- the tile may hang over the real image: pixels at or beyond (Hr, Wr) go out of range like the
 // slices beyond the batch, and the output / pooled tensors have extents of their own.
-template <class T, bool PART = false>
+// PAIRED: `out` and `pooled` are paired tensors -- a lane stores two adjacent pixels x its two couts as they are, no lane trade.
+template <class T, bool PART = false, bool PAIRED = false>
 __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&accv)[8], const WinoEpi& ep, int ntile, int n0, int y0, int x0,
                                                int wave, int lane, const Wino4StorePlan& plan)
 {
     // every MFMA has long retired: the last chunk's barrier lies between them and this point; the nops cover the asm-to-asm case
     // (an MFMA's D read by v_accvgpr_read) the compiler cannot see
     asm volatile("s_nop 15\n\ts_nop 7");
-    const int odd = lane & 1;
+    static_assert(!(PAIRED && PART), "padded levels are never paired");
+    [[maybe_unused]] const int odd = PAIRED ? 0 : lane & 1;
     // The kernel arguments the epilogue needs, read in ONE batch of scalar loads (a wave alone on its SIMD sits out every scalar-load round
     // trip: the branches of the earlier form -- outputs alive? pooled? -- each fetched their own arguments behind the branch).
     const int H = a.H, W = a.W, CoutP = a.CoutP, N = a.N;
@@ -360,11 +279,16 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
         f32x2 y[4][4];   // [row][col], components = the two couts
         wino4_output_tile<r>(accv, ep_r, relu_floor, y);
         // Neighbouring lanes (couts 2n, 2n+1 | 2n+2, 2n+3 of the same pixels) trade pixel columns: the even lane ends up with four
-        // couts of columns 0 and 2 of the tile, the odd lane with four couts of columns 1 and 3 -> 16-byte stores.
+        // couts of columns 0 and 2 of the tile, the odd lane with four couts of columns 1 and 3 -> 16-byte stores.  PAIRED: no trade.
 #pragma unroll
         for (int aa = 0; aa < 4; ++aa) {
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
+                if constexpr (PAIRED) {
+                    const f32x4 o = {y[aa][2 * h2].x, y[aa][2 * h2].y, y[aa][2 * h2 + 1].x, y[aa][2 * h2 + 1].y};
+                    wino_store16(o, ro, vo_r, (uint32_t)(tdx + 2 * h2) * px_bytes + (uint32_t)(tdy + aa) * row_bytes);
+                    continue;
+                }
                 const f32x2 keep = odd ? y[aa][2 * h2 + 1] : y[aa][2 * h2];
                 const f32x2 send = odd ? y[aa][2 * h2] : y[aa][2 * h2 + 1];
                 f32x2 recv;
@@ -383,6 +307,10 @@ __device__ __forceinline__ void wino4_epilogue(const ConvArgs& a, const f32x4 (&
                 for (int b2 = 0; b2 < 2; ++b2)
                     mx[b2] = __builtin_elementwise_max(__builtin_elementwise_max(y[2 * a2][2 * b2], y[2 * a2][2 * b2 + 1]),
                                                        __builtin_elementwise_max(y[2 * a2 + 1][2 * b2], y[2 * a2 + 1][2 * b2 + 1]));
+                if constexpr (PAIRED) {   // the tile's two pooled pixels of the row are a pair
+                    wino_store16(f32x4{mx[0].x, mx[0].y, mx[1].x, mx[1].y}, rp, vp, (uint32_t)(2 * r) * ppx_bytes + (uint32_t)a2 * prow_bytes);
+                    continue;
+                }
                 const f32x2 keep = odd ? mx[1] : mx[0];
                 const f32x2 send = odd ? mx[0] : mx[1];
                 f32x2 recv;
@@ -507,8 +435,11 @@ __host__ __device__ constexpr int wino4_pos_of(int q) { return 6 * wino4_row_of(
 // HEAD: the classifier head in the epilogue (wino4_epilogue_head).  total_items counts the tiles of ONE pass; the workgroup that owns a tile runs
 // the tile of every pass of the group back to back (sample n0 + pass * head_images), so the passes' read-modify-writes of a voxel's statistics
 // are ordered (pass 0 first, as head_kernel adds them) -- as rcu_wino.hip.
-template <class T, bool HEAD = false, bool PART = false>
-__global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, const int total_items)
+// PAIRED: the output and pooled tensors are paired (wino4_epilogue).  Whether the SOURCES are paired is a run-time flag (ConvArgs::in_paired): it
+// only changes constants made once per kernel -- the slots' source offsets and the lane's fragment addresses.
+// The kernels: conv_wino4_stream<T, HEAD, PART> writes blocked / channels-last tensors, conv_wino4_pairs<T> paired ones (one body).
+template <class T, bool HEAD, bool PART, bool PAIRED>
+__device__ __forceinline__ void conv_wino4_body(const ConvArgs& a, const int total_items)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(1024))) float smem[];
@@ -529,27 +460,12 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
 
     // fragment addresses (dword offsets inside a buffer) of the lane's patch columns j = 0..5, for patch rows 0..3 ([0]) and 4..5
     // ([1]: the swizzle's row bit flips); the row itself is an immediate offset
+    const bool in_paired = !PART && a.in_paired != 0;   // (padded levels are never paired)
     int aCol[2][6];
-    {
-        int s, R0, tc;
-        T::row_tile(wave, m16, s, R0, tc);
-        const int base = (s * T::SLICE_POS + R0 * T::PITCH) * 8 + 2 * kq;
 #pragma unroll
-        for (int ip = 0; ip < 2; ++ip)
+    for (int ip = 0; ip < 2; ++ip)
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                int x = 4 * tc + j - (T::FULLW ? 1 : 0);   // staged column of patch column j
-                int row0 = base;
-                if (T::FULLW) {
-                    // zero padding left and right of the image: the column outside is read from the buffer's zero region -- at the position its
-                    // clamped neighbour has in a row (the row bases are multiples of 64 dwords: the same banks as the neighbour), rows 4..5 four
-                    // rows lower, so that the immediate row offsets i * PITCH * 8 stay inside the region's ZERO_ROWS slots
-                    if (x < 0 || x >= T::TW) row0 = T::ZERO_OFF - 4 * ip * T::PITCH * 8 + 2 * kq;
-                    x = min(max(x, 0), T::TW - 1);
-                }
-                aCol[ip][j] = row0 + 8 * (x ^ T::swizzle(x, s, R0 + 4 * ip));
-            }
-    }
+        for (int j = 0; j < 6; ++j) aCol[ip][j] = wino4_patch_col<T>(in_paired, wave, m16, kq, ip, j);
     const int b_addr = T::A_DW + (kq * T::BN + 2 * m16) * 2;
     const uint32_t w_voff = (uint32_t)(lane * 16);
 
@@ -567,12 +483,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
     int dp_wtile = tile.wtile, dpn_wtile = tile.wtile;
 #pragma unroll
     for (int j = 0; j < T::NA; ++j) {
-        geo[j] = wino_slot_plan<T>(a, wino4_slot_geometry<T>(j, wave, lane));   // the slot's plan: tile-independent offset | border flags
+        // the slot's plan: tile-independent offset | border flags
+        geo[j] = in_paired ? wino4_slot_plan_paired<T>(a.H, a.W, a.C1, wino4_slot_geometry_paired<T>(j, wave, lane))
+                           : wino_slot_plan<T>(a, wino4_slot_geometry<T>(j, wave, lane));
         asm volatile("" : "+v"(geo[j]));
         dp[j] = dpn[j] = wino_slot_offset(geo[j], wino_tile_offset<T>(a, tile));
     }
 
-    Wino4StorePlan store_plan = wino4_store_plan<T, PART>(a, wave, lane);
+    Wino4StorePlan store_plan = wino4_store_plan<T, PART, PAIRED>(a, wave, lane);
     asm volatile("" : "+v"(store_plan.out), "+v"(store_plan.pool));   // two registers through the loop, not their ingredients
 
     // LDS-DMA of Cin chunk kc of a tile into LDS buffer `buf`: the wave's NW weight pieces and NA input pieces of 1 KB.  No branch
@@ -837,7 +755,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
             wino4_epilogue_head<T, PART>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.n0, tile.n0 - pass * wino_cold_args().head_images, tile.y0, tile.x0,
                                          wave, lane, lds_base + (uint32_t)(T::BUF_DW + T::A_DW) * 4u, lds_base + (uint32_t)(2 * T::BUF_DW) * 4u);
         else
-            wino4_epilogue<T, PART>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.wtile, tile.n0, tile.y0, tile.x0, wave, lane, store_plan);
+            wino4_epilogue<T, PART, PAIRED>(wino_cold_args(), accv, wino_epilogue_fold(epr), tile.wtile, tile.n0, tile.y0, tile.x0, wave, lane, store_plan);
         if (!has_next) break;
         load_first();   // (no wait and no barrier here any more: the tile's last chunk waited for the next tile's first chunk at its barrier)
         if (more_passes()) {
@@ -852,6 +770,18 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, co
 #endif
 }
 
+template <class T, bool HEAD = false, bool PART = false>
+__global__ __launch_bounds__(256, 1) void conv_wino4_stream(const ConvArgs a, const int total_items)
+{
+    conv_wino4_body<T, HEAD, PART, false>(a, total_items);
+}
+
+template <class T>
+__global__ __launch_bounds__(256, 1) void conv_wino4_pairs(const ConvArgs a, const int total_items)
+{
+    conv_wino4_body<T, false, false, true>(a, total_items);
+}
+
 using W4Cfg0 = Wino4Tile<1, 2, 8, 1, 4>;   // 32x32 pixels of one slice
 using W4Cfg1 = Wino4Tile<1, 2, 8, 2, 2>;   // 16x32 pixels of two consecutive slices (heights not divisible by 32)
 using W4Cfg2 = Wino4Tile<2, 2, 4, 4, 1, true>;   // 8x16 pixels of eight consecutive slices, full image width (the 24x16 level)
@@ -860,8 +790,9 @@ using W4Cfg4 = Wino4Tile<1, 2, 8, 4, 1, true>;   // 8x32 pixels of four consecut
 
 // "S8T12x8" names the S8 block geometry the folded tile descends from (and the enum, the layer tables and the profiles know it by): the tile holds TEN
 // slices (W4Cfg3::TS).
-// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: 36 multiplications per 4x4 output tile
-static constexpr ConvFamilyTraits kWino4 = {ConvFamily::Wino4, true, true, true, true, 1, 2.25};
+// id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults, reads_paired, writes_paired: 36 multiplications per 4x4 output tile; paired
+// tensors on unpadded levels only (the planner's rule, assign_layouts)
+static constexpr ConvFamilyTraits kWino4 = {ConvFamily::Wino4, true, true, true, true, 1, 2.25, true, true};
 
 static const ConvConfigInfo kWino4Info[6] = {
     {W4Cfg0::TS, W4Cfg0::TH, W4Cfg0::TW, W4Cfg0::BN, 8, 36, "conv3x3_winograd4<T32x32,N32,K8>", 8, 0, kWino4, 1.0, CONV_CFG_WINO4_T32x32_N32_HEAD},
@@ -874,17 +805,26 @@ static const ConvConfigInfo kWino4Info[6] = {
 
 const ConvConfigInfo& wino4_config_info(int cfg) { return kWino4Info[cfg - CONV_CFG_WINO4_T32x32_N32]; }
 
-template <class T, bool HEAD, bool PART>
+template <class T, bool HEAD, bool PART, bool PAIRED = false>
 static hipError_t launch_wino4_kernel(const ConvArgs& a, hipStream_t stream)
 {
     constexpr int lds_bytes = T::LDS_BYTES + (HEAD ? WINO4_HEAD_LDS_BYTES : 0);
     static_assert(lds_bytes <= 160 * 1024, "LDS");
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&conv_wino4_stream<T, HEAD, PART>), lds_bytes);
+    static_assert(!PAIRED || (!HEAD && !PART), "paired outputs: plain conv units of unpadded levels");
+    const void* kernel;
+    if constexpr (PAIRED)
+        kernel = reinterpret_cast<const void*>(&conv_wino4_pairs<T>);
+    else
+        kernel = reinterpret_cast<const void*>(&conv_wino4_stream<T, HEAD, PART>);
+    hipError_t e = set_max_dynamic_lds(kernel, lds_bytes);
     if (e != hipSuccess) return e;
     // HEAD: the work items of one pass (TS == 1: a slice group is a sample); the kernel runs every pass of the group on each
     const unsigned items = (unsigned)a.NT * a.tiles_x * a.tiles_y * (HEAD ? a.head_images : a.slice_groups);
     const unsigned grid = wino_persistent_grid(items);
-    hipLaunchKernelGGL((conv_wino4_stream<T, HEAD, PART>), dim3(grid), dim3(T::THREADS), lds_bytes, stream, a, (int)items);
+    if constexpr (PAIRED)
+        hipLaunchKernelGGL((conv_wino4_pairs<T>), dim3(grid), dim3(T::THREADS), lds_bytes, stream, a, (int)items);
+    else
+        hipLaunchKernelGGL((conv_wino4_stream<T, HEAD, PART>), dim3(grid), dim3(T::THREADS), lds_bytes, stream, a, (int)items);
     return hipGetLastError();
 }
 
@@ -905,7 +845,14 @@ static hipError_t launch_wino4_cfg(const ConvArgs& a, hipStream_t stream)
                    (size_t)a.N * a.out_H * a.out_W * a.CoutP * 4 >= ((size_t)1 << 31) ||
                    (a.pooled != nullptr && (a.pool_H < (a.Hr >> 1) || a.pool_W < (a.Wr >> 1)))))
         return hipErrorInvalidValue;
+    // paired tensors: whole tiles of unpadded levels with even widths; the sources in the chunk stride of the blocked layout
+    if ((a.in_paired || a.out_paired) && (a.part || (a.W & 1) != 0)) return hipErrorInvalidValue;
+    if (a.in_paired && (a.in_pix_bytes != 32u || a.in_chunk_bytes != (uint32_t)(a.H * a.W) * 32u)) return hipErrorInvalidValue;
+    if (a.out_paired && (HEAD || a.out_pix_bytes != 32u || (a.pooled != nullptr && (a.pool_pix_bytes != 32u || ((a.W >> 1) & 1) != 0))))
+        return hipErrorInvalidValue;
     if (a.part) return launch_wino4_kernel<T, HEAD, true>(a, stream);
+    if constexpr (!HEAD)
+        if (a.out_paired) return launch_wino4_kernel<T, false, false, true>(a, stream);
     return launch_wino4_kernel<T, HEAD, false>(a, stream);
 }
 

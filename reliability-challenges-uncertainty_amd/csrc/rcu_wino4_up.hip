@@ -13,7 +13,7 @@
 //
 // Everything else is rcu_wino4.hip's design: one wave per SIMD (a wave owns 16 tiles x 32 couts x 25 positions = 200 accumulator registers, kept
 // in the accumulator file by inline assembly), a workgroup of 4 waves per CU, persistent grid in XCD-aware order, staging by LDS-DMA only with
-// the swizzle on the source side, a double-buffered Cin-chunk pipeline running across the tiles of a workgroup, 16-byte stores.  What differs:
+// the swizzle on the source side, a double-buffered Cin-chunk pipeline running across the tiles of a workgroup, 16-byte stores (paired tensors: without the lane trade).  What differs:
 //   * the LDS input image is the LOW-resolution tile + a 1-pixel halo (18x18 positions for a 32x32 output tile), [slice][halo row][position]
 //     [8 channels], position = x ^ (((x >> 3) ^ slice) & 1): tiles are 2 positions = 16 dwords apart, so the 16 tiles x 2 channel pairs a
 //     ds_read_b64 serves per cycle fall two by two on the 32 two-dword slots of the 64 banks, as in rcu_wino4.hip;
@@ -21,59 +21,11 @@
 //   * the epilogue adds the bias and stores: an UpConv has no dropout, BatchNorm, ReLU or pool; K is single-source.
 // The tile grid walks the low-resolution level (ConvArgs::H x W), the geometry names are those of the OUTPUT tile.
 #include "rcu_wino_common.h"
+#include "rcu_wino4_geom.h"
 
 namespace rcu {
 
-// Workgroup tile on the output grid: WS slice groups x WR block rows of MFMA row blocks; a block = SB slices x BR tile rows x BC tile columns = 16
-// tiles of 4x4 output pixels spanning the tile's full width (Wino4Tile of rcu_wino4.hip).  TH x TW is the LOW-resolution tile the staging helpers
-// of rcu_wino_common.h see.
-template <int SB_, int BR_, int BC_, int WS_, int WR_>
-struct Up4Tile {
-    static constexpr int SB = SB_, BR = BR_, BC = BC_, WS = WS_, WR = WR_;
-    static constexpr int TS = SB * WS, OTH = 4 * BR * WR, OTW = 4 * BC;      // output pixels
-    static constexpr int TH = OTH / 2, TW = OTW / 2;                         // low-resolution pixels
-    static constexpr int BN = 32, KC = 8, THREADS = 256, WAVES = 4, NPOS = 25;
-    static constexpr int XCOLS = TW + 2;                                     // staged pixel columns per row: x = -1 .. TW
-    static constexpr int PITCH = (XCOLS + 3) / 4 * 4;                        // positions per halo row
-    static constexpr int SLICE_POS = ((TH + 2) * PITCH + 15) / 16 * 16;      // positions per slice image, a multiple of 16
-    static constexpr int A_POS = 2 * TS * SLICE_POS;                         // 16-byte units: [slice][halo row][position][channel half]
-    static constexpr int A_PIECES = (A_POS + 63) / 64;
-    static constexpr int NA = (A_PIECES + WAVES - 1) / WAVES;
-    static constexpr int A_DW = A_PIECES * 256;
-    static constexpr int W_DW = NPOS * 4 * BN * 2;                           // [p][channel pair][cout][2]
-    static constexpr int W_PIECES = W_DW / 256;
-    static constexpr int NW = (W_PIECES + WAVES - 1) / WAVES;
-    static constexpr int BUF_DW = A_DW + W_DW;
-    static constexpr int LDS_BYTES = 2 * BUF_DW * 4;
-    static_assert(SB * BR * BC == 16 && WS * WR == WAVES && BC % 4 == 0, "block geometry");
-    static_assert(W_DW % 256 == 0 && LDS_BYTES <= 160 * 1024, "LDS");
-    // wave -> (first slice of its block inside the tile, top OUTPUT pixel row of its block inside the slice tile)
-    static __device__ __forceinline__ void block_origin(int wave, int& s, int& y)
-    {
-        s = (wave / WR) * SB;
-        y = (wave % WR) * (4 * BR);
-    }
-    // tile m of a block -> (slice inside the block, tile row, tile column)
-    static __device__ __forceinline__ void tile_of(int m, int& sb, int& tr, int& tc)
-    {
-        sb = m / (BR * BC);
-        tr = (m / BC) % BR;
-        tc = m % BC;
-    }
-    static __device__ __forceinline__ int swizzle(int x, int s) { return ((x >> 3) ^ s) & 1; }
-};
-
-template <class T>
-__device__ __forceinline__ uint32_t up4_slot_geometry(int j, int wave, int lane)
-{
-    const int f = (j * T::WAVES + wave) * 64 + lane;       // 16-byte unit of the LDS image: adjacent lanes fetch the two halves of a pixel's 32 bytes
-    const int hh = f & 1, rem = f >> 1;
-    const int s = rem / T::SLICE_POS, r2 = rem % T::SLICE_POS;
-    const int yy = r2 / T::PITCH, pos = r2 % T::PITCH;
-    const int x = pos ^ T::swizzle(pos, s);                 // the swizzle swaps the two positions of an aligned pair
-    const bool real = f < T::A_POS && yy < T::TH + 2 && x < T::XCOLS;
-    return real ? (uint32_t)(x | (yy << 8) | (s << 16) | (hh << 24)) : 0xFFFFFFFFu;   // (x, yy): halo coordinates, pixel + 1
-}
+// The workgroup tiles (Up4Tile), the LDS image and the slot / fragment geometry of both source layouts: rcu_wino4_geom.h.
 
 // 200 accumulator registers per lane: 50 tuples of 4 in the accumulator file a[0:199], owned by the inline assembly below as in rcu_wino4.hip (see
 // there for the why, the s_nop 1 that opens every MFMA and the audit: tests/test_upconv4_cpu.py).
@@ -152,13 +104,14 @@ __device__ __forceinline__ void up4_output_tile(const f32x2 bias, f32x2 (&y)[4][
 
 // Output transform + bias + stores of one finished tile; (y0, x0): the work item's origin on the OUTPUT grid.  `plan`: the lane's part of the store
 // offset (slice, pixel and cout pair of its first tile relative to the workgroup tile's origin and cout tile), made once per kernel.
-template <class T>
+// PAIRED: `out` is a paired tensor (rcu_wino4_geom.h) -- a lane stores two adjacent pixels x its two couts as they are, no lane trade.
+template <class T, bool PAIRED>
 __device__ __forceinline__ void up4_epilogue(const ConvArgs& a, const f32x2 bias, int ntile, int n0, int y0, int x0, int lane, uint32_t plan)
 {
     // every MFMA has long retired: the last chunk's barrier lies between them and this point; the nops cover the asm-to-asm case
     // (an MFMA's D read by v_accvgpr_read) the compiler cannot see
     asm volatile("s_nop 15\n\ts_nop 7");
-    const int odd = lane & 1;
+    [[maybe_unused]] const int odd = lane & 1;
     const int oH = 2 * a.H, oW = 2 * a.W, CoutP = a.CoutP, N = a.N;   // one batch of scalar loads
     const uint32_t px_bytes = a.out_pix_bytes, chunk_bytes = a.out_chunk_bytes;
     float* const out = a.out;
@@ -176,6 +129,11 @@ __device__ __forceinline__ void up4_epilogue(const ConvArgs& a, const f32x2 bias
         for (int aa = 0; aa < 4; ++aa) {
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
+                if constexpr (PAIRED) {
+                    const f32x4 o = {y[aa][2 * h2].x, y[aa][2 * h2].y, y[aa][2 * h2 + 1].x, y[aa][2 * h2 + 1].y};
+                    wino_store16(o, ro, vo, (uint32_t)(4 * r + 2 * h2) * px_bytes + (uint32_t)aa * row_bytes);
+                    continue;
+                }
                 const f32x2 keep = odd ? y[aa][2 * h2 + 1] : y[aa][2 * h2];
                 const f32x2 send = odd ? y[aa][2 * h2] : y[aa][2 * h2 + 1];
                 f32x2 recv;
@@ -188,8 +146,10 @@ __device__ __forceinline__ void up4_epilogue(const ConvArgs& a, const f32x2 bias
     });
 }
 
-template <class T>
-__global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, const int total_items)
+// PAIRED: the output tensor is paired (up4_epilogue); whether the source is paired is a run-time flag (ConvArgs::in_paired), as in rcu_wino4.hip.
+// The kernels: up_wino4_stream<T> writes a blocked / channels-last tensor, up_wino4_pairs<T> a paired one (one body).
+template <class T, bool PAIRED>
+__device__ __forceinline__ void up_wino4_body(const ConvArgs& a, const int total_items)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(1024))) float smem[];
@@ -208,19 +168,10 @@ __global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, cons
 
     // fragment addresses (dword offsets inside a buffer) of the lane's patch columns j = 0..3 in patch row 0; the row is an immediate offset.
     // Output tile (row oy, column ox) reads low-resolution rows oy / 2 - 1 .. oy / 2 + 2 = halo rows oy / 2 .. oy / 2 + 3, and columns alike.
+    const bool in_paired = a.in_paired != 0;
     int aCol[4];
-    {
-        int bs, by, sb, tr, tc;
-        T::block_origin(wave, bs, by);
-        T::tile_of(m16, sb, tr, tc);
-        const int s = bs + sb, R0 = (by + 4 * tr) >> 1;
-        const int base = (s * T::SLICE_POS + R0 * T::PITCH) * 8 + 2 * kq;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int x = 2 * tc + j;
-            aCol[j] = base + 8 * (x ^ T::swizzle(x, s));
-        }
-    }
+    for (int j = 0; j < 4; ++j) aCol[j] = up4_patch_col<T>(in_paired, wave, m16, kq, j);
     const int b_addr = T::A_DW + (kq * T::BN + 2 * m16) * 2;
     const uint32_t w_voff = (uint32_t)(lane * 16);
 
@@ -231,7 +182,9 @@ __global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, cons
     int dp_wtile = tile.wtile;
 #pragma unroll
     for (int j = 0; j < T::NA; ++j) {
-        geo[j] = wino_slot_plan<T>(a, up4_slot_geometry<T>(j, wave, lane));   // the slot's plan: tile-independent offset | border flags
+        // the slot's plan: tile-independent offset | border flags
+        geo[j] = in_paired ? wino4_slot_plan_paired<T>(a.H, a.W, a.C1, wino4_slot_geometry_paired<T>(j, wave, lane))
+                           : wino_slot_plan<T>(a, up4_slot_geometry<T>(j, wave, lane));
         asm volatile("" : "+v"(geo[j]));
         dp[j] = wino_slot_offset(geo[j], wino_tile_offset<T>(a, tile));
     }
@@ -242,9 +195,12 @@ __global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, cons
         int bs, by, sb, tr, tc;
         T::block_origin(wave, bs, by);
         T::tile_of(4 * (lane >> 4), sb, tr, tc);
-        const int n16 = lane & 15, odd = n16 & 1, c = 2 * n16 - 2 * odd;   // the even lane stores four couts of one pixel column, the odd lane of the next
+        // the even lane stores four couts of one pixel column, the odd lane of the next; PAIRED: every lane its own cout pair kq = n & 3 of pixel pairs
+        // (unit kq of the pair's 64 bytes: 16 kq bytes into it where wino_out_offset counts 8 kq)
+        const int n16 = lane & 15, odd = PAIRED ? 0 : n16 & 1, c = 2 * n16 - 2 * odd;
         const int oH = 2 * a.H, oW = 2 * a.W;
         store_plan = wino_out_offset(bs + sb, oH * oW, a.CoutP, (uint32_t)((by + 4 * tr) * oW + 4 * tc + odd), c, a.out_pix_bytes, a.out_chunk_bytes);
+        if constexpr (PAIRED) store_plan += (uint32_t)(n16 & 3) * 8u;
         asm volatile("" : "+v"(store_plan));
     }
 
@@ -423,7 +379,7 @@ __global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, cons
             chunk(std::integral_constant<int, 0>{}, std::false_type{}, kc, dA, dB, bvA, bvB);
             chunk(std::integral_constant<int, 1>{}, std::false_type{}, kc + 1, dB, dA, bvB, bvA);
         }
-        up4_epilogue<T>(wino_cold_args(), bias, tile.wtile, tile.n0, 2 * tile.y0, 2 * tile.x0, lane, store_plan);
+        up4_epilogue<T, PAIRED>(wino_cold_args(), bias, tile.wtile, tile.n0, 2 * tile.y0, 2 * tile.x0, lane, store_plan);
         if (!has_next) break;
         load_first();   // (no wait and no barrier here: the tile's last chunk waited for the next tile's first chunk at its barrier)
         item += (int)gridDim.x;
@@ -433,6 +389,18 @@ __global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, cons
 #endif
 }
 
+template <class T>
+__global__ __launch_bounds__(256, 1) void up_wino4_stream(const ConvArgs a, const int total_items)
+{
+    up_wino4_body<T, false>(a, total_items);
+}
+
+template <class T>
+__global__ __launch_bounds__(256, 1) void up_wino4_pairs(const ConvArgs a, const int total_items)
+{
+    up_wino4_body<T, true>(a, total_items);
+}
+
 using U4Cfg0 = Up4Tile<1, 2, 8, 1, 4>;   // 32x32 output pixels of one slice (16x16 low-resolution)
 using U4Cfg1 = Up4Tile<1, 2, 8, 2, 2>;   // 16x32 output pixels of two consecutive slices (output heights not divisible by 32)
 using U4Cfg2 = Up4Tile<2, 2, 4, 4, 1>;   // 8x16 output pixels of eight consecutive slices (the 24x16 level)
@@ -440,7 +408,7 @@ using U4Cfg2 = Up4Tile<2, 2, 4, 4, 1>;   // 8x16 output pixels of eight consecut
 // TH x TW: the low-resolution tile, as the sub-pixel kernels report it (the tile grid walks the low-resolution level)
 // id, winograd, reads_blocked, writes_blocked, part, weight_sets, mults: both layouts, but whole tiles of unpadded levels only (no ConvArgs::part
 // form); 25 multiplications per 4x4 output tile = 2x2 low-resolution pixels
-static constexpr ConvFamilyTraits kWino4Up = {ConvFamily::Wino4Up, true, true, true, false, 1, 6.25};
+static constexpr ConvFamilyTraits kWino4Up = {ConvFamily::Wino4Up, true, true, true, false, 1, 6.25, true, true};
 
 static const ConvConfigInfo kWino4UpInfo[3] = {
     {U4Cfg0::TS, U4Cfg0::TH, U4Cfg0::TW, U4Cfg0::BN, 8, 25, "upconv_winograd4<T32x32,N32,K8>", 8, 0, kWino4Up},
@@ -449,6 +417,25 @@ static const ConvConfigInfo kWino4UpInfo[3] = {
 };
 
 const ConvConfigInfo& wino4_up_config_info(int cfg) { return kWino4UpInfo[cfg - CONV_CFG_UPW4_T32x32_N32]; }
+
+template <class T, bool PAIRED>
+static hipError_t launch_wino4_up_kernel(const ConvArgs& a, hipStream_t stream)
+{
+    const void* kernel;
+    if constexpr (PAIRED)
+        kernel = reinterpret_cast<const void*>(&up_wino4_pairs<T>);
+    else
+        kernel = reinterpret_cast<const void*>(&up_wino4_stream<T>);
+    hipError_t e = set_max_dynamic_lds(kernel, T::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    const unsigned items = (unsigned)a.NT * a.tiles_x * a.tiles_y * a.slice_groups;
+    const unsigned grid = wino_persistent_grid(items);
+    if constexpr (PAIRED)
+        hipLaunchKernelGGL((up_wino4_pairs<T>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, stream, a, (int)items);
+    else
+        hipLaunchKernelGGL((up_wino4_stream<T>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, stream, a, (int)items);
+    return hipGetLastError();
+}
 
 template <class T>
 static hipError_t launch_wino4_up_cfg(const ConvArgs& a, hipStream_t stream)
@@ -463,12 +450,10 @@ static hipError_t launch_wino4_up_cfg(const ConvArgs& a, hipStream_t stream)
         (size_t)a.N * out_slice >= ((size_t)1 << 31) || (size_t)(a.N + T::TS) * in_slice >= ((size_t)1 << 32) ||
         (size_t)(a.N + T::TS) * out_slice >= ((size_t)1 << 32))
         return hipErrorInvalidValue;
-    hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(&up_wino4_stream<T>), T::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    const unsigned items = (unsigned)a.NT * a.tiles_x * a.tiles_y * a.slice_groups;
-    const unsigned grid = wino_persistent_grid(items);
-    hipLaunchKernelGGL((up_wino4_stream<T>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, stream, a, (int)items);
-    return hipGetLastError();
+    // paired tensors: even widths, the chunk stride of the blocked layout
+    if (a.in_paired && ((a.W & 1) != 0 || a.in_pix_bytes != 32u || a.in_chunk_bytes != (uint32_t)(a.H * a.W) * 32u)) return hipErrorInvalidValue;
+    if (a.out_paired && a.out_pix_bytes != 32u) return hipErrorInvalidValue;
+    return a.out_paired ? launch_wino4_up_kernel<T, true>(a, stream) : launch_wino4_up_kernel<T, false>(a, stream);
 }
 
 hipError_t launch_upconv_wino4(int cfg, const ConvArgs& a, hipStream_t stream)

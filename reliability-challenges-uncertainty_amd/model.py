@@ -536,6 +536,18 @@ class UNet(nn.Module):
                              mfma_flops_per_slice=info.mfma_flops_per_slice))
         return rows
 
+    def layer_layouts(self, h, w, n=1):
+        """Per layer of the plan, the activation layouts (0 channels-last, 1 channel-blocked, 2 paired; -1: no such tensor) of its source, second
+        source, output and pooled output (include/rcu.h rcu_unet_layer_layouts)."""
+        lib = _lib.load()
+        handle = self._handle(h, w, n)
+        rows = []
+        for i in range(lib.rcu_unet_num_layers(handle)):
+            v = [ctypes.c_int32() for _ in range(4)]
+            _lib.check(lib.rcu_unet_layer_layouts(handle, i, *[ctypes.byref(x) for x in v]))
+            rows.append(tuple(x.value for x in v))
+        return rows
+
     def run_layer(self, h, w, n, layer, masks=None):
         _lib.check(_lib.load().rcu_unet_run_layer(self._handle(h, w, n), layer, n, _lib.ptr(masks),
                                                   _lib.current_stream()))

@@ -35,7 +35,8 @@ def short(name):
         flags = [f.strip() for f in flags.group(1).split(',') if f.strip()] if flags else []
         head = kind == 'conv' and bool(flags) and flags[0] in ('true', '1')
         return '{}<{},N{},K8>{}'.format('conv3x3_winograd' if kind == 'conv' else 'upconv_winograd', tile, bn, '+head' if head else '')
-    m = re.search(r'conv_wino4_stream<rcu::Wino4Tile<(\d+), (\d+), (\d+), (\d+), (\d+)(?:, (\w+))?(?:, (\w+))?>(?:, (\w+))?', name)
+    # (conv_wino4_pairs<T>: the same kernel writing paired tensors -- one row per tile with conv_wino4_stream, as in rcu_unet_layer_info)
+    m = re.search(r'conv_wino4_(?:stream|pairs)<rcu::Wino4Tile<(\d+), (\d+), (\d+), (\d+), (\d+)(?:, (\w+))?(?:, (\w+))?>(?:, (\w+))?', name)
     if m:   # block = SB slices x BR x BC tiles of 4x4 pixels, workgroup = WS x WR blocks; the tile's last flag: the folded 12x8 geometry;
             # the kernel's first flag behind the tile: the classifier head in the epilogue
         sb, br, bc, ws, wr = (int(v) for v in m.groups()[:5])
